@@ -2,6 +2,8 @@
 """Headline bench: whole-slide tile batches through the HIP compress -> decompress hot path.
 
     python bench.py --gpus N --steps K --warmup W          (N>1: launched by torch.distributed.run)
+    python bench.py ... --full                             (+ the side measurements listed below)
+    python bench.py ... --dump-outputs DIR                 (+ the last timed step's per-tile records as DIR/*.npy)
 
 A step = one pass of the hot path over one batch of synthetic 1024x1024x3 histology tiles that is
 already resident in HBM: analysis conv stack + GDN -> quantise -> rANS encode (chunk bitstreams in
@@ -14,6 +16,11 @@ Arithmetic.  Default `f16x3`: every fp32 operand of the conv / GDN contraction i
 halves and a product is three v_mfma_f32_32x32x16_f16 (fp32 accumulate, 22 significant bits; range
 guard with fp32 repeat, include/cae_hip.h).  `--precision fp32` = exact v_mfma_f32_32x32x2_f32.
 
+A plain run sets up, warms up, times the K steps and prints the line; everything marked [full] below is measured only
+with `--full`.  `--dump-outputs DIR` writes DIR/tile_stats.npy after the timed steps: the (tiles, 3) float64 records
+[compressed bytes, sum of squared error, pixel samples] that SlideCoder.run returned for the last timed step, every
+rank's tiles in rank order.
+
 Objects in the line besides the driver's contract:
   roofline      dominant fused kernel (conv/deconv + GDN).  `achieved` = MFMA FLOP/s the kernel ISSUES
                 (f16x3: 3 per algorithmic FLOP) from the algorithmic FLOP of one launch / its HIP-event time
@@ -22,16 +29,16 @@ Objects in the line besides the driver's contract:
                 `frac` = achieved / peak (<= 1 by construction).  `algorithmic_tflops` and
                 `algorithmic_vs_fp32_mfma_peak` are the same time against the useful fp32 work.
                 `traffic` = HBM bytes per launch from committed rocprofv3 PMC passes (offline; `traffic_source`).
-  fp32_path     (N=1) a short run of the same workload on the exact-fp32 kernels
-  tile256       (N=1) a short run on 256x256x3 tiles, 512 per step
-  cpu_baseline  the CPU oracle (torch-CPU conv + restated GDN + C rANS) on a bounded sample of the
+  fp32_path     [full] (N=1) a short run of the same workload on the exact-fp32 kernels
+  tile256       [full] (N=1) a short run on 256x256x3 tiles, 512 per step
+  cpu_baseline  [full] the CPU oracle (torch-CPU conv + restated GDN + C rANS) on a bounded sample of the
                 same tiles on this host's cores -- a reported baseline, not the target
-  parity_vs_cpu the GPU path against that oracle on the very same tiles: bpp, PSNR, bitstreams, pixels
-  host_8cpu     (N=1) the same round trip in a child process restricted to 8 CPUs (--cpus 8): the host budget per GPU, measured
-  low_rate_state (N=1) the same workload with a low-rate synthetic state (~0.9 bpp instead of 4): brackets the host coder's cost
-  train         (N=1) BASELINE config 5: train.train_step on 256x256 patches, batch 16 and 128, against the mixed
+  parity_vs_cpu [full] the GPU path against that oracle on the very same tiles: bpp, PSNR, bitstreams, pixels
+  host_8cpu     [full] (N=1) the same round trip in a child process restricted to 8 CPUs (--cpus 8): the host budget per GPU, measured
+  low_rate_state [full] (N=1) the same workload with a low-rate synthetic state (~0.9 bpp instead of 4): brackets the host coder's cost
+  train         [full] (N=1) BASELINE config 5: train.train_step on 256x256 patches, batch 16 and 128, against the mixed
                 bf16-conv / fp32-GDN roofline
-  dropin        (N=1) the reference's OWN call pattern: 1 / 8 / 16 Python threads calling codec.encode(chunk) /
+  dropin        [full] (N=1) the reference's OWN call pattern: 1 / 8 / 16 Python threads calling codec.encode(chunk) /
                 codec.decode(buf) one 1024^2 chunk at a time on one shared codec (dask's threaded scheduler,
                 compress.py:121-128), host memory in, host memory out: tiles/s of each direction, next to the
                 pipelined SlideCoder number above (which codes AND decodes every tile)
@@ -165,6 +172,23 @@ def batch_variants(tiles_dev, n):
            lambda t: t.flip(1).flip(2), lambda t: t.transpose(1, 2).flip(1), lambda t: t.transpose(1, 2).flip(2),
            lambda t: t.transpose(1, 2).flip(1).flip(2)]
     return [ops[i % len(ops)](tiles_dev).contiguous() for i in range(max(1, min(n, len(ops))))]
+
+
+def histo_tiles(n, h, first_index=0):
+    """synth.histo_tiles, the same array, generated on a thread pool: every tile has a seed of its own, and one 1024^2 tile
+    takes about a second of single-threaded scipy filtering, which would otherwise dominate the set-up of a run."""
+    from concurrent.futures import ThreadPoolExecutor
+    from cnn_autoencoder_amd import synth
+    workers = max(1, min(n, len(os.sched_getaffinity(0)), 16))
+    with ThreadPoolExecutor(workers) as pool:
+        return np.stack(list(pool.map(lambda i: synth.histo_tile(h, first_index + i), range(n))))
+
+
+def dump_outputs(out_dir, all_stats, world, steps, batch):
+    """The per-tile records of the last timed step, every rank's in rank order -> out_dir/tile_stats.npy (float64)."""
+    last = all_stats.detach().cpu().double().reshape(world, steps, batch, -1)[:, -1].reshape(world * batch, -1)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, 'tile_stats.npy'), last.numpy())
 
 
 def kernel_table(cfg, H, B, enc_ms, enc_calls, dec_ms, dec_calls, precision):
@@ -350,8 +374,14 @@ def main():
     ap.add_argument('--distinct', type=int, default=0,
                     help='distinct synthetic tiles per rank (0 = one per batch slot); 4 flip/transpose variants of the '
                          'batch are cycled over the steps')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-sub-runs', action='store_true', help='skip the fp32_path / tile256 side runs')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure everything besides the headline: CPU baseline and parity against it, drop-in call '
+                         'pattern, fp32_path / tile256 / low_rate_state / host_8cpu side runs, training')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write the per-tile records of the last step to DIR/tile_stats.npy '
+                         '(git ignores bench_outputs/)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline and the parity')
+    ap.add_argument('--no-sub-runs', action='store_true', help='with --full: skip the side runs and the training')
     ap.add_argument('--precision', choices=['f16x3', 'fp32'], default='f16x3',
                     help='conv/GDN arithmetic: f16x3 = operands split into two f16 halves, 3 f16 MFMAs per product, '
                          'fp32 accumulate (fp32-class accuracy); fp32 = exact v_mfma_f32_32x32x2_f32')
@@ -398,13 +428,15 @@ def main():
     B = args.batch
     n_distinct = B if args.distinct <= 0 else min(args.distinct, B)
     first = rank * B  # this rank's own tiles
-    base = synth.histo_tiles(n_distinct, H, first_index=first)
+    base = histo_tiles(n_distinct, H, first_index=first)
     reps = (B + n_distinct - 1) // n_distinct
     tiles_host = np.concatenate([base] * reps)[:B]
     tiles_dev = torch.from_numpy(tiles_host).to(dev)
     batches = batch_variants(tiles_dev, 4)
 
     dt, all_stats, prof = profiled_run(coder, batches, args.steps, args.warmup, world, dist, cdev)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, all_stats, world, args.steps, B)
 
     if rank == 0:
         total_tiles = world * args.steps * B
@@ -479,7 +511,7 @@ def main():
             line['host_cpu_ms_per_step'] = {k: 1e3 * coder.timers[k] / args.steps * threads[k.split('_')[1]]
                                             for k in ('host_encode', 'host_decode')}
         line['cpu_baseline'] = None
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             report, per_tile, cpu_payloads, cpu_recs, cpu_latents = cpu_baseline(state, cfg, list(tiles_host[:16]))
             line['cpu_baseline'] = report
             # the GPU path on exactly the tiles the oracle coded (BASELINE's "PSNR/bpp parity" at full tile size)
@@ -506,7 +538,7 @@ def main():
             for name, cd in ((args.precision, coder), ('fp32' if f16 else 'f16x3', ref32)):
                 line['parity_vs_cpu'][name] = flip_report(cd.enc, cd.eb, tiles_dev[:n].contiguous(), cpu_latents)
             del ref32
-        if world == 1 and not args.no_sub_runs:
+        if world == 1 and args.full and not args.no_sub_runs:
             sys.path.insert(0, os.path.join(ROOT, 'tools'))
             import dropin_bench
             d = dropin_bench.measure(coder.codec, tiles_host, (1, 8, 16), budget_s=1.5)

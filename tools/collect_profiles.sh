@@ -1,6 +1,6 @@
 #!/bin/bash
 # Collects the round's profile artifacts on the GPU box into gpurun_out/r03/ (copy what is to be judged into profiles/).
-#   1. un-profiled bench line (default command)
+#   1. un-profiled bench line with every side measurement (--full)
 #   2. rocprofv3 --kernel-trace --stats of a shorter run            -> kernel summary
 #   3. separate --pmc passes: FETCH_SIZE | WRITE_SIZE | busy / wait  -> HBM traffic per launch, clock, MFMA busy
 # (counters are collected in runs of their own, with --kernel-trace only: gpurun refuses other trace domains with --pmc)
@@ -9,7 +9,7 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/r03
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-python3 $R/bench.py > $O/bench_f16x3.json 2> $O/bench_f16x3.err < /dev/null
+python3 $R/bench.py --full > $O/bench_f16x3.json 2> $O/bench_f16x3.err < /dev/null
 echo "bench done" >> $O/progress.txt
 ARGS="--steps 24 --warmup 2 --no-cpu-baseline --no-sub-runs"
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o p -- python3 $R/bench.py $ARGS > $O/stats_bench.json 2> $O/stats.err < /dev/null
