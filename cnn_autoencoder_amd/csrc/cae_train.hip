@@ -525,10 +525,24 @@ int cae_t_corr_s1(const void *x16, int n, int h, int w, int ck, const void *pack
     return stride1_corr(x16, n, h, w, ck, packed, ks, mode, out32, out16, cn, bias, act, (hipStream_t)stream);
 }
 
+static int pointwise_impl(const void *x16, int n, int h, int w, int ck, const void *packed, float *out32, void *out16, int cn,
+                          const float *bias, int act, int acc, hipStream_t st);
+
 int cae_t_pointwise(const void *x16, int n, int h, int w, int ck, const void *packed, float *out32, void *out16, int cn,
                     const float *bias, int act, void *stream) {
     if (!x16 || !packed || (!out32 && !out16)) return fail(CAE_ERR_ARG, "NULL argument");
     if (n < 1 || h < 1 || w < 1 || act < 0 || act > 2) return fail(CAE_ERR_ARG, "bad shape or activation");
+    return pointwise_impl(x16, n, h, w, ck, packed, out32, out16, cn, bias, act, 0, (hipStream_t)stream);
+}
+
+int cae_t_pointwise_acc(const void *x16, int n, int h, int w, int ck, const void *packed, float *out32, int cn, void *stream) {
+    if (!x16 || !packed || !out32) return fail(CAE_ERR_ARG, "NULL argument");
+    if (n < 1 || h < 1 || w < 1) return fail(CAE_ERR_ARG, "bad shape");
+    return pointwise_impl(x16, n, h, w, ck, packed, out32, nullptr, cn, nullptr, 0, 1, (hipStream_t)stream);
+}
+
+static int pointwise_impl(const void *x16, int n, int h, int w, int ck, const void *packed, float *out32, void *out16, int cn,
+                          const float *bias, int act, int acc, hipStream_t st) {
     GGArgs a{};
     a.in = x16;
     a.out32 = out32;
@@ -548,10 +562,53 @@ int cae_t_pointwise(const void *x16, int n, int h, int w, int ck, const void *pa
     a.SO = 1;
     a.reflect = 0;
     a.act = act;
+    a.acc = acc;
     a.ktaps = 1;
     a.ntaps = 1;
     a.dy[0] = a.dx[0] = a.wt[0] = 0;
-    return launch_gg(a, (hipStream_t)stream);
+    return launch_gg(a, st);
+}
+
+int cae_t_col2im_s1r(const float *u32, const float *bias, int n, int c, int h, int w, int ks, int kp, float *out_nchw,
+                     void *stream) {
+    if (!u32 || !out_nchw) return fail(CAE_ERR_ARG, "NULL argument");
+    if (n < 1 || c < 1 || c > 3 || (ks != 3 && ks != 5) || kp % 32 || kp < ks * ks * c || kp > 96)
+        return fail(CAE_ERR_ARG, "bad shape (1 to 3 channels, kernel_size 3 or 5, kp = pad32(k * k * c) <= 96)");
+    if (h <= ks / 2 || w <= ks / 2) return fail(CAE_ERR_ARG, "image %d x %d too small for reflect padding %d", h, w, ks / 2);
+    hipLaunchKernelGGL(col2im_s1r_kernel, dim3(ew_grid((size_t)n * h * w)), dim3(256), 0, (hipStream_t)stream, u32, bias,
+                       out_nchw, n, c, h, w, ks, kp);
+    HIP_TRY(hipGetLastError());
+    return CAE_OK;
+}
+
+int cae_t_im2col_s1r(const float *g_nchw, int n, int c, int h, int w, int ks, int kp, void *out16, void *stream) {
+    if (!g_nchw || !out16) return fail(CAE_ERR_ARG, "NULL argument");
+    if (n < 1 || c < 1 || c > 3 || (ks != 3 && ks != 5) || kp % 32 || kp < ks * ks * c || kp > 96)
+        return fail(CAE_ERR_ARG, "bad shape (1 to 3 channels, kernel_size 3 or 5, kp = pad32(k * k * c) <= 96)");
+    if (h <= ks / 2 || w <= ks / 2) return fail(CAE_ERR_ARG, "image %d x %d too small for reflect padding %d", h, w, ks / 2);
+    hipLaunchKernelGGL(im2col_s1r_kernel, dim3(ew_grid((size_t)n * h * w * (kp / 8))), dim3(256), 0, (hipStream_t)stream,
+                       g_nchw, (__bf16 *)out16, n, c, h, w, ks, kp);
+    HIP_TRY(hipGetLastError());
+    return CAE_OK;
+}
+
+int cae_t_fold_acc(const float *gext32, int n, int h, int w, int pad, int cp, float *out32, void *stream) {
+    if (!gext32 || !out32) return fail(CAE_ERR_ARG, "NULL argument");
+    if (n < 1 || h <= pad || w <= pad || pad < 0 || cp % 32) return fail(CAE_ERR_ARG, "bad shape");
+    hipLaunchKernelGGL(fold_acc_kernel, dim3(ew_grid((size_t)n * h * w * cp)), dim3(256), 0, (hipStream_t)stream,
+                       FoldSrc{gext32, h, w, pad}, out32, n, cp);
+    HIP_TRY(hipGetLastError());
+    return CAE_OK;
+}
+
+int cae_t_pyramid_down(const float *x_nchw, int n, int c, int h, int w, float *out_nchw, void *stream) {
+    if (!x_nchw || !out_nchw) return fail(CAE_ERR_ARG, "NULL argument");
+    if (n < 1 || c < 1 || h < 2 || w < 2) return fail(CAE_ERR_ARG, "bad shape (the pyramid step needs h, w >= 2)");
+    const int oh = h / 2, ow = w / 2;
+    hipLaunchKernelGGL(pyramid_down_kernel, dim3(ew_grid((size_t)n * c * oh * ow)), dim3(256), 0, (hipStream_t)stream, x_nchw,
+                       out_nchw, n * c, h, w, oh, ow);
+    HIP_TRY(hipGetLastError());
+    return CAE_OK;
 }
 
 int cae_t_wgrad_pointwise(const void *x16, const void *y16, int n, int h, int w, int ca, int cb, float *gw32, void *stream) {

@@ -87,6 +87,7 @@ struct GGArgs {
     int nt0, nt_all;    // gg8_kernel: first n-tile of this launch and the n-tiles of the packed weights / output rows (0: NT):
                         // a 192-channel output goes as two launches of three n-tiles
     int tiles_x, tiles_y;
+    int acc;            // 1: out32 += result (cae_t_pointwise_acc; no activation, no bf16 copy)
     short dy[MAX_TAPS], dx[MAX_TAPS], wt[MAX_TAPS];
 };
 
@@ -277,7 +278,7 @@ __global__ void __launch_bounds__(256, 1) gather_gemm_kernel(const GGArgs p) {
                 for (int nt = 0; nt < NT; ++nt) {
                     float v = acc[pt][nt][r];
                     if (p.act) v = v > 0.0f ? v : (p.act == 1 ? 0.01f * v : 0.0f);
-                    if (p.out32) p.out32[base + 32 * nt] = v;
+                    if (p.out32) p.out32[base + 32 * nt] = p.acc ? p.out32[base + 32 * nt] + v : v;
                     if (p.out16) ((__bf16 *)p.out16)[base + 32 * nt] = (__bf16)v;
                 }
             }
@@ -436,7 +437,7 @@ __global__ void __launch_bounds__(512, 1) gg8_kernel(const GGArgs p) {
                     for (int nt = 0; nt < NT; ++nt) {
                         float v = acc[nt][r];
                         if (p.act) v = v > 0.0f ? v : (p.act == 1 ? 0.01f * v : 0.0f);
-                        if (p.out32) p.out32[base + 32 * nt] = v;
+                        if (p.out32) p.out32[base + 32 * nt] = p.acc ? p.out32[base + 32 * nt] + v : v;
                         if (p.out16) ((__bf16 *)p.out16)[base + 32 * nt] = (__bf16)v;
                     }
                 }
@@ -579,7 +580,7 @@ __global__ void __launch_bounds__(512, 1) gg8t_kernel(const GGArgs p) {
                         for (int nt = 0; nt < NT; ++nt) {
                             float v = acc[par][nt][r];
                             if (p.act) v = v > 0.0f ? v : (p.act == 1 ? 0.01f * v : 0.0f);
-                            if (p.out32) p.out32[base + 32 * nt] = v;
+                            if (p.out32) p.out32[base + 32 * nt] = p.acc ? p.out32[base + 32 * nt] + v : v;
                             if (p.out16) ((__bf16 *)p.out16)[base + 32 * nt] = (__bf16)v;
                         }
                     }
@@ -1325,6 +1326,132 @@ static __global__ void col2im_s2_kernel(const float *u, const float *bias, float
             }
         }
         for (int c = 0; c < C; ++c) out[((size_t)n * C + c) * oplane + (size_t)Y * OW + X] = s[c] + (bias ? bias[c] : 0.0f);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Multiscale colour layers (Conv2d(C -> c, k, stride 1, reflect padding k//2), _autoencoders.py:417-428) as an edge GEMM:
+// u[q][(tap, co)] = sum_ci a[q][ci] W[co][ci][tap] is a 1 x 1 gather-GEMM with K = (tap, channel) <= 96 columns (Kp), then
+//   col2im_s1r  out[p][co] = bias[co] + sum_tap u[reflect(p + tap - P)][(tap, co)]                      (NCHW fp32)
+//   im2col_s1r  gu[q][(tap, co)] = sum over p with reflect(p + tap - P) = q of g[p][co]   (its adjoint, as a hi / lo pair)
+// reflect(r) = -r below 0, 2 (H - 1) - r above H - 1 (one fold: P < H).
+// ---------------------------------------------------------------------------------------------------------------
+// One thread per output PIXEL, all its channels (c <= 3): the k * k records it reads share their index arithmetic.
+static __global__ void col2im_s1r_kernel(const float *u, const float *bias, float *out, int N, int C, int H, int W, int ks,
+                                         int Kp) {
+    const int P = ks / 2;
+    const size_t total = (size_t)N * H * W, plane = (size_t)H * W;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+        const int X = (int)(i % W);
+        size_t r = i / W;
+        const int Y = (int)(r % H);
+        const int n = (int)(r / H);
+        float s[3] = {0.0f, 0.0f, 0.0f};
+        for (int ky = 0; ky < ks; ++ky) {
+            const int iy = reflect_idx(Y + ky - P, H);
+            for (int kx = 0; kx < ks; ++kx) {
+                const int ix = reflect_idx(X + kx - P, W);
+                const float *rec = u + (((size_t)n * H + iy) * W + ix) * Kp + (ky * ks + kx) * C;
+                for (int c = 0; c < C; ++c) s[c] += rec[c];
+            }
+        }
+        for (int c = 0; c < C; ++c) out[((size_t)n * C + c) * plane + (size_t)Y * W + X] = s[c] + (bias ? bias[c] : 0.0f);
+    }
+}
+
+// the (at most 2) positions p of one axis with reflect(p + t - P) = q: r = q, and its mirror -q or 2 (M - 1) - q when that
+// lies in the padding band; -> count, positions in ps
+__device__ __forceinline__ int s1r_sources(int q, int t, int P, int M, int *ps) {
+    int np = 0;
+    int rs[3], nr = 0;
+    rs[nr++] = q;
+    if (q >= 1 && q <= P) rs[nr++] = -q;
+    if (q <= M - 2 && q >= M - 1 - P) rs[nr++] = 2 * (M - 1) - q;
+    for (int a = 0; a < nr; ++a) {
+        const int p = rs[a] - t + P;
+        if (p >= 0 && p < M) ps[np++] = p;
+    }
+    return np;
+}
+
+// One thread per (position, 8-column piece of its record).  The output gradient enters rounded to bf16 (the rounding point of
+// every other convolution's output gradient); the <= 4 terms a border entry folds are summed in fp32 and stored as a bf16
+// pair hi = bf16(sum), lo = bf16(sum - hi) in columns j and kp + j, so the GEMMs over the 2 kp columns see the folded sum to
+// ~2^-17 (the interior, one term, has lo = 0).  Record: [n][h][w][2 kp].
+static __global__ void im2col_s1r_kernel(const float *g, __bf16 *out, int N, int C, int H, int W, int ks, int Kp) {
+    const int P = ks / 2, K = ks * ks * C, pieces = Kp / 8;
+    const size_t total = (size_t)N * H * W * pieces, plane = (size_t)H * W;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+        const int q = (int)(i % pieces);
+        const size_t pos = i / pieces;
+        size_t r = pos;
+        const int qx = (int)(r % W);
+        r /= W;
+        const int qy = (int)(r % H);
+        const int n = (int)(r / H);
+        const float *gn = g + (size_t)n * C * plane;
+        bf16x8 hi, lo;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const int j = 8 * q + e;
+            float f = 0.0f;
+            if (j < K) {
+                const int tap = j / C, c = j - tap * C;
+                const int ky = tap / ks, kx = tap - ky * ks;
+                int ys[2], xs[2];
+                const int ny = s1r_sources(qy, ky, P, H, ys), nx = s1r_sources(qx, kx, P, W, xs);
+                for (int a = 0; a < ny; ++a)
+                    for (int b = 0; b < nx; ++b) f += (float)(__bf16)gn[(size_t)c * plane + (size_t)ys[a] * W + xs[b]];
+            }
+            hi[e] = (__bf16)f;
+            lo[e] = (__bf16)(f - (float)hi[e]);
+        }
+        __bf16 *rec = out + pos * 2 * Kp + 8 * q;
+        *(bf16x8 *)rec = hi;
+        *(bf16x8 *)(rec + Kp) = lo;
+    }
+}
+
+// acc[n][y][x][c] += reflect fold of an extended-domain gradient (the padded colour layer's data gradient, accumulated
+// into the level's fp32 gradient)
+static __global__ void fold_acc_kernel(FoldSrc f, float *acc, int N, int C) {
+    const size_t total = (size_t)N * f.H * f.W * C;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+        const int c = (int)(i % C);
+        size_t r = i / C;
+        const int x = (int)(r % f.W);
+        r /= f.W;
+        const int y = (int)(r % f.H);
+        const int n = (int)(r / f.H);
+        acc[i] += fold_read(f, n, y, x, C, c);
+    }
+}
+
+// Pyramid step of DistMSEPyramidLoss (_ratedist.py:10-43): 5 x 5 binomial blur [1 4 6 4 1]^2 / 256 with zero padding 2,
+// then bilinear x 0.5 (align_corners=False), which at that scale is the mean of each 2 x 2 block.  Together: the
+// separable 6-tap filter [1 5 10 10 5 1] / 32 at stride 2 over the zero-padded input, out[o] <- in[2 o - 2 .. 2 o + 3].
+// One thread per output value; the six rows are filtered along x first.
+static __global__ void pyramid_down_kernel(const float *x, float *out, int NC, int H, int W, int OH, int OW) {
+    const float f[6] = {1.0f, 5.0f, 10.0f, 10.0f, 5.0f, 1.0f};
+    const size_t total = (size_t)NC * OH * OW, plane = (size_t)H * W;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+        const int ox = (int)(i % OW);
+        size_t r = i / OW;
+        const int oy = (int)(r % OH);
+        const size_t nc = r / OH;
+        const float *xp = x + nc * plane;
+        float s = 0.0f;
+        for (int a = 0; a < 6; ++a) {
+            const int iy = 2 * oy - 2 + a;
+            if (iy < 0 || iy >= H) continue;
+            float row = 0.0f;
+            for (int b = 0; b < 6; ++b) {
+                const int ix = 2 * ox - 2 + b;
+                if (ix >= 0 && ix < W) row += f[b] * xp[(size_t)iy * W + ix];
+            }
+            s += f[a] * row;
+        }
+        out[i] = s * (1.0f / 1024.0f);
     }
 }
 

@@ -22,7 +22,9 @@ Variants covered: ``act_layer_type in (None, 'GDN', 'LeakyReLU', 'ReLU')`` units
 pre-convolutions) on the fused track functions, and residual units (``use_residual=True``) composed per operation from
 the same kernels (``_composed_track``), as are units with batch norm in training mode (batch statistics, running
 statistics updated as ``nn.BatchNorm2d`` does), grouped layers (dense kernels on the block-diagonal embedding of the
-grouped weight) and ``Dropout2d``; multiscale colour layers raise ``NotImplementedError`` under autograd.
+grouped weight) and ``Dropout2d``.  Multiscale colour layers (``multiscale_analysis``, _autoencoders.py:417-452) train
+on both forms: inside ``SynthesisFn`` (their data gradient summed with the next unit's before the level's IGDN / activation
+backward) and as ``_ColourFn`` behind the units of a composed track; ``criteria.DistMSEPyramidLoss`` scores them.
 """
 from __future__ import annotations
 
@@ -221,6 +223,106 @@ def _weight_grad(gw: torch.Tensor, spec_shape: Tuple[int, int], ks: int) -> torc
     return gw.permute(2, 1, 0)[:d0, :d1].reshape(d0, d1, ks, ks).contiguous()
 
 
+class ColourSpec:
+    """One multiscale colour layer: Conv2d(cin -> cout, ks, stride 1, reflect padding ks//2) (_autoencoders.py:417-428)."""
+
+    def __init__(self, cin: int, cout: int, ks: int, has_bias: bool):
+        self.cin, self.cout, self.ks, self.has_bias = int(cin), int(cout), int(ks), bool(has_bias)
+        self.cin_p = _pad32(cin)
+        self.K = self.ks * self.ks * self.cout  # GEMM columns (tap, channel) of the edge form
+        self.kp = _pad32(self.K)
+
+    @property
+    def n_tensors(self) -> int:
+        return 1 + int(self.has_bias)
+
+
+def _colour_edge(cs: ColourSpec) -> bool:
+    """the colour layer as a pointwise GEMM over K = (tap, channel) <= 96 (cae_t_col2im_s1r / cae_t_im2col_s1r); else, or with
+    CAE_EDGE_GEMM=0, the padded stride-1 form on the convolution kernels (cae_t_corr_s1 / cae_t_wgrad_s1)"""
+    return cs.cout <= 3 and cs.kp <= 96 and os.environ.get('CAE_EDGE_GEMM', '1') != '0'
+
+
+def _to_bf16(t32: torch.Tensor) -> torch.Tensor:
+    n, h, w, cp = t32.shape
+    out = torch.empty_like(t32, dtype=torch.bfloat16)
+    _lib.check(_L().cae_t_fold_to_bf16(t32.data_ptr(), n, h, w, 0, cp, out.data_ptr(), _st()))
+    return out
+
+
+def _colour_forward(a16: torch.Tensor, cs: ColourSpec, wt: torch.Tensor, b: Optional[torch.Tensor]) -> torch.Tensor:
+    """colour layer on a level's bf16 activation [n][h][w][cin_p] -> NCHW fp32 (n, cout, h, w)"""
+    L = _L()
+    n, h, w, cp = a16.shape
+    P, dev = cs.ks // 2, a16.device
+    if h <= P or w <= P:
+        raise ValueError(f'colour layer: a {h} x {w} level is too small for reflect padding {P}')
+    if _colour_edge(cs):
+        # u[q][(tap, co)] = sum_ci a[q][ci] W[co][ci][tap] (1 x 1 GEMM, N = kp), then the reflect col2im + bias
+        w1 = torch.zeros((cs.kp, cs.cin, 1, 1), dtype=torch.float32, device=dev)  # (j = tap * cout + co, ci)
+        w1[:cs.K, :, 0, 0] = wt.detach().float().permute(2, 3, 0, 1).reshape(cs.K, cs.cin)
+        wp = _pack(w1, 1, 1)
+        u32 = torch.empty((n, h, w, cs.kp), dtype=torch.float32, device=dev)
+        _lib.check(L.cae_t_pointwise(a16.data_ptr(), n, h, w, cp, wp.data_ptr(), u32.data_ptr(), None, cs.kp, None, 0, _st()))
+        out = torch.empty((n, cs.cout, h, w), dtype=torch.float32, device=dev)
+        bias_c = None if b is None else b.detach().float().contiguous()
+        _lib.check(L.cae_t_col2im_s1r(u32.data_ptr(), _ptr(bias_c), n, cs.cout, h, w, cs.ks, cs.kp, out.data_ptr(), _st()))
+        return out
+    cn = _pad32(cs.cout)
+    wp = _pack(wt, 1, cs.ks)
+    o32 = torch.empty((n, h, w, cn), dtype=torch.float32, device=dev)
+    _lib.check(L.cae_t_corr_s1(a16.data_ptr(), n, h, w, cp, wp.data_ptr(), cs.ks, 0, o32.data_ptr(), None, cn,
+                               _ptr(_bias_p(b, cn, dev)), 0, _st()))
+    return _to_nchw(o32, cs.cout)
+
+
+def _colour_backward(g: torch.Tensor, a16: torch.Tensor, cs: ColourSpec, wt: torch.Tensor, has_bias: bool,
+                     acc32: torch.Tensor):
+    """gradient of a colour layer's NCHW output g: its data gradient is ADDED to acc32 (fp32 [n][h][w][cin_p], the level's
+    gradient); -> (g_w, g_b | None)"""
+    L = _L()
+    n, h, w, cp = a16.shape
+    P, kk, dev = cs.ks // 2, cs.ks * cs.ks, a16.device
+    gc = g.detach().float().contiguous()
+    g_b = gc.bfloat16().float().sum(dim=(0, 2, 3)) if has_bias else None
+    if _colour_edge(cs):
+        # gu = the folded output gradient as a bf16 (hi, lo) pair: 2 kp GEMM columns, the weights repeated over both halves
+        k2 = 2 * cs.kp
+        gu16 = torch.empty((n, h, w, k2), dtype=torch.bfloat16, device=dev)
+        _lib.check(L.cae_t_im2col_s1r(gc.data_ptr(), n, cs.cout, h, w, cs.ks, cs.kp, gu16.data_ptr(), _st()))
+        gw1 = torch.empty((1, cp, k2), dtype=torch.float32, device=dev)
+        _lib.check(L.cae_t_wgrad_pointwise(a16.data_ptr(), gu16.data_ptr(), n, h, w, cp, k2, gw1.data_ptr(), _st()))
+        gw = gw1[0, :cs.cin, :cs.K] + gw1[0, :cs.cin, cs.kp:cs.kp + cs.K]
+        g_w = gw.reshape(cs.cin, cs.ks, cs.ks, cs.cout).permute(3, 0, 1, 2).contiguous()
+        w1d = torch.zeros((cs.cin, k2, 1, 1), dtype=torch.float32, device=dev)  # (ci, j)
+        wd = wt.detach().float().permute(1, 2, 3, 0).reshape(cs.cin, cs.K)
+        w1d[:, :cs.K, 0, 0] = wd
+        w1d[:, cs.kp:cs.kp + cs.K, 0, 0] = wd
+        wp_d = _pack(w1d, 1, 1)
+        _lib.check(L.cae_t_pointwise_acc(gu16.data_ptr(), n, h, w, k2, wp_d.data_ptr(), acc32.data_ptr(), cp, _st()))
+        return g_w, g_b
+    cn = _pad32(cs.cout)
+    gu16, _ = _from_nchw(gc, cn)
+    gwp = torch.empty((kk, cp, cn), dtype=torch.float32, device=dev)
+    _lib.check(L.cae_t_wgrad_s1(a16.data_ptr(), n, h, w, cp, gu16.data_ptr(), cn, cs.ks, 1, gwp.data_ptr(), _st()))
+    g_w = _weight_grad(gwp, (cs.cout, cs.cin), cs.ks)
+    wp_d = _pack(wt, 0, cs.ks)
+    gext = torch.empty((n, h + 2 * P, w + 2 * P, cp), dtype=torch.float32, device=dev)
+    _lib.check(L.cae_t_corr_s1(gu16.data_ptr(), n, h, w, cn, wp_d.data_ptr(), cs.ks, 1, gext.data_ptr(), None, cp, None, 0,
+                               _st()))
+    _lib.check(L.cae_t_fold_acc(gext.data_ptr(), n, h, w, P, cp, acc32.data_ptr(), _st()))
+    return g_w, g_b
+
+
+def _split_colour(colour, tensors):
+    """flat colour tensors -> per level (w, b | None)"""
+    out, k = [], 0
+    for cs in colour:
+        out.append((tensors[k], tensors[k + 1] if cs.has_bias else None))
+        k += cs.n_tensors
+    return out
+
+
 class AnalysisFn(torch.autograd.Function):
     """Analyzer.forward under autograd: L x [(conv s1 + act)? reflect conv s2 (+bias) (+GDN | act)]
     (_autoencoders.py:62-85, :29-30)."""
@@ -361,19 +463,30 @@ class AnalysisFn(torch.autograd.Function):
 
 class SynthesisFn(torch.autograd.Function):
     """Synthesizer.forward under autograd: L x [(conv-transpose s1 + act)? conv-transpose s2 (+bias) (+IGDN | act)]
-    (_autoencoders.py:187-211)."""
+    (_autoencoders.py:187-211).  `colour` (multiscale_analysis, :417-452): one ColourSpec per non-last level, their weights
+    (and biases) after the track's tensors; each reads the level's bf16 activation (what the next unit reads) and the
+    function returns (x_r, colour_0 .. colour_{L-2}).  In the backward a colour layer's data gradient is added to the
+    next unit's fp32 data gradient before the level's IGDN / activation backward (one rounding)."""
 
     @staticmethod
-    def forward(ctx, yq, specs, *tensors):
+    def forward(ctx, yq, specs, colour, *tensors):
         L = _L()
-        layers = _split_params(specs, tensors)
+        nt = sum(s.n_tensors for s in specs)
+        layers = _split_params(specs, tensors[:nt])
+        col_layers = _split_colour(colour, tensors[nt:]) if colour else []
+        colours = []
         n, _, h, w = yq.shape
         dev = yq.device
         a16, _ = _from_nchw(yq, specs[0].cin_p)
         saved, dims = [], []
         z32 = None
+        ctx.colour, ctx.col_layers, ctx.dev = colour or None, [(cw.detach(), cb) for cw, cb in col_layers], dev
+        if colour:
+            ctx.set_materialize_grads(False)  # (colour outputs the loss does not read hand back None)
         for i, (s, (wt, b, beta, gamma, pw, pb)) in enumerate(zip(specs, layers)):
             last = i == len(specs) - 1
+            if colour and i > 0:  # colour layer of the previous level, on the activation this unit reads
+                colours.append(_colour_forward(a16, colour[i - 1], *col_layers[i - 1]))
             a16_in, p16 = a16, None
             if s.has_pre:  # ConvTranspose2d(cin, cin, k, stride 1, padding k//2) + activation
                 p16 = torch.empty((n, h, w, s.cin_p), dtype=torch.bfloat16, device=dev)
@@ -398,7 +511,8 @@ class SynthesisFn(torch.autograd.Function):
                 ctx.specs, ctx.saved, ctx.dims = specs, saved, dims
                 ctx.layers = [tuple(t.detach() if t is not None else None for t in l) for l in layers]
                 ctx.need_input_grad = yq.requires_grad
-                return x_r
+                ctx.out_shape = tuple(x_r.shape)
+                return (x_r, *colours) if colour else x_r
             wp = _pack(wt, 0, s.ks)
             bias_p = _bias_p(b, s.cout_p, dev)
             need32 = s.has_gdn or last
@@ -420,14 +534,25 @@ class SynthesisFn(torch.autograd.Function):
         ctx.specs, ctx.saved, ctx.dims = specs, saved, dims
         ctx.layers = [tuple(t.detach() if t is not None else None for t in l) for l in layers]
         ctx.need_input_grad = yq.requires_grad
-        return x_r
+        ctx.out_shape = tuple(x_r.shape)
+        return (x_r, *colours) if colour else x_r
 
     @staticmethod
-    def backward(ctx, gx):
+    def backward(ctx, gx, *gcols):
         L = _L()
         specs, saved, dims, layers = ctx.specs, ctx.saved, ctx.dims, ctx.layers
+        colour, col_layers = ctx.colour, ctx.col_layers
+        dev = ctx.dev
+        if gx is None:
+            gx = torch.zeros(ctx.out_shape, dtype=torch.float32, device=dev)
         n = gx.shape[0]
-        dev = gx.device
+        col_grads = [(None, None)] * (len(colour) if colour else 0)
+
+        def add_colour(i, gx32):
+            """the colour layer of level i - 1 (input of unit i): its data gradient onto gx32, its parameter gradients"""
+            cw, cb = col_layers[i - 1]
+            col_grads[i - 1] = _colour_backward(gcols[i - 1], saved[i]['a_in'], colour[i - 1], cw, cb is not None, gx32)
+
         edge = bool(saved[-1].get('edge'))
         g16 = None if edge else _from_nchw(gx, specs[-1].cout_p)[0]  # gradient with respect to the last layer's output
         per_layer = [[None] * 6 for _ in specs]
@@ -460,11 +585,16 @@ class SynthesisFn(torch.autograd.Function):
                 wp_d = _pack(w1d, 1, 1)
                 prev_gdn = i > 0 and specs[i - 1].has_gdn
                 prev_act = i > 0 and saved[i - 1]['out'] is not None
-                want32 = prev_gdn or prev_act or i == 0
+                has_col = i > 0 and colour is not None and gcols[i - 1] is not None
+                want32 = prev_gdn or prev_act or i == 0 or has_col
                 gx32 = torch.empty((n, h, w, s.cin_p), dtype=torch.float32, device=dev) if want32 else None
                 gx16 = None if want32 else torch.empty((n, h, w, s.cin_p), dtype=torch.bfloat16, device=dev)
                 _lib.check(L.cae_t_pointwise(gu16.data_ptr(), n, h, w, 32, wp_d.data_ptr(), _ptr(gx32), _ptr(gx16), s.cin_p,
                                              None, 0, _st()))
+                if has_col:
+                    add_colour(i, gx32)
+                    if not (prev_gdn or prev_act):
+                        gx16 = _to_bf16(gx32)
                 if i == 0:
                     g_in = _to_nchw(gx32, s.cin)
                 elif prev_gdn:
@@ -493,7 +623,8 @@ class SynthesisFn(torch.autograd.Function):
             wp_d = _pack(wt, 1, s.ks)
             prev_gdn = i > 0 and specs[i - 1].has_gdn
             prev_act = i > 0 and saved[i - 1]['out'] is not None
-            want32 = prev_gdn or prev_act or i == 0 or s.has_pre  # (fp32 into an activation's backward: one rounding)
+            has_col = i > 0 and colour is not None and gcols[i - 1] is not None
+            want32 = prev_gdn or prev_act or i == 0 or s.has_pre or has_col  # (fp32 into an activation's backward: one rounding)
             gx32 = torch.empty((n, h, w, s.cin_p), dtype=torch.float32, device=dev) if want32 else None
             gx16 = None if want32 else torch.empty((n, h, w, s.cin_p), dtype=torch.bfloat16, device=dev)
             _lib.check(L.cae_t_deconv_dgrad(g16.data_ptr(), n, h, w, s.cout_p, wp_d.data_ptr(), s.ks, _ptr(gx32), _ptr(gx16),
@@ -509,11 +640,15 @@ class SynthesisFn(torch.autograd.Function):
                 if i == 0 and not ctx.need_input_grad:
                     break
                 wpp_d = _pack(pw, 1, s.ks)
-                want32 = prev_gdn or prev_act or i == 0
+                want32 = prev_gdn or prev_act or i == 0 or has_col
                 gx32 = torch.empty((n, h, w, s.cin_p), dtype=torch.float32, device=dev) if want32 else None
                 gx16 = None if want32 else torch.empty((n, h, w, s.cin_p), dtype=torch.bfloat16, device=dev)
                 _lib.check(L.cae_t_corr_s1(gu16.data_ptr(), n, h, w, s.cin_p, wpp_d.data_ptr(), s.ks, 3, _ptr(gx32), _ptr(gx16),
                                            s.cin_p, None, 0, _st()))
+            if has_col:
+                add_colour(i, gx32)
+                if not (prev_gdn or prev_act):
+                    gx16 = _to_bf16(gx32)
             if i == 0:
                 g_in = _to_nchw(gx32, s.cin)
             elif prev_gdn:
@@ -526,7 +661,8 @@ class SynthesisFn(torch.autograd.Function):
                 masked = True
             else:
                 g16 = gx16
-        return (g_in, None, *_flat_grads(specs, per_layer))
+        flat_col = [g for cs, (g_w, g_b) in zip(colour or (), col_grads) for g in ((g_w, g_b) if cs.has_bias else (g_w,))]
+        return (g_in, None, None, *_flat_grads(specs, per_layer), *flat_col)
 
 
 # ---- residual units (ResidualDownsamplingUnit / ResidualUpsamplingUnit, _autoencoders.py:104-174, :230-304) ----------
@@ -754,6 +890,24 @@ def _dense_weight(m) -> torch.Tensor:
     return dense.index_put((rows[:, None].expand_as(cols), cols), w)
 
 
+class _ColourFn(torch.autograd.Function):
+    """A multiscale colour layer alone on an NCHW fp32 level (composed tracks): the forms of _colour_forward /
+    _colour_backward."""
+
+    @staticmethod
+    def forward(ctx, x, cs, w, b):
+        a16, _ = _from_nchw(x, cs.cin_p)
+        ctx.a16, ctx.cs, ctx.w = a16, cs, w.detach()
+        return _colour_forward(a16, cs, w, b)
+
+    @staticmethod
+    def backward(ctx, g):
+        cs = ctx.cs
+        gx32 = torch.zeros(ctx.a16.shape, dtype=torch.float32, device=ctx.a16.device)
+        g_w, g_b = _colour_backward(g, ctx.a16, cs, ctx.w, cs.has_bias, gx32)
+        return _to_nchw(gx32, cs.cin), None, g_w, g_b
+
+
 def _run_sequence(u, seq, x: torch.Tensor, synthesis: bool) -> torch.Tensor:
     """The modules of a unit's nn.Sequential, one operation each (the module order IS the reference's forward)."""
     from .modules import GDN, _ConvParams
@@ -766,7 +920,7 @@ def _run_sequence(u, seq, x: torch.Tensor, synthesis: bool) -> torch.Tensor:
             if m is u.main:  # the strided layer
                 if synthesis:
                     spec = LayerSpec(m.in_channels, m.out_channels, m.kernel_size, m.bias is not None, False)
-                    x = SynthesisFn.apply(x, (spec,), *([wd] + ([m.bias] if m.bias is not None else [])))
+                    x = SynthesisFn.apply(x, (spec,), None, *([wd] + ([m.bias] if m.bias is not None else [])))
                 else:
                     x = _ConvS2Fn.apply(x, m.kernel_size, wd, m.bias)
             else:  # stride 1; a LeakyReLU / ReLU right behind it rides in the kernel's epilogue
@@ -790,24 +944,26 @@ def _run_sequence(u, seq, x: torch.Tensor, synthesis: bool) -> torch.Tensor:
     return x
 
 
-def _composed_track(units, x: torch.Tensor, synthesis: bool) -> torch.Tensor:
+def _composed_track(units, x: torch.Tensor, synthesis: bool, colour=None, ctensors=()):
     """Tracks with residual units (y = model(res_model(x) + x), _autoencoders.py:168-174, :298-304) or batch norm:
-    composed per operation."""
+    composed per operation.  With `colour` (synthesis, multiscale): -> (x, [colour_0 .. colour_{L-2}])."""
     from .modules import _ResidualUnit
-    for u in units:
+    col_layers = _split_colour(colour, ctensors) if colour else []
+    cols = []
+    for i, u in enumerate(units):
         if isinstance(u, _ResidualUnit):
             x = _run_sequence(u, u.model, _run_sequence(u, u.res_model, x, synthesis) + x, synthesis)
         else:
             x = _run_sequence(u, u.model, x, synthesis)
-    return x
+        if colour and i < len(units) - 1:
+            cols.append(_ColourFn.apply(x, colour[i], *col_layers[i]))
+    return (x, cols) if colour is not None else x
 
 
 def _track_inputs(track, units, synthesis: bool):
     """-> (specs, flat tensor list) of a track; effective, padded GDN parameters stay in the autograd graph."""
     from .modules import _ResidualUnit
     specs, tensors = [], []
-    if getattr(track, 'multiscale_analysis', False):
-        raise NotImplementedError('training with multiscale colour layers is not built')
     for u in units:
         if (isinstance(u, _ResidualUnit) or u.main_bn_index is not None or u.pre_bn_index is not None or u.main.groups != 1
                 or any(isinstance(m, nn.Dropout2d) and m.p > 0 for m in u.model)):
@@ -834,6 +990,24 @@ def _track_inputs(track, units, synthesis: bool):
     return tuple(specs), tensors
 
 
+def _colour_inputs(track, units):
+    """-> (ColourSpec per non-last level, flat weight / bias list) of a multiscale synthesis track, (None, []) without
+    multiscale_analysis.  Grouped colour layers (groups = channels_org) as the dense weight (_dense_weight)."""
+    if not getattr(track, 'multiscale_analysis', False):
+        return None, []
+    specs, tensors = [], []
+    for i, layer in enumerate(list(track.color_layers)[:len(units) - 1]):
+        conv = layer[0]
+        if conv.in_channels != units[i].main.out_channels:  # (the reference's own channel plan, channels_expansion != 1)
+            raise NotImplementedError(f'colour layer {i} expects {conv.in_channels} input channels, the level produces '
+                                      f'{units[i].main.out_channels}')
+        specs.append(ColourSpec(conv.in_channels, conv.out_channels, conv.kernel_size, conv.bias is not None))
+        tensors.append(_dense_weight(conv))
+        if conv.bias is not None:
+            tensors.append(conv.bias)
+    return tuple(specs), tensors
+
+
 def needs_grad(module: nn.Module, x: torch.Tensor) -> bool:
     """The differentiable track functions run when the module is in TRAINING mode and autograd is recording
     (train_cae_ms.py:183-187 puts the trainable modules in train(), the others in eval() under fixed_module's no_grad).
@@ -855,12 +1029,23 @@ def analysis_forward(track, x: torch.Tensor) -> torch.Tensor:
 
 def synthesis_forward(track, yq: torch.Tensor):
     dev = _lib.require_gpu()
-    specs, tensors = _track_inputs(track, track._units(), True)
+    units = track._units()
+    specs, tensors = _track_inputs(track, units, True)
+    colour, ctensors = _colour_inputs(track, units)
     yq = yq.to(device=dev, dtype=torch.float32)
-    out = _composed_track(track._units(), yq, True) if specs is None else SynthesisFn.apply(yq, specs, *tensors)
-    L = len(track._units())
-    # (x_r list, fx_brg) as the reference's Synthesizer; intermediate features are not materialised while training
-    return [out] + [None] * (L - 1), [None] * (L - 1) + [out]
+    cols: List[torch.Tensor] = []
+    if specs is None:
+        out = _composed_track(units, yq, True, colour, ctensors)
+        if colour is not None:
+            out, cols = out
+    elif colour:
+        out, *cols = SynthesisFn.apply(yq, specs, colour, *tensors, *ctensors)
+    else:
+        out = SynthesisFn.apply(yq, specs, None, *tensors)
+    L = len(units)
+    # (x_r list, fx_brg) as the reference's Synthesizer: x_r = [out, colour_{L-2}, ..., colour_0] (None without
+    # multiscale_analysis); intermediate features are not materialised while training
+    return [out] + (cols[::-1] if cols else [None] * (L - 1)), [None] * (L - 1) + [out]
 
 
 # ---- optimisers and the training step (train_cae_ms.py) -----------------------------------------------------------

@@ -318,6 +318,23 @@ int cae_t_pointwise(const void *x16, int n, int h, int w, int ck, const void *pa
                     const float *bias, int act, void *stream);
 int cae_t_wgrad_pointwise(const void *x16, const void *y16, int n, int h, int w, int ca, int cb, float *gw32, void *stream);
 
+/* Multiscale colour layers Conv2d(c_in -> c, k, stride 1, reflect padding k//2) (_autoencoders.py:417-428, c <= 3) as an edge
+ * GEMM over K = (tap, channel), kp = pad32(k * k * c) <= 96 columns: cae_t_pointwise forms u[q][(tap, co)] (fp32
+ * [n][h][w][kp]); cae_t_col2im_s1r sums out[p][co] = bias[co] + sum_tap u[reflect(p + tap - P)][(tap, co)] into NCHW fp32;
+ * cae_t_im2col_s1r is its adjoint gu[q][(tap, co)] = sum over p with reflect(p + tap - P) = q of bf16(g[p][co]) (fp32 sums
+ * stored as a bf16 pair: hi in columns [0, kp), lo = the rest in [kp, 2 kp) of each [n][h][w][2 kp] record; contracting
+ * both halves against the same weights gives the folded sum to ~2^-17).  cae_t_pointwise_acc is cae_t_pointwise with the result ADDED to out32 (no bias, no
+ * activation): the colour layer's data gradient onto the level's gradient.  cae_t_fold_acc adds the reflect fold of an
+ * extended-domain gradient to out32 (the padded form's data gradient).  h and w must exceed P (as the reflect pad).
+ * cae_t_pyramid_down: one step of DistMSEPyramidLoss's pyramid (_ratedist.py:10-43): 5 x 5 binomial blur, zero padding 2,
+ * then bilinear x 0.5 -- NCHW fp32 (n, c, h, w) -> (n, c, h / 2, w / 2). */
+int cae_t_col2im_s1r(const float *u32, const float *bias, int n, int c, int h, int w, int ks, int kp, float *out_nchw,
+                     void *stream);
+int cae_t_im2col_s1r(const float *g_nchw, int n, int c, int h, int w, int ks, int kp, void *out16, void *stream);
+int cae_t_pointwise_acc(const void *x16, int n, int h, int w, int ck, const void *packed, float *out32, int cn, void *stream);
+int cae_t_fold_acc(const float *gext32, int n, int h, int w, int pad, int cp, float *out32, void *stream);
+int cae_t_pyramid_down(const float *x_nchw, int n, int c, int h, int w, float *out_nchw, void *stream);
+
 /* Fused forms (csrc/cae_train_gdn.hpp; cp <= 128): the forward also saves the per-element factor f (y = z f: n^(-1/2),
  * IGDN n^(1/2)) in the register order the backward reads back -- f_saved holds cae_t_gdn_saved_elems(pixels, cp) floats
  * (0: shape not built) -- and the backward is ONE kernel: g_z (bf16), g_gamma, g_beta from z, f and the gradient with
