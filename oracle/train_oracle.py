@@ -131,7 +131,7 @@ def _bn(x: torch.Tensor, bn: Optional[dict]) -> torch.Tensor:
     return F.batch_norm(x, None, None, bn.get('weight'), bn.get('bias'), True, 0.0, bn.get('eps', 1e-5))
 
 
-def residual_track(x: torch.Tensor, units: Sequence[dict], synthesis: bool, bf16: bool = True) -> torch.Tensor:
+def residual_track(x: torch.Tensor, units: Sequence[dict], synthesis: bool, bf16: bool = True, levels: bool = False):
     """Residual units (ResidualDownsamplingUnit / ResidualUpsamplingUnit, _autoencoders.py:104-174, :230-304):
     y = model(res_model(x) + x).  units[i] = {'stages': [{'weight', 'bias'?, 'beta'?, 'gamma'?, 'act'?}], 'post_act'?,
     'weight', 'bias'?, 'beta'?, 'gamma'?, 'act'?}: res_model = stride-1 convolutions cin -> cin (analysis: reflect padding;
@@ -140,8 +140,10 @@ def residual_track(x: torch.Tensor, units: Sequence[dict], synthesis: bool, bf16
     the gradient at every convolution's output, the output of every GDN, and the gradient an analysis-side convolution hands to
     its input (folded from the extended domain into bf16).  Optional 'bn' entries ({'weight', 'bias', 'eps'}) behind a
     convolution: BatchNorm2d with batch statistics (:72-73, :87-88); units with 'residual': False are the plain
-    DownsamplingUnit / UpsamplingUnit (their stride-1 pre-convolution as the one stage, no residual sum)."""
+    DownsamplingUnit / UpsamplingUnit (their stride-1 pre-convolution as the one stage, no residual sum).  `levels`: the list
+    of every unit's output (the multiscale colour layers read the non-last ones) instead of the last one."""
     fx = x
+    outs = []
     for U in units:
         r = fx
         for S in U['stages']:
@@ -168,7 +170,8 @@ def residual_track(x: torch.Tensor, units: Sequence[dict], synthesis: bool, bf16
         else:
             y = _act(y, U.get('act'))
         fx = y
-    return fx
+        outs.append(fx)
+    return outs if levels else fx
 
 
 def entropy_forward(params: dict, y: torch.Tensor, noise: Optional[torch.Tensor], n_filters: int, form: str = 'plain',

@@ -251,7 +251,9 @@ def _named_grads(module, track):
                                          (dict(channels_net=32, channels_bn=48, compression_level=3, act_layer_type='LeakyReLU',
                                                bias=True), (2, 40, 56)),
                                          (dict(channels_net=64, channels_bn=48, compression_level=2, act_layer_type='ReLU',
-                                               kernel_size=5), (1, 37, 45))])
+                                               kernel_size=5), (1, 37, 45)),
+                                         # one image channel: the fused AnalysisFn edge GEMM at K = 9 of 32
+                                         (dict(channels_org=1, channels_net=32, channels_bn=48, compression_level=3), (2, 40, 56))])
 def test_track_gradients_match_the_restatement(cae, cfgkw, shape):
     from cnn_autoencoder_amd import synth
     from oracle import train_oracle as T
@@ -260,7 +262,7 @@ def test_track_gradients_match_the_restatement(cae, cfgkw, shape):
     enc, dec = model['encoder'].module, model['decoder'].module
     n, h, w = shape
     torch.manual_seed(1)
-    x = torch.rand(n, 3, h, w)
+    x = torch.rand(n, cfg['channels_org'], h, w)
     # analysis
     y = enc(x.cuda())
     gy = torch.randn_like(y.detach()).cpu()
@@ -613,3 +615,39 @@ def test_fused_reparametrisation_matches_the_torch_ops(cae):
         np.testing.assert_allclose(out.detach().cpu().numpy(), rp.cpu()(x).numpy(), rtol=1e-6, atol=1e-12)
         np.testing.assert_allclose(x_gpu.grad.cpu().numpy(), x_cpu.grad.numpy(), rtol=1e-6, atol=1e-12)
         assert float((x_cpu.grad == 0).float().mean()) > 0.005  # blocked gradients are part of the case
+
+
+# The four cases the training sweep flagged (tests/fuzz/fuzz_train.py, seed:case; profiles/r03_experiments.md 12): all
+# channels_org = 1 analysis tracks, the flagged gradient in the first unit's 1 -> 1 stride-1 stage or the batch norm behind it.
+ONE_CHANNEL_CASES = {'plain LeakyReLU + batch norm': (3, 93), 'residual LeakyReLU': (3, 167),
+                     'residual GDN + batch norm': (5, 84), 'residual k = 5 LeakyReLU + batch norm': (4, 160)}
+
+
+def _train_cases():
+    """tests/fuzz/train_cases.py, imported by file path (tests/fuzz holds scripts that run on import)"""
+    import importlib.util
+    import os
+    path = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'fuzz', 'train_cases.py')
+    spec = importlib.util.spec_from_file_location('train_cases', path)
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+@pytest.mark.parametrize('structure', list(ONE_CHANNEL_CASES))
+def test_one_channel_analysis_tracks(cae, structure):
+    """channels_org = 1 analysis tracks of the four structures the sweep flagged, rebuilt from its generator: every kernel call
+    of the composed track replayed alone in float64 passes its local bound (tests/train_replay.py), and every parameter
+    gradient is as close to the float64 restatement as the bf16 restatement is (train_replay.e2e_rule)."""
+    from train_replay import e2e_rule, judge_track
+    train_cases = _train_cases()
+    seed, k = ONE_CHANNEL_CASES[structure]
+    c = train_cases.case(seed, k)
+    assert c['enc_kw']['channels_org'] == 1
+    enc, _, x, _ = train_cases.build(c, cae)
+    act = c['kw']['act_layer_type']
+    V, rows = judge_track(enc, enc.analysis_track, x, False, act if act in ('LeakyReLU', 'ReLU') else None)
+    print(structure, V.summary())
+    assert V.ops > 0 and not V.failures, V.failures[:5]
+    for row in rows:
+        assert e2e_rule(row) != 'fail', row

@@ -250,3 +250,35 @@ def _restatement_with(layers, colours, yq):
                          colours[i]['bias'])
             cols.append(T._g(c, True))
     return [fx] + cols[::-1], layers, colours
+
+
+@pytest.mark.parametrize('c_org', [1, 3])
+@pytest.mark.parametrize('kind,edge', [('grouped', '1'), ('residual', '1'), ('residual', '0'), ('batch norm', '1')])
+def test_composed_multiscale_decoders_match_float64(cae, kind, edge, c_org, monkeypatch):
+    """Multiscale decoders on composed tracks (_ColourFn behind grouped, residual or batch-norm units; grouped colour layers
+    with groups = channels_org): every kernel call replayed alone in float64 within its local bound, colour layers included
+    (tests/train_replay.py), and every output, parameter gradient and the latent gradient as close to the float64 restatement
+    (oracle.train_oracle.residual_track(levels=True) + reflect-padded colour convolutions) as the bf16 restatement is
+    (train_replay.e2e_rule).  edge '0': the colour layers' padded stride-1 form."""
+    from train_replay import e2e_rule, judge_track
+    monkeypatch.setenv('CAE_EDGE_GEMM', edge)
+    # (one image channel makes a grouped model a dense one, which takes the fused track: batch norm keeps it composed)
+    kw = {'grouped': dict(channels_net=c_org, channels_bn=c_org, groups=True, bias=True, act_layer_type='ReLU',
+                          batch_norm=c_org == 1),
+          'residual': dict(channels_net=32, channels_bn=48, use_residual=True, act_layer_type='GDN'),
+          'batch norm': dict(channels_net=32, channels_bn=48, batch_norm=True, bias=True, act_layer_type='LeakyReLU')}[kind]
+    dec = _decoder(cae, 31 + c_org, channels_org=c_org, compression_level=3, **kw)
+    with torch.no_grad():
+        for m in dec.modules():
+            if isinstance(m, torch.nn.BatchNorm2d):
+                m.weight.uniform_(0.5, 1.5)
+                m.bias.uniform_(-0.2, 0.2)
+    torch.manual_seed(6)
+    yq = torch.round(3 * torch.randn(2, kw['channels_bn'], 4, 5))
+    act = kw['act_layer_type']
+    V, rows = judge_track(dec, dec.synthesis_track, yq, True, act if act in ('LeakyReLU', 'ReLU') else None)
+    print(kind, c_org, V.summary())
+    assert sum('colour' in k for k in V.ratios) > 0 and not V.failures, V.failures[:5]
+    assert any(r[0].startswith('color_layers.') for r in rows) and sum(r[0].startswith('out ') for r in rows) == 3
+    for row in rows:
+        assert e2e_rule(row) != 'fail', row
