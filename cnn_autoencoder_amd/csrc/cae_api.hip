@@ -822,19 +822,34 @@ int cae_model_set_entropy(cae_model_t *mm, int channels, int cdf_stride, const i
 }
 
 static int analysis_impl(cae_model_t *mm, const void *tiles, int fmt, int n, int h, int w, void *latents, bool symbols,
-                         void *stream);
+                         float *const *levels, void *stream);
 
 int cae_analysis(cae_model_t *mm, const void *tiles, int fmt, int n, int h, int w, float *latents, void *stream) {
-    return analysis_impl(mm, tiles, fmt, n, h, w, latents, false, stream);
+    return analysis_impl(mm, tiles, fmt, n, h, w, latents, false, nullptr, stream);
+}
+
+int cae_analysis_levels(cae_model_t *mm, const void *tiles, int fmt, int n, int h, int w, float *latents,
+                        float *const *levels, void *stream) {
+    return analysis_impl(mm, tiles, fmt, n, h, w, latents, false, levels, stream);
 }
 
 int cae_analysis_symbols(cae_model_t *mm, const void *tiles, int fmt, int n, int h, int w, int32_t *symbols,
                          void *stream) {
-    return analysis_impl(mm, tiles, fmt, n, h, w, symbols, true, stream);
+    return analysis_impl(mm, tiles, fmt, n, h, w, symbols, true, nullptr, stream);
+}
+
+// Every reflect-padded convolution of the analysis track (strided layers and stride-1 stages; F.pad(mode='reflect')
+// needs pad < size, as the reference) sees an input above the padding k//2?  Level i's input is h x w halved i times.
+static int check_reflect_levels(const Model *m, int h, int w) {
+    const int P = m->ks / 2;
+    for (int i = 0; i < m->L; ++i, h = (h + 1) / 2, w = (w + 1) / 2)
+        if (h <= P || w <= P)
+            return fail(CAE_ERR_ARG, "analysis level %d input %d x %d too small for reflect padding %d", i, h, w, P);
+    return CAE_OK;
 }
 
 static int analysis_impl(cae_model_t *mm, const void *tiles, int fmt, int n, int h, int w, void *latents, bool symbols,
-                         void *stream) {
+                         float *const *levels, void *stream) {
     Model *m = reinterpret_cast<Model *>(mm);
     if (!m || !tiles || !latents) return fail(CAE_ERR_ARG, "NULL argument");
     if (symbols && m->ent.channels == 0) return fail(CAE_ERR_ARG, "entropy model not set");
@@ -842,9 +857,10 @@ static int analysis_impl(cae_model_t *mm, const void *tiles, int fmt, int n, int
     if (fmt != CAE_FMT_U8_HWC && fmt != CAE_FMT_F32_NCHW) return fail(CAE_ERR_ARG, "bad pixel format %d", fmt);
     for (auto &l : m->enc)
         if (!l.set) return fail(CAE_ERR_ARG, "analysis layer not set");
+    int rc;
+    if ((rc = check_reflect_levels(m, h, w))) return rc;
     hipStream_t st = (hipStream_t)stream;
     std::lock_guard<std::mutex> lk(m->mu);
-    int rc;
     if ((rc = m->ensure_device()) || (rc = m->order_stream(stream))) return rc;
     const bool f16 = m->f16_usable();
     const bool first_fused = f16 ? m->enc[0].wp_edge16 != nullptr : m->enc[0].wp_edge != nullptr;
@@ -976,6 +992,16 @@ static int analysis_impl(cae_model_t *mm, const void *tiles, int fmt, int n, int
             if ((rc = launch_conv(m->ks, l.ct, l.gdn, a, st))) return rc;
         }
         prof.end();
+        if (!last && levels && levels[i]) {  // the unit's output as the next unit reads it (split: exactly hi + lo)
+            const size_t t2 = (size_t)n * l.cout * a.OH * a.OW;
+            if (f16)
+                hipLaunchKernelGGL(c8s_to_nchw_kernel<false>, dim3(ew_grid(t2)), dim3(256), 0, st, (const char *)a.out,
+                                   levels[i], n, l.cout, a.OH, a.OW, l.ct * 4);
+            else
+                hipLaunchKernelGGL(c8_to_nchw_kernel, dim3(ew_grid(t2)), dim3(256), 0, st, (const float *)a.out,
+                                   levels[i], n, l.cout, a.OH * a.OW, l.ct * 4);
+            HIP_TRY(hipGetLastError());
+        }
         cur = (const float *)a.out;
         cur_planes = l.ct * 4;
         ch = a.OH;
@@ -1015,6 +1041,11 @@ static int synthesis_impl(cae_model_t *mm, const float *latents, const int32_t *
     if (fmt != CAE_FMT_U8_HWC && fmt != CAE_FMT_F32_NCHW) return fail(CAE_ERR_ARG, "bad pixel format %d", fmt);
     for (auto &l : m->dec)
         if (!l.set) return fail(CAE_ERR_ARG, "synthesis layer not set");
+    // colour layers are reflect-padded stride-1 convolutions on level i's output (lh, lw doubled i + 1 times)
+    for (int i = 0; colors && i + 1 < m->L; ++i)
+        if (colors[i] && ((lh << (i + 1)) <= m->ks / 2 || (lw << (i + 1)) <= m->ks / 2))
+            return fail(CAE_ERR_ARG, "colour layer %d input %d x %d too small for reflect padding %d", i, lh << (i + 1),
+                        lw << (i + 1), m->ks / 2);
     hipStream_t st = (hipStream_t)stream;
     std::lock_guard<std::mutex> lk(m->mu);
     int rc;

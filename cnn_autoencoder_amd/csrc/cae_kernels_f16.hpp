@@ -1,7 +1,10 @@
 // Split-precision ("f16x3") variants of the conv / deconv / GDN kernels for CDNA4.
 //
-// Every fp32 value v is carried as two halves  v = hi + lo,  hi = f16(v), lo = f16(v - hi)
-// (22 significant bits).  A product is three f16 MFMAs accumulated in fp32:
+// Every fp32 value v is carried as two halves  v ~ hi + lo,  hi = f16(v), lo = f16(v - hi), with
+//     |v - (hi + lo)| <= max(2^-22 |v|, 2^-25):
+// 22 significant bits for |v| >= 2^-3; below that lo is an f16 subnormal (a multiple of 2^-24), so small values --
+// typical weights and gamma among them -- keep an absolute accuracy of 2^-25 only (include/cae_hip.h "ACCURACY").
+// A product is three f16 MFMAs accumulated in fp32:
 //     a*b ~= ah*bh + ah*bl + al*bh            (the dropped al*bl term is < 2^-22 |a b|)
 // On v_mfma_f32_32x32x16_f16 this costs 3 x 32 cycles per 32x32x16 block against 8 x 64 cycles on
 // v_mfma_f32_32x32x2_f32: 5.3x less matrix-pipe time at fp32-class accuracy (measured through the

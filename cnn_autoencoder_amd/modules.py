@@ -569,20 +569,45 @@ class Analyzer(_Track):
         self._setup(channels_org, channels_net, channels_bn, compression_level, kernel_size)
 
     def latent_size(self, h: int, w: int) -> Tuple[int, int]:
-        for _ in range(self._dims[3]):
-            h, w = (h + 1) // 2, (w + 1) // 2
-        return h, w
+        return self.latent_size_at(h, w, self._dims[3])
 
-    def _run(self, ptr: int, fmt: int, n: int, h: int, w: int) -> torch.Tensor:
+    def _run(self, ptr: int, fmt: int, n: int, h: int, w: int, levels: bool = False):
         dev = _lib.require_gpu()
         hd = self._sync()
         lh, lw = self.latent_size(h, w)
+        L = self._dims[3]
 
         def call():
             y = torch.empty((n, self._dims[2], lh, lw), dtype=torch.float32, device=dev)
-            _lib.check(_lib.lib().cae_analysis(hd.ptr, ptr, fmt, n, h, w, y.data_ptr(), _lib.stream_ptr()))
-            return y
+            if not levels:
+                _lib.check(_lib.lib().cae_analysis(hd.ptr, ptr, fmt, n, h, w, y.data_ptr(), _lib.stream_ptr()))
+                return y
+            lv = [torch.empty((n, u.main.out_channels) + self.latent_size_at(h, w, i + 1), dtype=torch.float32,
+                              device=dev) for i, u in enumerate(self._units()[:-1])]
+            lv_ptr = (ctypes.c_void_p * max(L - 1, 1))(*[t.data_ptr() for t in lv])
+            _lib.check(_lib.lib().cae_analysis_levels(hd.ptr, ptr, fmt, n, h, w, y.data_ptr(), lv_ptr,
+                                                      _lib.stream_ptr()))
+            return y, lv
         return self._guarded(hd, call)
+
+    def latent_size_at(self, h: int, w: int, level: int) -> Tuple[int, int]:
+        for _ in range(level):
+            h, w = (h + 1) // 2, (w + 1) // 2
+        return h, w
+
+    def forward_levels(self, x: torch.Tensor):
+        """x (B,C,H,W) float or (B,H,W,C) uint8 -> (latents, [output of unit i for i < L-1]) as float NCHW: every unit's
+        output as the next unit reads it (cae_analysis_levels; f16x3: hi + lo of the stored split value)."""
+        dev = _lib.require_gpu()
+        if x.dtype == torch.uint8:
+            if x.dim() != 4 or x.size(3) != self._dims[0]:
+                raise ValueError(f'expected uint8 (B,H,W,{self._dims[0]}), got {tuple(x.shape)}')
+            x = x.to(dev).contiguous()
+            return self._run(x.data_ptr(), _lib.FMT_U8_HWC, x.size(0), x.size(1), x.size(2), levels=True)
+        if x.dim() != 4 or x.size(1) != self._dims[0]:
+            raise ValueError(f'expected (B,{self._dims[0]},H,W), got {tuple(x.shape)}')
+        x = x.detach().to(device=dev, dtype=torch.float32).contiguous()
+        return self._run(x.data_ptr(), _lib.FMT_F32_NCHW, x.size(0), x.size(2), x.size(3), levels=True)
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         """x (B,C,H,W) float in [0,1] -> y (B,channels_bn,ceil(H/2^L),ceil(W/2^L))."""

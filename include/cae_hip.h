@@ -77,12 +77,19 @@ int cae_model_set_layer_act(cae_model_t *m, int track, int index, int act, const
 
 /* Arithmetic of the conv / GDN contraction: 0 = exact fp32 MFMA (v_mfma_f32_32x32x2_f32),
  * 1 = "f16x3": every operand split into two f16 halves, three f16 MFMAs per product, fp32
- * accumulate (22 significant bits; same 1e-4 parity bar, ~5x less matrix-pipe time).  Set before
+ * accumulate (same 1e-4 parity bar, ~5x less matrix-pipe time).  Set before
  * cae_model_set_layer.  (No reference counterpart: the reference computes in fp32 on ATen,
  * _autoencoders.py:78-85, :204-211.)
  *
+ * ACCURACY of f16x3.  A value v is carried as hi = f16(v), lo = f16(v - hi):
+ *   |v - (hi + lo)| <= max(2^-22 |v|, 2^-25).
+ * lo falls below the smallest normal f16 (2^-14) as soon as |v| < 2^-3, and is then rounded to a multiple of 2^-24:
+ * the relative accuracy is 2^-22 at |v| = 0.25 but 2^-17.4 at 0.01 and 2^-14 at 1e-3.  Typical convolution weights
+ * (|w| ~ 0.01-0.05) and most of gamma lie in that band.  A product a b is ah bh + ah bl + al bh (the dropped al bl
+ * is below 2^-22 |a b|); the sums accumulate in fp32.  (tests/test_inference_kernels.py pins this model.)
+ *
  * VALID RANGE of f16x3.  f16 has 5 exponent bits, so the split format holds finite values with
- * |v| <= 65504 at 22 significant bits (values below 2^-14 keep an absolute accuracy of 2^-25).
+ * |v| <= 65504, at the accuracy above.
  *   - weights / gamma outside that range: cae_model_set_layer marks the model and every call runs on the
  *     fp32 kernels (cae_model_effective_precision reports 0);
  *   - GDN / IGDN squares: formed from y scaled per pixel by a power of two (largest |y| of the pixel's
@@ -115,6 +122,14 @@ int cae_model_set_entropy(cae_model_t *m, int channels, int cdf_stride, const in
 int cae_analysis(cae_model_t *m, const void *tiles_dev, int fmt, int n, int h, int w,
                  float *latents_dev, void *stream);
 
+/* cae_analysis that also writes the output of every unit i < compression_level-1 for which levels_dev[i] is not NULL:
+ * (n, cout_i, ceil(h/2^(i+1)), ceil(w/2^(i+1))) float NCHW, the values the next unit reads (f16x3: exactly hi + lo of
+ * the stored split value).  levels_dev may be NULL.  The kernels and the latents are the same as cae_analysis's.
+ * Every call of the analysis entry points returns CAE_ERR_ARG when a reflect-padded convolution would see an input
+ * of k//2 rows or columns or fewer (F.pad(mode='reflect') rejects it, as the reference does). */
+int cae_analysis_levels(cae_model_t *m, const void *tiles_dev, int fmt, int n, int h, int w, float *latents_dev,
+                        float *const *levels_dev, void *stream);
+
 /* cae_synthesis replaces Synthesizer.forward (_autoencoders.py:442-455) and, for U8_HWC, the
  * x*255 -> clip -> truncating uint8 -> HWC epilogue of ConvolutionalAutoencoder.decode
  * (:576-580).  latents_dev (n, channels_bn, lh, lw) float NCHW; output (n, ., lh*2^L, lw*2^L).
@@ -138,7 +153,8 @@ int cae_model_set_layer_stage(cae_model_t *m, int track, int index, int stage, c
  * convolution from the output of synthesis level `index` (< compression_level-1) to the image channels.
  * w: (cout, cin, k, k).  cae_synthesis_multiscale additionally writes colors_dev[i] (n, cout, lh*2^(i+1),
  * lw*2^(i+1)) float NCHW for every non-NULL entry: the reference's x_r[compression_level-1-i]
- * (_autoencoders.py:446-452).  Precision 1 (f16x3): colour layers to at most 32 channels; wider: precision 0. */
+ * (_autoencoders.py:446-452).  Precision 1 (f16x3): colour layers to at most 32 channels; wider: precision 0.
+ * A requested colour layer whose level is k//2 rows or columns or fewer (reflect padding) is CAE_ERR_ARG. */
 int cae_model_set_color_layer(cae_model_t *m, int index, int cin, int cout, const float *w, const float *bias);
 int cae_synthesis_multiscale(cae_model_t *m, const float *latents_dev, int n, int lh, int lw, void *out_dev, int fmt,
                              float *const *bridges_dev, float *const *colors_dev, void *stream);
