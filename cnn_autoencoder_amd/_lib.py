@@ -69,6 +69,7 @@ SYMBOLS = {
     'cae_t_pack_weights': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     'cae_t_from_nchw': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     'cae_t_to_nchw': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    'cae_t_set_samples_per_block': (c_int, [c_int]),
     'cae_t_conv_forward': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int,
                                     c_void_p, c_void_p]),
     'cae_t_conv_dgrad_ext': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_int,

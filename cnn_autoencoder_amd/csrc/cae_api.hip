@@ -539,7 +539,7 @@ static int run_stages(Model *m, const Layer &l, bool synthesis, int n, int ch, i
         b.out_planes = ctin * 4;
         b.cout = l.cin;
         b.tiles_x = (cw + 15) / 16;
-        b.tiles_y = (ch + 2 * CAE_CONV_NW - 1) / (2 * CAE_CONV_NW);
+        b.tiles_y = (ch + 2 * CONV_NW - 1) / (2 * CONV_NW);
         b.outfmt = OUT_C8;
         b.act = sg.act;
         b.res = sg.add_res ? unit_in : nullptr;
@@ -949,7 +949,7 @@ static int analysis_impl(cae_model_t *mm, const void *tiles, int fmt, int n, int
         a.out_planes = l.ct * 4;
         a.cout = l.cout;
         a.tiles_x = (a.OW + 15) / 16;
-        a.tiles_y = (a.OH + 2 * CAE_CONV_NW - 1) / (2 * CAE_CONV_NW);
+        a.tiles_y = (a.OH + 2 * CONV_NW - 1) / (2 * CONV_NW);
         a.outfmt = last ? (symbols ? OUT_SYM : OUT_NCHW) : OUT_C8;
         if (last && symbols) a.medians = m->medians_dev;
         prof.begin();
@@ -1143,7 +1143,7 @@ static int synthesis_impl(cae_model_t *mm, const float *latents, const int32_t *
         a.out_planes = l.ct * 4;
         a.cout = l.cout;
         a.tiles_x = (cw + 31) / 32;
-        a.tiles_y = (ch + CAE_DECONV_NW - 1) / CAE_DECONV_NW;
+        a.tiles_y = (ch + DECONV_NW - 1) / DECONV_NW;
         a.outfmt = last ? (fmt == CAE_FMT_U8_HWC ? OUT_U8HWC : OUT_NCHW) : OUT_C8;
         if (use_pmap && i == m->L - 2) {
             a.outfmt = OUT_PMAP;
@@ -1198,7 +1198,7 @@ static int synthesis_impl(cae_model_t *mm, const float *latents, const int32_t *
             c.out_planes = round_ct(l.color_cout) * 4;
             c.cout = l.color_cout;
             c.tiles_x = (a.OW + 15) / 16;
-            c.tiles_y = (a.OH + 2 * CAE_CONV_NW - 1) / (2 * CAE_CONV_NW);
+            c.tiles_y = (a.OH + 2 * CONV_NW - 1) / (2 * CONV_NW);
             c.outfmt = OUT_NCHW;
             c.act = 0;
             if (f16) {  // split rows in (C8SP), reflect padding, NCHW fp32 out

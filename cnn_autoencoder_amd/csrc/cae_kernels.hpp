@@ -258,29 +258,20 @@ __device__ __forceinline__ void store_tiles(const f32x16 (&acc)[CT], const Layer
 //   tile   = (2 NW) x 16 output pixels, all CT*32 output channels
 //   stage  = (8-channel chunk c, kernel row ky): KS taps x CT KiB of weights + TY halo rows
 // =================================================================================================
-#ifndef CAE_CONV_WAVES
-#define CAE_CONV_WAVES 2
-#endif
 // XCD-aware tile order: consecutive workgroup ids are dealt round-robin over the 8 XCDs, each with a private L2, so
 // neighbouring tiles -- which share halo rows / columns and re-read them per kernel-row stage -- land on different L2s.
 // Give every XCD a contiguous range of tiles instead (whole images at bench sizes).  Bijective for any grid size; a
 // placement guess that only affects speed (the block -> XCD map is not a contract).
-#ifndef CAE_XCD_SWIZZLE
-#define CAE_XCD_SWIZZLE 1
-#endif
 __device__ __forceinline__ int xcd_tile_order(int bid, int nwg) {
-#if CAE_XCD_SWIZZLE
     const int q = nwg >> 3, r = nwg & 7, x = bid & 7;
     return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (bid >> 3);
-#else
-    return bid;
-#endif
 }
 
 // S = stride (2: DownsamplingUnit's strided conv; 1: the pre-activation conv of the LeakyReLU/ReLU units,
 // _autoencoders.py:62-70, and -- with ZEROPAD and flipped weights -- ConvTranspose2d(stride 1), :187-196)
+// (two waves per SIMD: room for three measured no faster, occupancy is not the limiter -- profiles/r01_experiments.md)
 template <int KS, int CT, int NW, bool GDN, int S = 2, bool ZEROPAD = false, bool INV = false>
-__global__ void __launch_bounds__(NW * 64, (GDN && CT >= 6) ? 1 : (CT <= 4 ? CAE_CONV_WAVES : 2)) conv_s2_kernel(const LayerArgs p) {
+__global__ void __launch_bounds__(NW * 64, (GDN && CT >= 6) ? 1 : 2) conv_s2_kernel(const LayerArgs p) {
     constexpr int PAD = KS / 2;
     constexpr int TX = 16, TY = 2 * NW;
     constexpr int WH = S * (TX - 1) + KS;  // halo columns
@@ -364,12 +355,8 @@ __global__ void __launch_bounds__(NW * 64, (GDN && CT >= 6) ? 1 : (CT <= 4 ? CAE
     for (int c = 0; c < p.cci; ++c) {
         static_for<KS>([&](auto ky_tag) {
             constexpr int ky = decltype(ky_tag)::value;
-#if defined(CAE_EXP_NOWAIT)
-            __builtin_amdgcn_s_barrier();
-#elif !defined(CAE_EXP_NOBARRIER)
             wait_vm0();
             __syncthreads();
-#endif
             char *cur = smem + (sc & 1) * STAGE_BYTES;
             char *nxt = smem + ((sc + 1) & 1) * STAGE_BYTES;
             const char *wb = cur + lane * 16;
@@ -380,7 +367,6 @@ __global__ void __launch_bounds__(NW * 64, (GDN && CT >= 6) ? 1 : (CT <= 4 ? CAE
             f32x4 a_cur[CT];
 #pragma unroll
             for (int ct = 0; ct < CT; ++ct) a_cur[ct] = *(const f32x4 *)(wb + ct * 1024);
-#ifndef CAE_EXP_NODMA
             if constexpr (ky + 1 < KS) {
                 issue_stage(c, std::integral_constant<int, ky + 1>{}, nxt);
             } else {
@@ -390,7 +376,6 @@ __global__ void __launch_bounds__(NW * 64, (GDN && CT >= 6) ? 1 : (CT <= 4 ? CAE
                     issue_gamma0<CT, NW>(p, nxt, wave, lane);
                 }
             }
-#endif
 #pragma unroll
             for (int kx = 0; kx < KS; ++kx) {
                 f32x4 b_nxt = b_cur;

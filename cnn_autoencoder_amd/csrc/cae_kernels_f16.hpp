@@ -25,21 +25,10 @@
 
 namespace cae {
 
-#ifndef CAE_FIRST_PIPE
-#define CAE_FIRST_PIPE 1  // conv_first_f16: hand-placed GDN schedule (gdn_resident_pipe_f16); 0: the compiler's
-#endif
-#ifndef CAE_F16_PIPE
-#define CAE_F16_PIPE 0  // 1: software-pipelined operand reads in deconv_s2_f16's K loop (measured null: the stack is power-limited)
-#endif
-#ifndef CAE_F16_ISSUERS
-#define CAE_F16_ISSUERS 2  // LDS-DMA issuer waves of conv_s2_f16 / deconv_s2_f16: NI = NW / CAE_F16_ISSUERS
-#endif
-// issuer index of wave w (0 .. NI-1), or -1: the first NI waves, or (CAE_F16_ISSUE_HI) the last NI
-#ifdef CAE_F16_ISSUE_HI
-#define ISSUER(w, NW, NI) ((w) >= (NW) - (NI) ? (w) - ((NW) - (NI)) : -1)
-#else
+// LDS-DMA issuer waves of conv_s2_f16 / deconv_s2_f16: NI = NW / F16_ISSUERS (profiles/r02_experiments.md 9)
+constexpr int F16_ISSUERS = 2;
+// issuer index of wave w (0 .. NI-1), or -1: the first NI waves
 #define ISSUER(w, NW, NI) ((w) < (NI) ? (w) : -1)
-#endif
 
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
@@ -256,9 +245,6 @@ __device__ __forceinline__ void store_split_f16(const f32x16 (&acc)[CT], const L
                 const u32x4 v = {r0[0], r1[0], r0[1], r1[1]};
                 char *dst = dst0;
                 dst0 += plane_bytes;  // next plane: one 64-bit add of a uniform (no per-plane 64-bit multiplies)
-#ifdef CAE_EXP_F16_NOSTORE  // timing-only ablation: activations are computed but not written (wrong results)
-                if (p.N < 0)
-#endif
                 *(u32x4 *)dst = v;
             }
     }
@@ -330,9 +316,7 @@ __device__ __forceinline__ void store_tiles_f16(f32x16 (&acc)[CT], const LayerAr
 // =================================================================================================
 // waves per block: 8 waves x 1 column tile (two waves per SIMD cover each other's operand waits) measured 4-8 % (conv2),
 // 2-4 % (conv3), 17 % (conv4) faster than 4 waves x 2 column tiles at the same staging traffic (r01_experiments.md)
-#ifndef CAE_CONV_F16_NW
-#define CAE_CONV_F16_NW 8
-#endif
+constexpr int CONV_F16_NW = 8;
 // S = 1 (the stride-1 convolution in front of the strided one in LeakyReLU / ReLU units, _autoencoders.py:62-76): same
 // staging, WH = 16 + KS - 1 halo columns.  SP: rows in and out are C8SP (synthesis track); ZP: zero padding instead of
 // reflection -- the synthesis units' ConvTranspose2d(stride 1, padding k//2) (:187-202) is the zero-padded correlation
@@ -340,8 +324,8 @@ __device__ __forceinline__ void store_tiles_f16(f32x16 (&acc)[CT], const LayerAr
 // RES: stage of a residual unit -- (I)GDN or activation, + the unit's input, + the strided layer's pre-activation
 // (add_residual_f16); the synthesis units (ZP) normalise with the inverse GDN.
 template <int KS, int CT, bool GDN, int S = 2, bool SP = false, bool ZP = false, bool RES = false>
-__global__ void __launch_bounds__(CAE_CONV_F16_NW * 64, 1) conv_s2_f16_kernel(const LayerArgs p) {
-    constexpr int NW = CAE_CONV_F16_NW, PT = 8 / NW;  // 8 waves x 1 column tile (shipped) | 4 waves x 2
+__global__ void __launch_bounds__(CONV_F16_NW * 64, 1) conv_s2_f16_kernel(const LayerArgs p) {
+    constexpr int NW = CONV_F16_NW, PT = 8 / NW;  // 8 waves x 1 column tile
     constexpr int PAD = KS / 2;
     constexpr int TX = 16, TY = 16;
     constexpr int WH = S * TX + KS - S;
@@ -361,10 +345,7 @@ __global__ void __launch_bounds__(CAE_CONV_F16_NW * 64, 1) conv_s2_f16_kernel(co
     // a SIMD: with NI = NW/2 one wave per SIMD spends the first part of a stage issuing the copies (tens of cycles per
     // instruction) while its partner has the matrix pipe to itself, then computes while the partner waits at the
     // barrier -- the two waves of a SIMD run half a stage apart instead of in lockstep (profiles/r02_experiments.md 9).
-#ifndef CAE_F16_ISSUERS
-#define CAE_F16_ISSUERS 2  // divisor: NI = NW / CAE_F16_ISSUERS
-#endif
-    constexpr int NI = NW / CAE_F16_ISSUERS > 0 ? NW / CAE_F16_ISSUERS : 1;
+    constexpr int NI = NW / F16_ISSUERS > 0 ? NW / F16_ISSUERS : 1;
     constexpr int MAXP = (HALO_INSTR + NI - 1) / NI;
     extern __shared__ __attribute__((aligned(16))) char smem[];
 
@@ -410,18 +391,12 @@ __global__ void __launch_bounds__(CAE_CONV_F16_NW * 64, 1) conv_s2_f16_kernel(co
         if (ISSUER(wave, NW, NI) < 0) return;
         const int iw = ISSUER(wave, NW, NI);
         const char *wsrc = (const char *)p.wp + (size_t)(q * KS + ky) * W_BYTES;
-#ifdef CAE_EXP_F16C_NOWDMA  // timing-only ablation: weights staged for stage 0 only (wrong results)
-        if (q == 0 && ky == 0)
-#endif
 #pragma unroll
         for (int i = 0; i < (W_INSTR + NI - 1) / NI; ++i) {
             const int j = iw + i * NI;
             if (j < W_INSTR) glds16(wsrc + j * 1024 + woff, buf + j * 1024);
         }
         const char *planes = in_n + (size_t)(2 * q) * plane_bytes;
-#ifdef CAE_EXP_F16C_NOHDMA  // timing-only ablation: halo staged for stage 0 only (wrong results)
-        if (q == 0 && ky == 0)
-#endif
 #pragma unroll
         for (int i = 0; i < MAXP; ++i) {
             const int j = iw + i * NI;
@@ -442,22 +417,16 @@ __global__ void __launch_bounds__(CAE_CONV_F16_NW * 64, 1) conv_s2_f16_kernel(co
     constexpr int B_PT = 2 * WH * 16;        // column tile 0 -> 1 (two rows down)
     int sc = 0;
 
-#ifdef CAE_EXP_SETPRIO  // static priority for the younger half of the block (MI355X_MICROARCH.md, two waves per SIMD, item 4)
-    if (wave >= NW / 2) __builtin_amdgcn_s_setprio(1);
-#endif
     issue_stage(0, std::integral_constant<int, 0>{}, smem);
     for (int q = 0; q < p.cci; ++q) {
         static_for<KS>([&](auto ky_tag) {
             constexpr int ky = decltype(ky_tag)::value;
             wait_vm0();
-#ifndef CAE_EXP_F16C_NOBAR  // timing-only ablations of this loop (wrong results): profiles/r01_experiments.md
             __syncthreads();
-#endif
             char *cur = smem + (sc & 1) * STAGE_BYTES;
             char *nxt = smem + ((sc + 1) & 1) * STAGE_BYTES;
             // the whole next stage is issued here, at the top: spreading the LDS-DMA instructions between the MFMA
             // groups was measured 8-11 % slower (the data simply lands later), profiles/r01_experiments.md
-#ifndef CAE_EXP_F16C_NODMA
             if constexpr (ky + 1 < KS) {
                 issue_stage(q, std::integral_constant<int, ky + 1>{}, nxt);
             } else {
@@ -467,16 +436,11 @@ __global__ void __launch_bounds__(CAE_CONV_F16_NW * 64, 1) conv_s2_f16_kernel(co
                     issue_gamma0<CT, NW>(p, nxt, wave, lane);
                 }
             }
-#endif
             const char *wb = cur + lane * 16;
             const char *hb = cur + b_off;
 #pragma unroll
             for (int kx = 0; kx < KS; ++kx) {
-#ifdef CAE_EXP_F16C_ONETAP
-                constexpr int kxr = 0;  // every tap re-uses tap 0's operands: one third of the LDS reads
-#else
                 const int kxr = kx;
-#endif
                 f16x8 bh[PT], bl[PT];
 #pragma unroll
                 for (int pt = 0; pt < PT; ++pt) {
@@ -912,11 +876,7 @@ __global__ void __launch_bounds__(512, 1) conv_first_f16_kernel(const LayerArgs 
         __builtin_amdgcn_wave_barrier();
         if (has_next) commit();
         __builtin_amdgcn_wave_barrier();
-#if CAE_FIRST_PIPE
         if constexpr (GDN) gdn_resident_pipe_f16<CT, false>(acc, gbuf, beta_lds, lane);
-#else
-        if constexpr (GDN) gdn_resident_f16<CT, false>(acc, gbuf, beta_lds, lane);
-#endif
         const int oy = ty * TY + 2 * wave + (m >> 4), ox = tx * TX + (m & 15);
         store_tiles_f16<CT, false, !GDN>(acc, p, n, oy, ox, h, oy < p.OH && ox < p.OW);
     }
@@ -942,7 +902,7 @@ __host__ __device__ __forceinline__ size_t pmap_record(int n, int OH, int OW, in
 
 // j0: index (in its parity row) of the wave's first pixel; tbuf: 4 KiB of LDS private to the wave.  The accumulator
 // layout gives every lane four scattered 16-byte pieces of its pixel's record; written like that (16 bytes per lane at a
-// 128-byte stride) the store cost 0.25 ms of deconv3's 3.07 (CAE_EXP_PMAP_NOSTORE).  So the tile is transposed through
+// 128-byte stride) the store cost 0.25 ms of deconv3's 3.07 (timed without it).  So the tile is transposed through
 // LDS (XOR-swizzled pieces: conflict-free both ways) and leaves as four instructions of 1 KiB contiguous each.
 template <int CT>
 __device__ __forceinline__ void store_pmap_f16(const f32x16 (&y)[CT], const LayerArgs &p, char *tbuf, int n, int oy, int par,
@@ -972,9 +932,6 @@ __device__ __forceinline__ void store_pmap_f16(const f32x16 (&y)[CT], const Laye
             pm = mfma3(ah, al, sh, sl, pm);
         }
     raise_if_over(mx, p.flag);
-#ifdef CAE_EXP_PMAP_NOSTORE  // timing-only ablation: the map is computed but not written (wrong results)
-    if (p.N > 0) return;
-#endif
     // D: register r = map row acc_row(r) + 4h: lane (m, h) holds pieces q = 2g + h (g = 0..3) of pixel m's record
     __builtin_amdgcn_wave_barrier();
 #pragma unroll
@@ -1119,7 +1076,7 @@ struct DeconvGeomF16 {
     static constexpr int G_BYTES = IGDN ? CT * 4096 : 0;
     static constexpr int CONV_STAGE = W_BYTES + HALO_INSTR * 1024;
     static constexpr int STAGE_BYTES = CONV_STAGE > G_BYTES ? CONV_STAGE : G_BYTES;
-    static constexpr int NI = NW / CAE_F16_ISSUERS > 0 ? NW / CAE_F16_ISSUERS : 1;  // LDS-DMA issuer waves (conv_s2_f16)
+    static constexpr int NI = NW / F16_ISSUERS > 0 ? NW / F16_ISSUERS : 1;  // LDS-DMA issuer waves (conv_s2_f16)
     static constexpr int MAXP = (HALO_INSTR + NI - 1) / NI;
     // aligned pieces per issuer and their (plane, half) step: piece i of issuer iw is instruction iw + i NI, i.e. halo
     // piece (iw 64 + lane) + i NI 64 -- the same (row, column), AL_STEP (plane, half) images further
@@ -1201,7 +1158,6 @@ __device__ __forceinline__ void deconv_phase_f16(const LayerArgs &p, const char 
         __syncthreads();
         char *cur = smem + (sc & 1) * STAGE_BYTES;
         char *nxt = smem + ((sc + 1) & 1) * STAGE_BYTES;
-#ifndef CAE_EXP_F16_NODMA  // timing-only ablation: no LDS-DMA after the first stage (wrong results)
         if (s + 1 < NS) {
             deconv_issue_f16<KS, CT, NW, PT, IGDN, PY>(p, in_n, plane_bytes, s + 1, nxt, hrow, hbase, wave, lane);
         } else if (IGDN && !G::RESIDENT) {
@@ -1209,56 +1165,8 @@ __device__ __forceinline__ void deconv_phase_f16(const LayerArgs &p, const char 
         } else if (PY == 0) {
             deconv_issue_f16<KS, CT, NW, PT, IGDN, 1>(p, in_n, plane_bytes, 0, nxt, hrow, hbase, wave, lane);
         }
-#endif
         const char *wb = cur + lane * 16;
-#if CAE_F16_PIPE
-        if constexpr (PT == 1) {
-            // software-pipelined stage: the operand fragments of group pair g + 1 are read from LDS before the six
-            // MFMAs of pair g are issued (one register set ahead), and the two groups of a pair (two channel tiles of a
-            // tap) alternate so that consecutive MFMAs never depend on each other.  Without this the compiler
-            // re-used ONE fragment register set: read -> lgkmcnt(0) -> 1-2 MFMAs, the LDS latency exposed 24 times
-            // per stage and wave.
-            static_assert(CT % 2 == 0 || CT == 1, "channel tiles are paired");
-            constexpr int GP = CT == 1 ? 1 : 2;          // groups (channel tiles) per step
-            constexpr int NSTEP = KS * CT / GP;
-            f16x8 a[2][GP][2], b[2][2];                  // [set][group][hi, lo], [set][hi, lo]
-            auto load_b = [&](int kx, int set) {
-                const bool stray = (stray_mask >> kx) & 1;
-                const int b_hl = stray ? G::ROWS * 16 : G::ROWS * 32 * 16;
-                b[set][0] = *(const f16x8 *)(cur + b_off[kx]);
-                b[set][1] = *(const f16x8 *)(cur + b_off[kx] + b_hl);
-            };
-            auto load_a = [&](int step, int set) {
-#pragma unroll
-                for (int g = 0; g < GP; ++g) {
-                    a[set][g][0] = *(const f16x8 *)(wb + ((step * GP + g) * 2 + 0) * 1024);
-                    a[set][g][1] = *(const f16x8 *)(wb + ((step * GP + g) * 2 + 1) * 1024);
-                }
-            };
-            load_b(0, 0);
-            load_a(0, 0);
-            __builtin_amdgcn_sched_group_barrier(0x100, 2 + 2 * GP, 0);
-            static_for<NSTEP>([&](auto it) {
-                constexpr int st = decltype(it)::value;
-                constexpr int kx = st * GP / CT, ct0 = st * GP % CT;
-                constexpr int px = (kx + P) & 1;
-                constexpr bool more = st + 1 < NSTEP, next_tap = more && (st + 1) * GP % CT == 0;
-                constexpr int nread = more ? 2 * GP + (next_tap ? 2 : 0) : 0;
-                if constexpr (more) load_a(st + 1, (st + 1) & 1);
-                if constexpr (next_tap) load_b(kx + 1, (kx + 1) & 1);
-                const f16x8 bh = b[kx & 1][0], bl = b[kx & 1][1];
-                f32x16 *dst = px == 0 ? acc[0][0] : acc[1][0];
-#pragma unroll
-                for (int m = 0; m < 3; ++m)
-#pragma unroll
-                    for (int g = 0; g < GP; ++g)
-                        dst[ct0 + g] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[st & 1][g][m == 2], m == 1 ? bl : bh,
-                                                                              dst[ct0 + g], 0, 0, 0);
-                if constexpr (nread > 0) __builtin_amdgcn_sched_group_barrier(0x100, nread, 0);  // next step's reads,
-                __builtin_amdgcn_sched_group_barrier(0x008, 3 * GP, 0);                         // then this step's MFMAs
-            });
-        } else
-#endif
+        // (a software-pipelined form of this K loop measured no faster: profiles/r02_experiments.md)
 #pragma unroll
         for (int kx = 0; kx < KS; ++kx) {
             if (PT > 1) __builtin_amdgcn_sched_barrier(0);  // bound operand live ranges to one tap (register budget)
@@ -1274,11 +1182,7 @@ __device__ __forceinline__ void deconv_phase_f16(const LayerArgs &p, const char 
             }
 #pragma unroll
             for (int ct = 0; ct < CT; ++ct) {
-#ifdef CAE_EXP_F16_FEWREADS  // timing-only ablation: one weight fragment pair per tap instead of CT (wrong results)
-                constexpr int ctr = 0;
-#else
                 const int ctr = ct;
-#endif
                 const f16x8 ah = *(const f16x8 *)(wb + ((kx * CT + ctr) * 2 + 0) * 1024);
                 const f16x8 al = *(const f16x8 *)(wb + ((kx * CT + ctr) * 2 + 1) * 1024);
 #pragma unroll
@@ -1394,9 +1298,6 @@ __global__ void __launch_bounds__(NW * 64, NW * PT <= 4 ? 2 : 1) deconv_s2_f16_k
         for (int j = wave; j < G::G_ALL / 1024; j += NW)
             glds16((const char *)p.gp + (size_t)j * 1024 + lane * 16, smem + 2 * G::STAGE_BYTES + j * 1024);
     }
-#ifdef CAE_EXP_SETPRIO
-    if (wave >= NW / 2) __builtin_amdgcn_s_setprio(1);
-#endif
     deconv_issue_f16<KS, CT, NW, PT, IGDN, 0>(p, in_n, plane_bytes, 0, smem, hrow, hbase, wave, lane);
     deconv_phase_f16<KS, CT, NW, PT, IGDN, 0>(p, in_n, plane_bytes, smem, sc, hrow, hbase, wave, lane, b_off, stray_mask, n,
                                               iy, ix);

@@ -1,14 +1,13 @@
 // Launchers of the kernel families; each is defined in its own translation unit (cae_launch_*.hip).
 #pragma once
 #include <hip/hip_runtime.h>
-#include "cae_internal.hpp"
 
-#ifndef CAE_CONV_NW
-#define CAE_CONV_NW 4
-#endif
-#ifndef CAE_DECONV_NW
-#define CAE_DECONV_NW 4
-#endif
+#include <map>
+#include <mutex>
+#include <utility>
+
+#include "cae_hip.h"
+#include "cae_internal.hpp"
 
 #define HIP_TRY(expr)                                                                             \
     do {                                                                                          \
@@ -16,7 +15,55 @@
         if (e_ != hipSuccess) return ::cae::fail(CAE_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_));  \
     } while (0)
 
+// returns a CAE_* error code early
+#define CAE_TRY(expr)                          \
+    do {                                       \
+        const int rc_ = (expr);                \
+        if (rc_ != CAE_OK) return rc_;         \
+    } while (0)
+
 namespace cae {
+// waves per block of the fp32 conv_s2_kernel / deconv_s2_kernel (the host sizes their tile grids from them)
+constexpr int CONV_NW = 4;
+constexpr int DECONV_NW = 4;
+
+// Guards the per-device launch state below (and the training path's zero pages).
+inline std::mutex &launch_mutex() {
+    static std::mutex mu;
+    return mu;
+}
+
+// Raises `kernel`'s dynamic LDS limit on the current device to at least `bytes` (the attribute is per device; it is set
+// once per kernel, device and larger size).
+inline int ensure_lds(const void *kernel, int bytes) {
+    int dev = 0;
+    HIP_TRY(hipGetDevice(&dev));
+    static std::map<std::pair<const void *, int>, int> seen;  // (kernel, device) -> bytes set
+    std::lock_guard<std::mutex> lock(launch_mutex());
+    int &have = seen[{kernel, dev}];
+    if (have < bytes) {
+        HIP_TRY(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+        have = bytes;
+    }
+    return CAE_OK;
+}
+
+// Compute units of the current device, into `cus` (sizes the persistent grids).
+inline int device_cus(int &cus) {
+    int dev = 0;
+    HIP_TRY(hipGetDevice(&dev));
+    static std::map<int, int> known;
+    std::lock_guard<std::mutex> lock(launch_mutex());
+    auto it = known.find(dev);
+    if (it == known.end()) {
+        int n = 0;
+        HIP_TRY(hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev));
+        it = known.emplace(dev, n).first;
+    }
+    cus = it->second;
+    return CAE_OK;
+}
+
 struct LayerArgs;
 struct FirstArgs;
 int launch_conv(int ks, int ct, bool gdn, const LayerArgs &a, hipStream_t st);

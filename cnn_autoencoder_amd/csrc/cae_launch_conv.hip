@@ -7,22 +7,14 @@
 namespace cae {
 template <int KS, int CT, bool GDN>
 static int launch_conv_t(const LayerArgs &a, hipStream_t st) {
-    constexpr int NW = CAE_CONV_NW;
+    constexpr int NW = CONV_NW;
     constexpr int WH = 2 * 16 + KS - 2;
     constexpr int HALO_INSTR = (2 * NW * WH * 2 + 63) / 64;
     constexpr int CONV_STAGE = KS * CT * 1024 + HALO_INSTR * 1024;
     constexpr int G_BYTES = GDN ? CT * 4096 : 0;
-#ifdef CAE_EXP_1BLOCK
-    constexpr int LDS = 96 * 1024;
-#else
     constexpr int LDS = 2 * (CONV_STAGE > G_BYTES ? CONV_STAGE : G_BYTES);
-#endif
     auto kern = conv_s2_kernel<KS, CT, NW, GDN>;
-    static bool attr_done = false;
-    if (!attr_done) {
-        HIP_TRY(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
-        attr_done = true;
-    }
+    CAE_TRY(ensure_lds((const void *)kern, LDS));
     const unsigned grid = (unsigned)((size_t)a.N * a.tiles_x * a.tiles_y);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(NW * 64), LDS, st, a);
     HIP_TRY(hipGetLastError());
@@ -42,7 +34,7 @@ static int launch_conv_t(const LayerArgs &a, hipStream_t st) {
 // flipped weights (ConvTranspose2d stride 1, synthesis)
 template <int KS, int CT, bool ZP, bool GDN>
 static int launch_conv_s1_t(const LayerArgs &a, hipStream_t st) {
-    constexpr int NW = CAE_CONV_NW;
+    constexpr int NW = CONV_NW;
     constexpr int WH = 15 + KS;
     constexpr int HALO_INSTR = (2 * NW * WH * 2 + 63) / 64;
     constexpr int CONV_STAGE = KS * CT * 1024 + HALO_INSTR * 1024;
@@ -50,11 +42,7 @@ static int launch_conv_s1_t(const LayerArgs &a, hipStream_t st) {
     constexpr int LDS = 2 * (CONV_STAGE > G_BYTES ? CONV_STAGE : G_BYTES);
     // GDN on the analysis track (reflect padded), IGDN on the synthesis track (zero padded, flipped weights)
     auto kern = conv_s2_kernel<KS, CT, NW, GDN, 1, ZP, GDN && ZP>;
-    static bool attr_done = false;
-    if (!attr_done) {
-        HIP_TRY(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
-        attr_done = true;
-    }
+    CAE_TRY(ensure_lds((const void *)kern, LDS));
     const unsigned grid = (unsigned)((size_t)a.N * a.tiles_x * a.tiles_y);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(NW * 64), LDS, st, a);
     HIP_TRY(hipGetLastError());

@@ -7,7 +7,7 @@
 namespace cae {
 template <int KS, int CT, bool GDN>
 static int launch_conv_f16_t(const LayerArgs &a, hipStream_t st) {
-    constexpr int NW = CAE_CONV_F16_NW;
+    constexpr int NW = CONV_F16_NW;
     constexpr int WH = 2 * 16 + KS - 2;
     constexpr int HALO_INSTR = (4 * 16 * WH + 63) / 64;
     constexpr int CONV_STAGE = KS * CT * 2 * 1024 + HALO_INSTR * 1024;
@@ -17,11 +17,7 @@ static int launch_conv_f16_t(const LayerArgs &a, hipStream_t st) {
         return fail(CAE_ERR_UNSUPPORTED, "f16x3: this kernel_size/channel combination exceeds the LDS; use fp32");
     } else {
         auto kern = conv_s2_f16_kernel<KS, CT, GDN>;
-        static bool attr_done = false;
-        if (!attr_done) {
-            HIP_TRY(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
-            attr_done = true;
-        }
+        CAE_TRY(ensure_lds((const void *)kern, LDS));
         const unsigned grid = (unsigned)((size_t)a.N * a.tiles_x * a.tiles_y);
         hipLaunchKernelGGL(kern, dim3(grid), dim3(NW * 64), LDS, st, a);
         HIP_TRY(hipGetLastError());
@@ -46,7 +42,7 @@ static int launch_conv_f16_t(const LayerArgs &a, hipStream_t st) {
 // units' transposed convolutions) instead of reflection (analysis units, and the colour layers of the synthesis track).
 template <int KS, int CT, bool GDN, bool SYN, bool ZP>
 static int launch_conv_s1_f16_t(const LayerArgs &a, hipStream_t st) {
-    constexpr int NW = CAE_CONV_F16_NW;
+    constexpr int NW = CONV_F16_NW;
     constexpr int WH = 16 + KS - 1;
     constexpr int HALO_INSTR = (4 * 16 * WH + 63) / 64;
     constexpr int CONV_STAGE = KS * CT * 2 * 1024 + HALO_INSTR * 1024;
@@ -56,11 +52,7 @@ static int launch_conv_s1_f16_t(const LayerArgs &a, hipStream_t st) {
         return fail(CAE_ERR_UNSUPPORTED, "f16x3: this kernel_size/channel combination exceeds the LDS; use fp32");
     } else {
         auto kern = conv_s2_f16_kernel<KS, CT, GDN, 1, SYN, ZP, (CT <= 4)>;
-        static bool attr_done = false;
-        if (!attr_done) {
-            HIP_TRY(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
-            attr_done = true;
-        }
+        CAE_TRY(ensure_lds((const void *)kern, LDS));
         const unsigned grid = (unsigned)((size_t)a.N * a.tiles_x * a.tiles_y);
         hipLaunchKernelGGL(kern, dim3(grid), dim3(NW * 64), LDS, st, a);
         HIP_TRY(hipGetLastError());

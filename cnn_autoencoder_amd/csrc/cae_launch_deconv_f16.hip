@@ -9,10 +9,7 @@ template <int KS, int CT, bool GDN>
 static int launch_deconv_f16_t(const LayerArgs &a, hipStream_t st) {
     // 8 waves x 1 input row measured faster than 4 waves x 2 rows (register spills at 512 VGPRs):
     // profiles/r01_experiments.md
-#ifndef CAE_DF16_NW
-#define CAE_DF16_NW 8
-#endif
-    constexpr int NW = CAE_DF16_NW, PT = 1;
+    constexpr int NW = 8, PT = 1;
     using G = DeconvGeomF16<KS, CT, NW, PT, GDN>;
     constexpr int LDS = G::lds_bytes(false);
     if constexpr (2 * G::STAGE_BYTES > 160 * 1024) {
@@ -22,11 +19,7 @@ static int launch_deconv_f16_t(const LayerArgs &a, hipStream_t st) {
         const bool pmap = a.outfmt == OUT_PMAP;
         const int lds = pmap ? G::lds_bytes(true) : LDS;
         if (lds > 160 * 1024) return fail(CAE_ERR_UNSUPPORTED, "product map: LDS exceeded");
-        static int attr_bytes = 0;
-        if (lds > attr_bytes) {
-            HIP_TRY(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-            attr_bytes = lds;
-        }
+        CAE_TRY(ensure_lds((const void *)kern, lds));
         LayerArgs b = a;
         b.tiles_y = (a.H + G::ROWS - 1) / G::ROWS;  // input rows per block follow the kernel's wave count
         const unsigned grid = (unsigned)((size_t)b.N * b.tiles_x * b.tiles_y);

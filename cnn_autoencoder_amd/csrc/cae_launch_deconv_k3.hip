@@ -7,7 +7,7 @@
 namespace cae {
 template <int KS, int CT, bool GDN>
 static int launch_deconv_t(const LayerArgs &a, hipStream_t st) {
-    constexpr int NW = CAE_DECONV_NW;
+    constexpr int NW = DECONV_NW;
     constexpr int P = KS / 2;
     constexpr int WH = 32 + (KS - 1 - P) / 2 + (P + 1) / 2;
     constexpr int HALO_INSTR = (NW * WH * 2 + 63) / 64;
@@ -15,11 +15,7 @@ static int launch_deconv_t(const LayerArgs &a, hipStream_t st) {
     constexpr int G_BYTES = GDN ? CT * 4096 : 0;
     constexpr int LDS = 2 * (CONV_STAGE > G_BYTES ? CONV_STAGE : G_BYTES);
     auto kern = deconv_s2_kernel<KS, CT, NW, GDN>;
-    static bool attr_done = false;
-    if (!attr_done) {
-        HIP_TRY(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
-        attr_done = true;
-    }
+    CAE_TRY(ensure_lds((const void *)kern, LDS));
     const unsigned grid = (unsigned)((size_t)a.N * a.tiles_x * a.tiles_y);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(NW * 64), LDS, st, a);
     HIP_TRY(hipGetLastError());

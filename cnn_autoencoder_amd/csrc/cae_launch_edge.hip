@@ -11,11 +11,7 @@ static int launch_first_t(const LayerArgs &a, const FirstArgs &f, hipStream_t st
     constexpr int WH = 2 * 16 + KS - 2, HH = 4 * NW + KS - 2;
     constexpr int LDS = 2 * (GDN ? CT * 4096 : 0) + KS * KS * CT * 512 + ((HH * WH * 16 + 1023) / 1024) * 1024 + 1024;
     auto kern = conv_first_kernel<KS, CT, NW, GDN>;
-    static bool attr_done = false;
-    if (!attr_done) {
-        HIP_TRY(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
-        attr_done = true;
-    }
+    CAE_TRY(ensure_lds((const void *)kern, LDS));
     const unsigned grid = (unsigned)((size_t)a.N * a.tiles_x * a.tiles_y);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(NW * 64), LDS, st, a, f);
     HIP_TRY(hipGetLastError());
@@ -30,7 +26,7 @@ static int launch_last_t(const LayerArgs &a, hipStream_t st) {
     constexpr int HALO_INSTR = (4 * (NW + NB - 1) * (64 + NB - 1) + 63) / 64;
     const int lds = 2 * HALO_INSTR * 1024 + NB * NB * a.cci * 1024;
     auto kern = deconv_last_kernel<KS, NW>;
-    HIP_TRY(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    CAE_TRY(ensure_lds((const void *)kern, 160 * 1024));
     const unsigned grid = (unsigned)((size_t)a.N * a.tiles_x * a.tiles_y);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(NW * 64), lds, st, a);
     HIP_TRY(hipGetLastError());

@@ -16,16 +16,10 @@ static int launch_first_f16_t(const LayerArgs &a, const FirstArgs &f, hipStream_
     } else {
         auto kern_u8 = conv_first_f16_kernel<KS, CT, GDN, true>;
         auto kern_f32 = conv_first_f16_kernel<KS, CT, GDN, false>;
-        static bool attr_done = false;
-        static int n_cu = 0;
-        if (!attr_done) {
-            HIP_TRY(hipFuncSetAttribute((const void *)kern_u8, hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
-            HIP_TRY(hipFuncSetAttribute((const void *)kern_f32, hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
-            int dev = 0;
-            HIP_TRY(hipGetDevice(&dev));
-            HIP_TRY(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev));
-            attr_done = true;
-        }
+        int n_cu = 0;
+        CAE_TRY(ensure_lds((const void *)kern_u8, LDS));
+        CAE_TRY(ensure_lds((const void *)kern_f32, LDS));
+        CAE_TRY(device_cus(n_cu));
         LayerArgs b = a;
         b.tiles_x = (a.OW + G::TX - 1) / G::TX;
         b.tiles_y = (a.OH + G::TY - 1) / G::TY;
@@ -61,15 +55,9 @@ static int launch_gdn_f16_t(const LayerArgs &a, hipStream_t st) {
     constexpr int LDS = CT * CT * 4096 + CT * 32 * 4;
     static_assert(LDS <= 160 * 1024, "packed gamma must fit the LDS");
     auto kern = gdn_f16_kernel<CT, INVERSE, INVERSE>;  // analysis rows are C8S, synthesis rows C8SP
-    static bool attr_done = false;
-    static int n_cu = 0;
-    if (!attr_done) {
-        HIP_TRY(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
-        int dev = 0;
-        HIP_TRY(hipGetDevice(&dev));
-        HIP_TRY(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev));
-        attr_done = true;
-    }
+    int n_cu = 0;
+    CAE_TRY(ensure_lds((const void *)kern, LDS));
+    CAE_TRY(device_cus(n_cu));
     const size_t groups = c8s_row_bytes<INVERSE>(a.OW) / 1024;
     const size_t total = (size_t)a.N * a.OH * groups;  // wave tiles of 32 pixels
     if (total > 0x7fffffff) return fail(CAE_ERR_ARG, "batch too large");
@@ -91,15 +79,9 @@ static int launch_last_f16_t(const LayerArgs &a, hipStream_t st) {
     const int lds = G::lds_bytes(a.cci);
     if (lds > 160 * 1024) return fail(CAE_ERR_UNSUPPORTED, "last-layer weights do not fit the LDS");
     auto kern = deconv_last_f16_kernel<KS, NW, DEPTH>;
-    static bool attr_done = false;
-    static int n_cu = 0;
-    if (!attr_done) {
-        HIP_TRY(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        int dev = 0;
-        HIP_TRY(hipGetDevice(&dev));
-        HIP_TRY(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev));
-        attr_done = true;
-    }
+    int n_cu = 0;
+    CAE_TRY(ensure_lds((const void *)kern, 160 * 1024));
+    CAE_TRY(device_cus(n_cu));
     LayerArgs b = a;
     b.tiles_x = (a.W + G::TXC - 1) / G::TXC;
     b.tiles_y = (a.H + NW - 1) / NW;

@@ -6,18 +6,32 @@
 #include "cae_train_gdn.hpp"
 
 #include <algorithm>
-#include <cstdlib>
+#include <atomic>
+#include <map>
+#include <mutex>
 
 using namespace cae;
 using namespace cae::tr;
 
 namespace {
 
+std::atomic<int> g_samples_per_block{0};  // cae_t_set_samples_per_block (0: automatic)
+
+// 1 KiB of zeros on the current device (the halo source of positions outside the input), or null
 const void *zero_page() {
-    static void *z = nullptr;
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return nullptr;
+    static std::map<int, void *> pages;
+    std::lock_guard<std::mutex> lock(launch_mutex());
+    void *&z = pages[dev];
     if (!z) {
-        if (hipMalloc(&z, 1024) != hipSuccess) return nullptr;
-        (void)hipMemset(z, 0, 1024);
+        void *p = nullptr;
+        if (hipMalloc(&p, 1024) != hipSuccess) return nullptr;
+        if (hipMemset(p, 0, 1024) != hipSuccess) {
+            (void)hipFree(p);
+            return nullptr;
+        }
+        z = p;
     }
     return z;
 }
@@ -32,11 +46,7 @@ bool bad_channels(int c) { return c < 32 || c % 32 != 0 || c > 192; }
 template <int NT, bool PIPE>
 int launch_gg_tp(const GGArgs &a, size_t lds, hipStream_t st) {
     auto kern = gather_gemm_kernel<NT, PIPE>;
-    static size_t attr = 0;
-    if (lds > attr) {
-        HIP_TRY(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr = lds;
-    }
+    CAE_TRY(ensure_lds((const void *)kern, (int)lds));
     const unsigned grid = (unsigned)((size_t)a.N * a.tiles_x * a.tiles_y);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, a);
     HIP_TRY(hipGetLastError());
@@ -49,15 +59,10 @@ int launch_gg8(GGArgs &a, hipStream_t st) {
     auto kern = gg8_kernel<NT, NQ, NTAPS>;
     const size_t h_instr = (size_t)(NQ * a.HR * a.HC + 63) / 64;
     const size_t lds = 2 * (h_instr + (size_t)NTAPS * NT * (NQ / 2)) * 1024;
-    static size_t attr = 0;
-    if (lds > attr) {
-        HIP_TRY(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr = lds;
-    }
+    CAE_TRY(ensure_lds((const void *)kern, (int)lds));
     // samples per block: enough blocks for two rounds over the 256 CUs, the rest of the batch amortises a block's prologue
     const size_t tiles = (size_t)a.tiles_x * a.tiles_y;
-    const char *enpb = std::getenv("CAE_GG8_NPB");  // (read per call: tests and A/B runs switch it)
-    const int forced = enpb ? std::atoi(enpb) : 0;
+    const int forced = g_samples_per_block.load(std::memory_order_relaxed);
     a.npb = forced > 0 ? std::min(forced, a.N) : (int)std::min<size_t>(std::max<size_t>((size_t)a.N * tiles / 512, 1), (size_t)a.N);
     const unsigned grid = (unsigned)(tiles * (size_t)((a.N + a.npb - 1) / a.npb));
     hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, st, a);
@@ -67,11 +72,7 @@ int launch_gg8(GGArgs &a, hipStream_t st) {
 
 // -> true when a gg8 instantiation covers the launch (rc holds its result)
 bool try_gg8(GGArgs &a, int NT, hipStream_t st, int &rc) {
-    static const char *e8 = std::getenv("CAE_GG8");
-    static const bool off = std::getenv("CAE_GG_LEGACY") != nullptr || (e8 && e8[0] == '0');
-    if (off) return false;
-    const char *ewide = std::getenv("CAE_GG8_WIDE");  // "0": 192-channel outputs stay on gather_gemm_kernel (A/B)
-    if (NT == 6 && !(ewide && ewide[0] == '0') && (a.ntaps == 9 || a.ntaps == 4 || a.ntaps == 2 || a.ntaps == 1)) {
+    if (NT == 6 && (a.ntaps == 9 || a.ntaps == 4 || a.ntaps == 2 || a.ntaps == 1)) {
         // 192 output channels: two launches of three n-tiles (six do not leave room for two slice buffers in the LDS)
         int nq = 0;
         for (int q : {4, 2}) {
@@ -135,7 +136,7 @@ int launch_gg(GGArgs &a, hipStream_t st) {
     a.nq = 0;
     for (int nq : {4, 2}) {
         const size_t slice = (size_t)((nq * a.HR * a.HC + 63) / 64) * 1024 + (size_t)a.ntaps * NT * (nq / 2) * 1024;
-        if (2 * slice <= 160 * 1024 && !std::getenv("CAE_GG_LEGACY")) {
+        if (2 * slice <= 160 * 1024) {
             a.nq = nq;
             lds = 2 * slice;
             break;
@@ -159,10 +160,9 @@ int launch_gg(GGArgs &a, hipStream_t st) {
     }
 }
 
-// strided correlation: position (i, j) <- input (2i + ky - P, 2j + kx - P), every tap
-int strided_corr(const void *in16, int n, int ih, int iw, int ck, const void *packed, int ks, int reflect, float *out32,
-                 void *out16, int cn, int oh, int ow, const float *bias, hipStream_t st, int act = 0) {
-    if (ks != 3 && ks != 5) return fail(CAE_ERR_UNSUPPORTED, "kernel_size %d not supported (3 or 5)", ks);
+// operands, shapes, strides and activation of a gather-GEMM launch; the rest of the fields zero
+GGArgs gg_args(const void *in16, int n, int ih, int iw, int ck, const void *packed, float *out32, void *out16, int cn, int oh,
+               int ow, const float *bias, int S, int SO, int act) {
     GGArgs a{};
     a.in = in16;
     a.out32 = out32;
@@ -176,12 +176,20 @@ int strided_corr(const void *in16, int n, int ih, int iw, int ck, const void *pa
     a.Cn = cn;
     a.OH = oh;
     a.OW = ow;
+    a.S = S;
+    a.SO = SO;
+    a.act = act;
+    return a;
+}
+
+// strided correlation: position (i, j) <- input (2i + ky - P, 2j + kx - P), every tap
+int strided_corr(const void *in16, int n, int ih, int iw, int ck, const void *packed, int ks, int reflect, float *out32,
+                 void *out16, int cn, int oh, int ow, const float *bias, hipStream_t st, int act = 0) {
+    if (ks != 3 && ks != 5) return fail(CAE_ERR_UNSUPPORTED, "kernel_size %d not supported (3 or 5)", ks);
+    GGArgs a = gg_args(in16, n, ih, iw, ck, packed, out32, out16, cn, oh, ow, bias, 2, 1, act);
     a.LH = oh;
     a.LW = ow;
-    a.S = 2;
-    a.SO = 1;
     a.reflect = reflect;
-    a.act = act;
     a.ktaps = ks * ks;
     a.ntaps = ks * ks;
     const int P = ks / 2;
@@ -205,11 +213,7 @@ int launch_gg8t(GGArgs &a, hipStream_t st) {
     auto kern = gg8t_kernel<EXT>;
     const size_t h_instr = (size_t)(4 * a.HR * a.HC + 63) / 64;
     const size_t lds = 2 * (h_instr + 9 * 2 * 2) * 1024;
-    static size_t attr = 0;
-    if (lds > attr) {
-        HIP_TRY(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr = lds;
-    }
+    CAE_TRY(ensure_lds((const void *)kern, (int)lds));
     const size_t tiles = (size_t)a.tiles_x * a.tiles_y, halves = (size_t)a.Cn / 64;
     a.npb = (int)std::min<size_t>(std::max<size_t>((size_t)a.N * tiles * halves / 512, 1), (size_t)a.N);
     const unsigned grid = (unsigned)(tiles * (size_t)((a.N + a.npb - 1) / a.npb));
@@ -220,26 +224,10 @@ int launch_gg8t(GGArgs &a, hipStream_t st) {
 
 bool try_gg8t(const void *in16, int n, int ih, int iw, int ck, const void *packed, int shift, float *out32, void *out16, int cn,
               int oh, int ow, const float *bias, hipStream_t st, int act, int &rc) {
-    const char *e = std::getenv("CAE_GG8T");
-    if ((e && e[0] == '0') || std::getenv("CAE_GG_LEGACY") || cn % 64 || bad_channels(ck) || bad_channels(cn)) return false;
-    GGArgs a{};
-    a.in = in16;
-    a.out32 = out32;
-    a.out16 = out16;
-    a.wp = packed;
-    a.bias = bias;
-    a.N = n;
-    a.IH = ih;
-    a.IW = iw;
-    a.Ck = ck;
-    a.Cn = cn;
-    a.OH = oh;
-    a.OW = ow;
+    if (cn % 64 || bad_channels(ck) || bad_channels(cn)) return false;
+    GGArgs a = gg_args(in16, n, ih, iw, ck, packed, out32, out16, cn, oh, ow, bias, 1, 2, act);
     a.LH = (oh + 1) / 2;
     a.LW = (ow + 1) / 2;
-    a.S = 1;
-    a.SO = 2;
-    a.act = act;
     a.ktaps = 9;
     a.ntaps = 9;
     int nt = 0, dymin = 1 << 20, dymax = -(1 << 20), dxmin = 1 << 20, dxmax = -(1 << 20);
@@ -283,28 +271,12 @@ int strided_corr_t(const void *in16, int n, int ih, int iw, int ck, const void *
         return rc8t;
     for (int py = 0; py < 2; ++py)
         for (int px = 0; px < 2; ++px) {
-            GGArgs a{};
-            a.in = in16;
-            a.out32 = out32;
-            a.out16 = out16;
-            a.wp = packed;
-            a.bias = bias;
-            a.N = n;
-            a.IH = ih;
-            a.IW = iw;
-            a.Ck = ck;
-            a.Cn = cn;
-            a.OH = oh;
-            a.OW = ow;
+            GGArgs a = gg_args(in16, n, ih, iw, ck, packed, out32, out16, cn, oh, ow, bias, 1, 2, act);
             a.LH = (oh - py + 1) / 2;
             a.LW = (ow - px + 1) / 2;
             if (a.LH < 1 || a.LW < 1) continue;
-            a.S = 1;
-            a.SO = 2;
             a.oy0 = py;
             a.ox0 = px;
-            a.reflect = 0;
-            a.act = act;
             a.ktaps = ks * ks;
             int nt = 0;
             for (int ky = 0; ky < ks; ++ky) {
@@ -335,25 +307,11 @@ int stride1_corr(const void *in16, int n, int ih, int iw, int ck, const void *pa
     if (ks != 3 && ks != 5) return fail(CAE_ERR_UNSUPPORTED, "kernel_size %d not supported (3 or 5)", ks);
     if (mode < 0 || mode > 3) return fail(CAE_ERR_ARG, "bad mode %d", mode);
     const int P = ks / 2;
-    GGArgs a{};
-    a.in = in16;
-    a.out32 = out32;
-    a.out16 = out16;
-    a.wp = packed;
-    a.bias = bias;
-    a.N = n;
-    a.IH = ih;
-    a.IW = iw;
-    a.Ck = ck;
-    a.Cn = cn;
-    a.OH = mode == 1 ? ih + 2 * P : ih;
-    a.OW = mode == 1 ? iw + 2 * P : iw;
-    a.LH = a.OH;
-    a.LW = a.OW;
-    a.S = 1;
-    a.SO = 1;
+    const int oh = mode == 1 ? ih + 2 * P : ih, ow = mode == 1 ? iw + 2 * P : iw;
+    GGArgs a = gg_args(in16, n, ih, iw, ck, packed, out32, out16, cn, oh, ow, bias, 1, 1, act);
+    a.LH = oh;
+    a.LW = ow;
     a.reflect = mode == 0;
-    a.act = act;
     a.ktaps = ks * ks;
     a.ntaps = ks * ks;
     for (int ky = 0; ky < ks; ++ky)
@@ -369,11 +327,7 @@ int stride1_corr(const void *in16, int n, int ih, int iw, int ck, const void *pa
 template <int NB>
 int launch_wg_t(const WGArgs &a, size_t lds, int ksplit, int at, int tg, hipStream_t st) {
     auto kern = wgrad_kernel<NB>;
-    static size_t attr = 0;
-    if (lds > attr) {
-        HIP_TRY(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr = lds;
-    }
+    CAE_TRY(ensure_lds((const void *)kern, (int)lds));
     hipLaunchKernelGGL(kern, dim3(ksplit, at, tg), dim3(256), lds, st, a);
     HIP_TRY(hipGetLastError());
     return CAE_OK;
@@ -383,11 +337,7 @@ template <int CT, int MODE>
 int launch_gdn_a_t(const GdnArgs &a, hipStream_t st) {
     auto kern = gdn_gemm_a_kernel<CT, MODE>;
     constexpr int LDS = CT * 32 * (CT * 32 + 4) * 4 + (CT <= 4 ? 2 * 32768 : 0);  // M (+ the A double buffer)
-    static bool done = false;
-    if (!done) {
-        HIP_TRY(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
-        done = true;
-    }
+    CAE_TRY(ensure_lds((const void *)kern, LDS));
     const long tiles = (a.pixels + 255) / 256;
     const unsigned grid = (unsigned)std::min<long>(tiles, 512);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(256), LDS, st, a);
@@ -422,12 +372,8 @@ int launch_gdn_fused_t(const GdnFusedArgs &a, bool backward, hipStream_t st) {
     constexpr int LDS_B = C * (C + 4) * 4 + 4 * 32 * C * 4 + 32 * (C * 2 + 16);
     auto kf = gdn_fwd_fused_kernel<CT>;
     auto kb = gdn_bwd_fused_kernel<CT>;
-    static bool done = false;
-    if (!done) {
-        HIP_TRY(hipFuncSetAttribute((const void *)kf, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_F));
-        HIP_TRY(hipFuncSetAttribute((const void *)kb, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_B));
-        done = true;
-    }
+    CAE_TRY(ensure_lds((const void *)kf, LDS_F));
+    CAE_TRY(ensure_lds((const void *)kb, LDS_B));
     const long tiles = (a.pixels + 31) / 32;
     // persistent blocks walk the tiles: one per CU (backward: Gamma + two tile sets fill the LDS), two per CU (forward)
     const unsigned grid = (unsigned)std::min<long>(tiles, backward ? 256 : 512);
@@ -455,6 +401,12 @@ static int wgrad_impl(const void *xbig16, int n, int h, int w, int ca, const voi
                       int reflect, int S, float *gw32, void *stream);
 
 extern "C" {
+
+int cae_t_set_samples_per_block(int npb) {
+    if (npb < 0) return fail(CAE_ERR_ARG, "samples per block must be 0 (automatic) or positive, got %d", npb);
+    g_samples_per_block.store(npb, std::memory_order_relaxed);
+    return CAE_OK;
+}
 
 size_t cae_t_packed_bytes(int contract_channels, int out_channels, int kernel_size) {
     const size_t q = (contract_channels + 31) / 32, nt = (out_channels + 31) / 32;
@@ -543,25 +495,9 @@ int cae_t_pointwise_acc(const void *x16, int n, int h, int w, int ck, const void
 
 static int pointwise_impl(const void *x16, int n, int h, int w, int ck, const void *packed, float *out32, void *out16, int cn,
                           const float *bias, int act, int acc, hipStream_t st) {
-    GGArgs a{};
-    a.in = x16;
-    a.out32 = out32;
-    a.out16 = out16;
-    a.wp = packed;
-    a.bias = bias;
-    a.N = n;
-    a.IH = h;
-    a.IW = w;
-    a.Ck = ck;
-    a.Cn = cn;
-    a.OH = h;
-    a.OW = w;
+    GGArgs a = gg_args(x16, n, h, w, ck, packed, out32, out16, cn, h, w, bias, 1, 1, act);
     a.LH = h;
     a.LW = w;
-    a.S = 1;
-    a.SO = 1;
-    a.reflect = 0;
-    a.act = act;
     a.acc = acc;
     a.ktaps = 1;
     a.ntaps = 1;
@@ -730,49 +666,27 @@ static int wgrad_impl(const void *xbig16, int n, int h, int w, int ca, const voi
     HIP_TRY(hipMemsetAsync(gw32, 0, (size_t)a.kk * ca * cb * sizeof(float), st));
     const size_t lds = (size_t)((a.HR * a.HC * 4 + 63) / 64) * 1024 + (size_t)((128 * (cb / 8) + 63) / 64) * 1024;
     const int a_tiles = ca / 32, tap_groups = (a.kk + 8) / 9;
-    {
-        // wgrad8_kernel: 8 waves, double-buffered samples; needs two staging buffers in the LDS and Cb <= 128
-        static const char *e8 = std::getenv("CAE_WG8");
-        // up to 128 b channels per launch; a wider Y (192) goes in two halves of 96 (three of the four b-tile waves busy)
-        // (measured: the two-launch form is SLOWER than wgrad_kernel<2> on the canonical 192-channel layers -- 13.97 vs 13.59 ms
-        //  per 128 x 256^2 step, X staged twice and a quarter of the waves idle -- so it is opt-in: CAE_WG8_WIDE=1)
-        static const char *ew = std::getenv("CAE_WG8_WIDE");
-        const bool wide_off = cb > 128 && !(ew && ew[0] == '1');
-        const int parts = cb <= 128 ? 1 : 2, cbl = cb / parts;
-        const int x_instr = (a.HR * a.HC * 4 + 63) / 64, y_instr = (128 * (cbl / 8) + 63) / 64;
-        // (two staging buffers; at least the 80 KiB in which the position groups merge their partial sums at the end)
-        const size_t lds8 = std::max<size_t>(2 * (size_t)(x_instr + y_instr) * 1024, 4 * 5 * 16 * 64 * sizeof(float));
-        if (!(e8 && e8[0] == '0') && !wide_off && cbl % 32 == 0 && cbl <= 128 && x_instr <= 64 && lds8 <= 160 * 1024) {
-            static size_t attr = 0;
-            if (lds8 > attr) {
-                HIP_TRY(hipFuncSetAttribute((const void *)wgrad8_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds8));
-                attr = lds8;
-            }
-            const int tpi = a.tiles_x * a.tiles_y;
-            // sample lanes: about two rounds of blocks over the 256 CUs, each block walking n, n + step, ...
-            // sample lanes: about ONE block per CU, and at least four samples per block -- every block ends with an atomic flush
-            // of its 9 x 32 x Cb partial sums, and that flush, not the contraction, set the time with more blocks
-            // (128 -> 128, 128^2 / 64^2 inputs; batch 128: 512 blocks 0.50 / 0.18 ms, 256 blocks 0.46 / 0.14 ms;
-            //  batch 16: 512 blocks 0.15 / 0.13 ms, 256 / 128 blocks 0.105 / 0.053 ms).  CAE_WG8_BLOCKS overrides the target.
-            const char *estep = std::getenv("CAE_WG8_BLOCKS");
-            const int target = estep ? std::max(1, std::atoi(estep)) : 256;
-            const int base = std::max(1, tpi * a_tiles * tap_groups);
-            const int step = std::max(1, std::min(std::max(1, estep ? n : n / 4), target / base));
-            for (int part = 0; part < parts; ++part) {
-                WGArgs b = a;
-                b.Cbs = cb;
-                b.cb0 = part * cbl;
-                b.Cb = cbl;
-                b.m_ypp = (unsigned)(((1ull << 32) + (unsigned)(cbl / 8) - 1) / (unsigned)(cbl / 8));
-                hipLaunchKernelGGL(wgrad8_kernel, dim3(tpi * step, a_tiles, tap_groups), dim3(512), lds8, st, b, tpi, step);
-                HIP_TRY(hipGetLastError());
-            }
-            return CAE_OK;
-        }
+    // wgrad8_kernel: 8 waves, double-buffered samples; needs two staging buffers in the LDS and Cb <= 128
+    // (the 192-channel layers as two launches of 96 b channels measured slower than wgrad_kernel<2>: r03_experiments.md)
+    const int x_instr = (a.HR * a.HC * 4 + 63) / 64, y_instr = (128 * (cb / 8) + 63) / 64;
+    // (two staging buffers; at least the 80 KiB in which the position groups merge their partial sums at the end)
+    const size_t lds8 = std::max<size_t>(2 * (size_t)(x_instr + y_instr) * 1024, 4 * 5 * 16 * 64 * sizeof(float));
+    if (cb <= 128 && x_instr <= 64 && lds8 <= 160 * 1024) {
+        CAE_TRY(ensure_lds((const void *)wgrad8_kernel, (int)lds8));
+        const int tpi = a.tiles_x * a.tiles_y;
+        // sample lanes: about ONE block per CU, and at least four samples per block -- every block ends with an atomic flush
+        // of its 9 x 32 x Cb partial sums, and that flush, not the contraction, set the time with more blocks
+        // (128 -> 128, 128^2 / 64^2 inputs; batch 128: 512 blocks 0.50 / 0.18 ms, 256 blocks 0.46 / 0.14 ms;
+        //  batch 16: 512 blocks 0.15 / 0.13 ms, 256 / 128 blocks 0.105 / 0.053 ms)
+        const int base = std::max(1, tpi * a_tiles * tap_groups);
+        const int step = std::max(1, std::min(std::max(1, n / 4), 256 / base));
+        a.Cbs = cb;  // (cb0 = 0: all b channels in one launch)
+        hipLaunchKernelGGL(wgrad8_kernel, dim3(tpi * step, a_tiles, tap_groups), dim3(512), lds8, st, a, tpi, step);
+        HIP_TRY(hipGetLastError());
+        return CAE_OK;
     }
     // (about one block per CU here too: 256 blocks 13.06 - 13.11 ms per 128 x 256^2 step, 512: 13.18, 128: 13.15 - 13.18, 64: 13.45 - 13.5)
-    const char *eblk = std::getenv("CAE_WG_BLOCKS");
-    const int ksplit = std::max(1, std::min(a.total_tiles, (eblk ? std::max(1, std::atoi(eblk)) : 256) / (a_tiles * tap_groups)));
+    const int ksplit = std::max(1, std::min(a.total_tiles, 256 / (a_tiles * tap_groups)));
     if (cb / 32 <= 4) return launch_wg_t<1>(a, lds, ksplit, a_tiles, tap_groups, st);
     return launch_wg_t<2>(a, lds, ksplit, a_tiles, tap_groups, st);
 }

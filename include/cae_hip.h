@@ -272,6 +272,9 @@ size_t cae_t_packed_bytes(int contract_channels, int out_channels, int kernel_si
 int cae_t_pack_weights(const float *w_dev, int dim0, int dim1, int kernel_size, int contract_dim, void *packed_dev, void *stream);
 int cae_t_from_nchw(const float *x_nchw_dev, int n, int c, int h, int w, int cp, void *out16, float *out32, void *stream);
 int cae_t_to_nchw(const float *t32, int n, int c, int h, int w, int cp, float *out_nchw_dev, void *stream);
+/* Samples each block of the strided / pointwise gather-GEMM kernels walks (the same tile of consecutive samples);
+ * 0 (the default): chosen per launch from the batch and the tile count.  A testing knob: it forces ragged sample groups. */
+int cae_t_set_samples_per_block(int npb);
 /* z = conv(x) (+bias): x16 [n][h][w][cin_p] -> z [n][ceil(h/2)][ceil(w/2)][cout_p] as fp32 and / or bf16 */
 int cae_t_conv_forward(const void *x16, int n, int h, int w, int cin_p, const void *packed, int kernel_size, float *z32,
                        void *z16, int cout_p, const float *bias, void *stream);

@@ -91,15 +91,25 @@ def test_conv_kernels(cae, cin, cout, ks, shape):
     assert rel(gb[:cout], gz.sum(dim=(0, 2, 3))) < 1e-3
 
 
+@pytest.fixture
+def samples_per_block(cae, npb):
+    """cae_t_set_samples_per_block(npb) for one test ('': automatic), back to automatic afterwards"""
+    from cnn_autoencoder_amd import _lib
+    L = _lib.lib()
+    _lib.check(L.cae_t_set_samples_per_block(int(npb or 0)))
+    try:
+        yield
+    finally:
+        _lib.check(L.cae_t_set_samples_per_block(0))
+
+
 @pytest.mark.parametrize('npb', ['', '3'])
-def test_conv_kernels_walk_several_samples_per_block(cae, npb, monkeypatch):
+def test_conv_kernels_walk_several_samples_per_block(cae, npb, samples_per_block):
     """gg8_kernel / wgrad8_kernel on the canonical 128 -> 128 layer with blocks that walk several samples (the shapes of the
     other tests give every block one sample): 8 samples of 72 x 120, forward, both data-gradient forms and the weight gradient;
-    CAE_GG8_NPB=3 forces ragged sample groups (3, 3, 2) in the gather-GEMM, the weight gradient walks 2 samples per block."""
+    3 samples per block forces ragged sample groups (3, 3, 2) in the gather-GEMM, the weight gradient walks 2 samples per block."""
     from cnn_autoencoder_amd import _lib, train
     L = _lib.lib()
-    if npb:
-        monkeypatch.setenv('CAE_GG8_NPB', npb)
     torch.manual_seed(7)
     n, c, h, w, ks = 8, 128, 72, 120, 3
     x = bf(torch.randn(n, c, h, w)).requires_grad_(True)
