@@ -125,6 +125,10 @@ SYMBOLS = {
     'cae_rans_encode_batch': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int]),
     'cae_rans_encode_packed': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int]),
     'cae_rans_decode_batch': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int]),
+    'cae_rans_encode_workspace': (c_int, [c_void_p, c_int, c_int, ctypes.POINTER(c_size_t)]),
+    'cae_rans_encode_device': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p,
+                                       c_size_t, c_void_p]),
+    'cae_rans_decode_device': (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     'cae_door_create': (c_int, [c_void_p, c_void_p, c_int, c_int, ctypes.POINTER(c_void_p)]),
     'cae_door_destroy': (None, [c_void_p]),
     'cae_door_encode': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, ctypes.POINTER(c_void_p),

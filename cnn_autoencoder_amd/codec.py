@@ -22,7 +22,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from .entropy import EntropyBottleneck
+from .entropy import EntropyBottleneck, check_coder
 from .modules import Analyzer, Synthesizer
 
 try:  # numcodecs is an optional dependency of the *caller* (zarr); absent in the build image
@@ -168,25 +168,29 @@ class ConvolutionalAutoencoder(_CodecBase):
 
     # ---- batched side doors ------------------------------------------------------------------
     @torch.no_grad()
-    def encode_batch(self, tiles: np.ndarray) -> List[bytes]:
-        """tiles (n,h,w,c) uint8 -> n chunk byte strings."""
+    def encode_batch(self, tiles: np.ndarray, coder: str = 'host') -> List[bytes]:
+        """tiles (n,h,w,c) uint8 -> n chunk byte strings.  coder: 'host' range coder or 'device' (the same bytes)."""
+        check_coder(coder)
         tiles = np.ascontiguousarray(tiles)
         if tiles.ndim != 4 or tiles.dtype != np.uint8:
             raise ValueError(f'expected uint8 (n,h,w,c), got {tiles.dtype} {tiles.shape}')
         n, h, w, _ = tiles.shape
         dev = _lib.require_gpu()
         eb = _module(self._model['fact_ent'])
-        with self._lock:  # GPU section: H2D, analysis with the fused quantiser, D2H of the symbols
+        head = struct.pack('>QQ', h, w)
+        with self._lock:  # GPU section: H2D, analysis with the fused quantiser, D2H of the symbols (or the device coder)
             x = torch.from_numpy(tiles).to(dev)
             sym = _module(self._model['encoder']).forward_u8_symbols(x, eb)
+            if coder == 'device':
+                return [head + s for s in eb.encode_symbols_device(sym)]
             sym_host = sym.reshape(n, sym.size(1), -1).cpu().numpy()
         strings = eb.encode_symbols(sym_host)  # host range coder: outside the lock
-        head = struct.pack('>QQ', h, w)
         return [head + s for s in strings]
 
     @torch.no_grad()
-    def decode_batch(self, bufs: Sequence[bytes]) -> np.ndarray:
-        """chunk byte strings of equal tile size -> (n,h,w,c) uint8."""
+    def decode_batch(self, bufs: Sequence[bytes], coder: str = 'host') -> np.ndarray:
+        """chunk byte strings of equal tile size -> (n,h,w,c) uint8.  coder: 'host' or 'device' range decoder."""
+        check_coder(coder)
         dec = _module(self._model['decoder'])
         eb = _module(self._model['fact_ent'])
         level = len(dec.synthesis_track)
@@ -196,6 +200,11 @@ class ConvolutionalAutoencoder(_CodecBase):
         h, w = hw.pop()
         lh, lw = h // 2 ** level, w // 2 ** level
         dev = _lib.require_gpu()
+        if coder == 'device':
+            with self._lock:
+                sym = eb.decode_symbols_device([bytes(b[16:]) for b in bufs], lh * lw)
+                out = dec.forward_symbols_u8(sym.reshape(len(bufs), eb.channels, lh, lw), eb)
+                return out.cpu().numpy()
         sym_host = eb.decode_symbols([bytes(b[16:]) for b in bufs], lh * lw)  # host range decoder: outside the lock
         with self._lock:
             sym = torch.from_numpy(sym_host).to(dev).reshape(len(bufs), eb.channels, lh, lw)

@@ -372,6 +372,7 @@ Model::~Model() {
     if (medians_dev) (void)hipFree(medians_dev);
     if (density_dev) (void)hipFree(density_dev);
     if (bits_ws) (void)hipFree(bits_ws);
+    if (ent_dev.buf) (void)hipFree(ent_dev.buf);
 }
 
 // ---- kernel dispatch ---------------------------------------------------------------------------
@@ -817,6 +818,7 @@ int cae_model_set_entropy(cae_model_t *mm, int channels, int cdf_stride, const i
     m->ent.off.assign(offset, offset + channels);
     m->ent.medians.assign(medians, medians + channels);
     m->ent.build_tables();
+    ++m->ent_version;
     m->medians_dirty = true;
     return CAE_OK;
 }

@@ -74,10 +74,20 @@ int rans_decode_chunk(const EntropyTables &T, const uint8_t *buf, size_t len, in
 int rans_decode_chunk_pair(const EntropyTables &T, const uint8_t *const *bufs, const size_t *lens, int hw,
                            int32_t *const *symbols);
 
+// Device copy of EntropyTables for the device coder (cae_rans_device.hip): one buffer, byte offsets of its parts.
+struct DevEntropy {
+    void *buf = nullptr;
+    uint64_t version = 0;  // Model::ent_version it was uploaded from
+    size_t enc = 0, cdf = 0, lut = 0, len = 0, off = 0;
+};
+
 struct Model {
     int c_org = 0, c_net = 0, c_bn = 0, L = 0, ks = 3;
     std::vector<Layer> enc, dec;
     EntropyTables ent;
+    uint64_t ent_version = 0;  // bumped by every cae_model_set_entropy
+    DevEntropy ent_dev;
+    int ensure_ent_device();   // (under `mu`)
     float *medians_dev = nullptr;
     bool medians_dirty = false;
     // factorized density network (cae_model_set_density): effective parameters, uniform width

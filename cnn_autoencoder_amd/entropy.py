@@ -53,9 +53,10 @@ class PackedStreams:
     byte strings that is handed from the encoder to the decoder / file writer without per-stream copies.
     ``len(p)``, ``p.nbytes(i)``, ``p[i]`` (a ``bytes`` copy), iteration, ``==`` with a list of bytes."""
 
-    def __init__(self, ptr: int, offsets):
+    def __init__(self, ptr: int, offsets, owner=None):
         self._ptr = ptr
         self.offsets = [int(o) for o in offsets]
+        self._owner = owner  # host array holding the bytes (device coder); None: library-allocated, released by cae_free
 
     def __len__(self):
         return len(self.offsets) - 1
@@ -83,12 +84,92 @@ class PackedStreams:
             return NotImplemented
 
     def __del__(self):
+        if getattr(self, '_owner', None) is not None:
+            self._owner = self._ptr = None
+            return
         if getattr(self, '_ptr', None):
             try:
                 _lib.lib().cae_free(self._ptr)
             except Exception:
                 pass
             self._ptr = None
+
+
+# Where the range coder runs: 'host' (default: the C++ coder on a pool of CPU threads) or 'device' (the HIP coder,
+# cae_rans_*_device).  Both write the same bytes.
+CODERS = ('host', 'device')
+
+
+def check_coder(coder: str) -> str:
+    if coder not in CODERS:
+        raise ValueError(f'coder must be one of {CODERS}, got {coder!r}')
+    return coder
+
+
+@torch.no_grad()
+def rans_encode_device(handle: _lib.Handle, sym: torch.Tensor):
+    """(B,C,...) int32 symbols in HBM -> (packed, offsets): the B rANS streams of `handle`'s tables packed into one uint8
+    tensor in HBM, stream i = packed[offsets[i]:offsets[i+1]] (offsets: host list of B+1).  Kernels on the current
+    stream, then one wait for it to read back the offsets and per-stream statuses.  The word workspace starts at one
+    word per symbol and doubles while escape-heavy streams need more."""
+    dev = _lib.require_gpu()
+    L = _lib.lib()
+    n = sym.size(0)
+    hw = sym[0, 0].numel() if sym.dim() > 2 else 1
+    sym = sym.to(device=dev, dtype=torch.int32).contiguous()
+    need = ctypes.c_size_t()
+    _lib.check(L.cae_rans_encode_workspace(handle.ptr, n, hw, ctypes.byref(need)))
+    ws_bytes = need.value
+    for _ in range(6):  # one word per symbol x 2^5 covers the 9 steps an escaped symbol can take
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        out = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)  # >= the word region: never the limit
+        meta = torch.empty(2 * n + 2, dtype=torch.int64, device=dev)  # offsets [n+1] | status int32 [n]
+        _lib.check(L.cae_rans_encode_device(handle.ptr, sym.data_ptr(), n, hw, out.data_ptr(), out.numel(), meta.data_ptr(),
+                                            meta.data_ptr() + 8 * (n + 1), ws.data_ptr(), ws_bytes, _lib.stream_ptr()))
+        m = meta.cpu().numpy()
+        status = m[n + 1:].view(np.int32)[:n]
+        if (status == -1).any():
+            raise ValueError(f'a symbol of stream {int(np.flatnonzero(status == -1)[0])} is outside the codable range')
+        if (status == -3).any():
+            ws_bytes *= 2
+            continue
+        return out, [int(v) for v in m[:n + 1]]
+    raise _lib.CaeError('libcae_hip error -3: device coder workspace still too small')
+
+
+@torch.no_grad()
+def rans_decode_device(handle: _lib.Handle, channels: int, strings, hw: int) -> torch.Tensor:
+    """rANS byte strings (a list, or PackedStreams) -> (B,C,hw) int32 symbols in HBM: the packed bytes go H2D, the
+    kernel runs on the current stream, then one wait for it to read back the per-stream statuses."""
+    dev = _lib.require_gpu()
+    n = len(strings)
+    if n < 1:
+        raise ValueError('no streams to decode')
+    if isinstance(strings, PackedStreams):  # one contiguous buffer already
+        base = strings.offsets[0]
+        offsets = [o - base for o in strings.offsets]
+        total = offsets[-1]
+        host = np.ctypeslib.as_array((ctypes.c_uint8 * total).from_address(strings.pointer(0))) if total else None
+    else:
+        keep = [bytes(s) for s in strings]
+        offsets = [0]
+        for s in keep:
+            offsets.append(offsets[-1] + len(s))
+        total = offsets[-1]
+        host = np.frombuffer(bytearray(b''.join(keep)), dtype=np.uint8) if total else None
+    buf = torch.empty(max(total, 16), dtype=torch.uint8, device=dev)
+    if total:
+        buf[:total].copy_(torch.from_numpy(host))
+    offs = torch.tensor(offsets, dtype=torch.int64).to(dev)
+    sym = torch.empty((n, channels, hw), dtype=torch.int32, device=dev)
+    status = torch.empty(n, dtype=torch.int32, device=dev)
+    _lib.check(_lib.lib().cae_rans_decode_device(handle.ptr, buf.data_ptr(), total, offs.data_ptr(), n, hw, sym.data_ptr(),
+                                                 status.data_ptr(), _lib.stream_ptr()))
+    st = status.cpu().numpy()
+    if (st != 0).any():
+        raise _lib.CaeError(f'libcae_hip error -5: bitstream of stream {int(np.flatnonzero(st != 0)[0])} is damaged or '
+                            'shorter than its symbols (device decoder)')
+    return sym
 
 
 def pmf_to_quantized_cdf(pmf: torch.Tensor, precision: int = 16) -> torch.Tensor:
@@ -519,17 +600,39 @@ class EntropyBottleneck(nn.Module):
         return sym
 
     @torch.no_grad()
-    def compress(self, x: torch.Tensor) -> List[bytes]:
+    def encode_symbols_device(self, sym: torch.Tensor) -> PackedStreams:
+        """(B,C,...) int32 symbols in HBM -> the same streams as encode_symbols, coded on the device (current stream);
+        only the compressed bytes cross PCIe."""
+        h = self._sync_handle()
+        if sym.dim() < 2 or sym.size(1) != self.channels:
+            raise ValueError(f'Invalid symbol shape {tuple(sym.shape)} for {self.channels} channels')
+        packed, offsets = rans_encode_device(h, sym)
+        host = packed[:offsets[-1]].cpu().numpy()
+        return PackedStreams(host.ctypes.data, offsets, owner=host)
+
+    @torch.no_grad()
+    def decode_symbols_device(self, strings: Sequence[bytes], hw: int) -> torch.Tensor:
+        """rANS byte strings -> (B,C,hw) int32 symbols in HBM, decoded on the device (current stream)."""
+        return rans_decode_device(self._sync_handle(), self.channels, strings, hw)
+
+    @torch.no_grad()
+    def compress(self, x: torch.Tensor, coder: str = 'host') -> List[bytes]:
+        if check_coder(coder) == 'device':
+            return list(self.encode_symbols_device(self.quantize_symbols(x)))
         sym = self.quantize_symbols(x)
         return self.encode_symbols(sym.reshape(sym.size(0), sym.size(1), -1).cpu().numpy())
 
     @torch.no_grad()
-    def decompress(self, strings: Sequence[bytes], size) -> torch.Tensor:
+    def decompress(self, strings: Sequence[bytes], size, coder: str = 'host') -> torch.Tensor:
+        check_coder(coder)
         dev = _lib.require_gpu()
         h = self._sync_handle()
         size = tuple(int(s) for s in size)
         hw = int(np.prod(size))
-        sym = torch.from_numpy(self.decode_symbols(strings, hw)).to(dev)
+        if coder == 'device':
+            sym = self.decode_symbols_device(strings, hw)
+        else:
+            sym = torch.from_numpy(self.decode_symbols(strings, hw)).to(dev)
         out = torch.empty((len(strings), self.channels) + size, dtype=torch.float32, device=dev)
         _lib.check(_lib.lib().cae_dequantize(h.ptr, sym.data_ptr(), len(strings), hw, out.data_ptr(),
                                              _lib.stream_ptr()))

@@ -87,9 +87,14 @@ class SlideCoder:
     k+1 and the synthesis of batch k-1.  Symbols cross PCIe through pinned buffers on a side stream.
     """
 
-    def __init__(self, codec, coder_threads: int = 0):
+    def __init__(self, codec, coder_threads: int = 0, coder: str = 'host'):
         from .codec import _module
+        from .entropy import check_coder
         self.codec = codec
+        # 'device': the range coder runs as HIP kernels on streams of their own (one per batch in flight); symbols never
+        # leave HBM, only the compressed bytes cross PCIe.  Same bytes, statistics and range guard as 'host'.
+        self.coder = check_coder(coder)
+        self._coder_streams = None
         self.enc = _module(codec._model['encoder'])
         self.dec = _module(codec._model['decoder'])
         self.eb = _module(codec._model['fact_ent'])
@@ -133,6 +138,8 @@ class SlideCoder:
         """tiles_dev (n,h,w,c) uint8 in HBM -> rANS payloads (without the 16-byte chunk header)."""
         y = self.enc.forward_u8(tiles_dev)
         sym = self.eb.quantize_symbols(y)
+        if self.coder == 'device':
+            return list(self.eb.encode_symbols_device(sym))
         sym_host = sym.reshape(sym.size(0), sym.size(1), -1).cpu().numpy()
         return self.eb.encode_symbols(sym_host, self.coder_threads)
 
@@ -140,8 +147,24 @@ class SlideCoder:
     def decompress(self, payloads: Sequence[bytes], h: int, w: int) -> torch.Tensor:
         """payloads -> (n,h,w,c) uint8 in HBM."""
         size = (h // 2 ** self.level, w // 2 ** self.level)
-        y_q = self.eb.decompress(payloads, size)
+        y_q = self.eb.decompress(payloads, size, coder=self.coder)
         return self.dec.forward_u8(y_q)
+
+    # ---- device coder: kernels on a stream per batch in flight, called from worker threads ----------------------
+    def _coder_stream(self, k):
+        if self._coder_streams is None:
+            self._coder_streams = [torch.cuda.Stream(_dev()) for _ in range(max(1, self.depth))]
+        return self._coder_streams[k % len(self._coder_streams)]
+
+    def _device_encode(self, k, sym):
+        """symbols of batch k (complete: the caller has waited for them) -> PackedStreams on the host"""
+        with torch.cuda.device(sym.device), torch.cuda.stream(self._coder_stream(k)):
+            return self.eb.encode_symbols_device(sym)
+
+    def _device_decode(self, k, payloads, hw):
+        """payloads -> (n, C, hw) int32 symbols in HBM, complete when this returns (allocated on the coder stream)"""
+        with torch.cuda.device(_dev()), torch.cuda.stream(self._coder_stream(k)):
+            return self.eb.decode_symbols_device(payloads, hw)
 
     @torch.no_grad()
     def tile_sse(self, rec: torch.Tensor, tiles: torch.Tensor) -> torch.Tensor:
@@ -230,7 +253,7 @@ class SlideCoder:
             sym, guard = self.enc.forward_u8_symbols(t, self.eb, defer=True)
             n, C = sym.size(0), sym.size(1)
             hw = sym.numel() // (n * C)
-            pin = self._pin(('a', k % (depth + 1)), (n, C, hw), torch.int32)
+            pin = None if self.coder == 'device' else self._pin(('a', k % (depth + 1)), (n, C, hw), torch.int32)
             ready = torch.cuda.Event(blocking=True)
             ready.record(main)
             return pin, ready, sym, guard, t
@@ -245,10 +268,20 @@ class SlideCoder:
         def encode(pulled):
             return self.eb.encode_symbols(pulled.result().numpy(), self.encode_threads)
 
-        with ThreadPoolExecutor(max_workers=1) as d2h_pool, ThreadPoolExecutor(max_workers=1) as pool:
+        def device_encode(k, pin, ready, sym, guard, t):  # one worker per batch in flight, each on a coder stream
+            ready.synchronize()
+            if guard.overflowed():
+                sym = self._redo_analysis(t, main)
+            return self._device_encode(k, sym)
+
+        device = self.coder == 'device'
+        with ThreadPoolExecutor(max_workers=1) as d2h_pool, ThreadPoolExecutor(max_workers=depth if device else 1) as pool:
             inflight = []
             for k, batch in enumerate(batches):
-                inflight.append(pool.submit(encode, d2h_pool.submit(pull, *stage(k, batch))))
+                if device:
+                    inflight.append(pool.submit(device_encode, k, *stage(k, batch)))
+                else:
+                    inflight.append(pool.submit(encode, d2h_pool.submit(pull, *stage(k, batch))))
                 if len(inflight) > depth:
                     yield inflight.pop(0).result()
             while inflight:
@@ -269,7 +302,11 @@ class SlideCoder:
         lh, lw = h // 2 ** self.level, w // 2 ** self.level
         C = self.eb.channels
 
+        device = self.coder == 'device'
+
         def decode(k, payloads):
+            if device:  # symbols straight into HBM; complete when this returns
+                return None, self._device_decode(k, payloads, lh * lw)
             key = ('d', k % (depth + 2))
             back = self._pin(key, (len(payloads), C, lh * lw), torch.int32)
             self._wait_free(key)  # the H2D that last read this buffer
@@ -278,12 +315,15 @@ class SlideCoder:
 
         def synth(item):
             key, back = item
-            with torch.cuda.stream(up):
-                sym = back.to(_dev(), non_blocking=True)
-                ev = torch.cuda.Event(blocking=True)
-                ev.record(up)
-            self._busy[key] = ev
-            main.wait_event(ev)
+            if device:
+                sym = back
+            else:
+                with torch.cuda.stream(up):
+                    sym = back.to(_dev(), non_blocking=True)
+                    ev = torch.cuda.Event(blocking=True)
+                    ev.record(up)
+                self._busy[key] = ev
+                main.wait_event(ev)
             sym.record_stream(main)
             rec, guard = self.dec.forward_symbols_u8(sym.reshape(sym.size(0), C, lh, lw), self.eb, defer=True)
             done = torch.cuda.Event(blocking=True)
@@ -304,7 +344,7 @@ class SlideCoder:
             _lib.check(_lib.lib().cae_copy_to_host(out.data_ptr(), rec.data_ptr(), rec.numel()))
             return out.numpy()
 
-        with ThreadPoolExecutor(max_workers=1) as pool, ThreadPoolExecutor(max_workers=1) as out_pool:
+        with ThreadPoolExecutor(max_workers=depth if device else 1) as pool, ThreadPoolExecutor(max_workers=1) as out_pool:
             inflight, outgoing, held, j = [], [], [], 0
 
             def emit(item, payloads):
@@ -360,11 +400,12 @@ class SlideCoder:
         tm = dict(host_encode=0.0, host_decode=0.0, wait_host=0.0, d2h_copy=0.0)
         all_payloads, stats_parts = [], []
         # all pinned symbol buffers up front (hipHostMalloc of 100 MB costs ~10 ms: not inside the pipeline)
+        device = self.coder == 'device'
         n0, h0, w0, _ = batches[0].shape
         lh0, lw0 = self.enc.latent_size(h0, w0)
-        for j in range(DEPTH + 2):
+        for j in range(0 if device else DEPTH + 2):
             self._pin(('a', j), (n0, self.eb.channels, lh0 * lw0), torch.int32)
-        for j in range(DEPTH + 2):
+        for j in range(0 if device else DEPTH + 2):
             self._pin(('d', j), (n0, self.eb.channels, lh0 * lw0), torch.int32)
 
         def stage_a(k):
@@ -373,7 +414,8 @@ class SlideCoder:
             sym, guard = self.enc.forward_u8_symbols(t, self.eb, defer=True)
             n, C = sym.size(0), sym.size(1)
             hw = sym.numel() // (n * C)
-            pin = self._pin(('a', k % (DEPTH + 2)), (n, C, hw), torch.int32)  # in use until encode(k) is done
+            # (host coder: in use until encode(k) is done)
+            pin = None if device else self._pin(('a', k % (DEPTH + 2)), (n, C, hw), torch.int32)
             ready = torch.cuda.Event(blocking=True)
             ready.record(main)
             return k, pin, ready, hw, sym, guard
@@ -405,14 +447,33 @@ class SlideCoder:
             self.eb.decode_symbols(payloads, hw, self.decode_threads, out=back.numpy())
             return payloads, back, te, time.perf_counter() - t1
 
+        # device coder: the same three stages with the symbols kept in HBM -- encode on batch k's coder stream, the bytes
+        # D2H, back H2D and decode on that stream; one worker per batch in flight in each stage
+        def device_encode(k, pin, ready, hw, sym, guard):
+            ready.synchronize()
+            if guard.overflowed():
+                sym = self._redo_analysis(batches[k], main)
+            t0 = time.perf_counter()
+            payloads = self._device_encode(k, sym)
+            return k, payloads, hw, tuple(sym.shape), time.perf_counter() - t0
+
+        def device_decode(enc_future):
+            k, payloads, hw, shape, te = enc_future.result()
+            t1 = time.perf_counter()
+            sym = self._device_decode(k, payloads, hw)
+            return payloads, sym, te, time.perf_counter() - t1
+
         def stage_d(k, payloads, back):
             t = batches[k]
             n, h, w, c = t.shape
-            with torch.cuda.stream(copy_up):  # H2D beside the kernels of the main stream
-                sym = back.to(dev, non_blocking=True)
-                up = torch.cuda.Event(blocking=True)
-                up.record(copy_up)
-            main.wait_event(up)
+            if device:
+                sym = back  # decoded into HBM, complete
+            else:
+                with torch.cuda.stream(copy_up):  # H2D beside the kernels of the main stream
+                    sym = back.to(dev, non_blocking=True)
+                    up = torch.cuda.Event(blocking=True)
+                    up.record(copy_up)
+                main.wait_event(up)
             sym.record_stream(main)
             lh, lw = h // 2 ** self.level, w // 2 ** self.level
             # dequantiser fused into the layout conversion in front of the first synthesis layer
@@ -450,12 +511,16 @@ class SlideCoder:
             stats_parts.append(tile_stats(nbytes, sse_host, samples))
 
         # three host workers: batch k+2 is pulled while batch k+1 is range-encoded and batch k is decoded
-        with ThreadPoolExecutor(max_workers=1) as pull_pool, ThreadPoolExecutor(max_workers=1) as enc_pool, \
-                ThreadPoolExecutor(max_workers=1) as dec_pool:
+        workers = DEPTH if device else 1
+        with ThreadPoolExecutor(max_workers=1) as pull_pool, ThreadPoolExecutor(max_workers=workers) as enc_pool, \
+                ThreadPoolExecutor(max_workers=workers) as dec_pool:
             futs = {}
 
             def submit(k):
-                futs[k] = dec_pool.submit(host_decode, enc_pool.submit(host_encode, pull_pool.submit(host_pull, *stage_a(k))))
+                if device:
+                    futs[k] = dec_pool.submit(device_decode, enc_pool.submit(device_encode, *stage_a(k)))
+                else:
+                    futs[k] = dec_pool.submit(host_decode, enc_pool.submit(host_encode, pull_pool.submit(host_pull, *stage_a(k))))
 
             for k in range(min(DEPTH, K)):
                 submit(k)

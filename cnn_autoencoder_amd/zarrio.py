@@ -239,11 +239,14 @@ def _batches(items: Sequence, n: int) -> Iterable[Sequence]:
 
 def compress_image(codec: str, checkpoint, image: np.ndarray, output_filename: str, patch_size: int = 512,
                    data_group: str = '0/0', save_as_bottleneck: bool = False, gpu: bool = True,
-                   batch_tiles: int = 32) -> ZarrArray:
+                   batch_tiles: int = 32, coder: str = 'host') -> ZarrArray:
     """compress.py:29-128 for an in-memory (H, W, C) uint8 image: rechunk to (patch, patch, C) and write a
     zarr array whose chunks are ``codec`` bitstreams.  codec: 'CAE' | 'Zlib' | 'None' (the reference's
-    'Blosc' / 'Jpeg*' names are other libraries' codecs and raise ValueError here)."""
+    'Blosc' / 'Jpeg*' names are other libraries' codecs and raise ValueError here).  coder: where the range coder of
+    the CAE codecs runs, 'host' or 'device' (same chunk bytes)."""
     from . import slide
+    from .entropy import check_coder
+    check_coder(coder)
     from .codec import (ConvolutionalAutoencoder, ConvolutionalAutoencoderBottleneck, _module,
                         autoencoder_from_state_dict)
     image = np.asarray(image)
@@ -277,7 +280,7 @@ def compress_image(codec: str, checkpoint, image: np.ndarray, output_filename: s
             batch = np.stack([src.pad_chunk(image[src.chunk_slices(i)]) for i in group])
             with torch.no_grad():
                 y = enc.forward_u8(torch.from_numpy(batch).cuda())
-                strings = fe.compress(y)
+                strings = fe.compress(y, coder=coder)
             for idx, s in zip(group, strings):
                 import struct
                 z.write_chunk_bytes(idx, struct.pack('>QQ', y.shape[2], y.shape[3]) + s)
@@ -300,8 +303,8 @@ def compress_image(codec: str, checkpoint, image: np.ndarray, output_filename: s
         # pipelined: the GPU analyses the next batches while a host worker range-encodes and this thread writes files
         import struct
         groups = list(_batches(tiles[lo:hi], batch_tiles))
-        coder = slide.SlideCoder(compressor)
-        stream = coder.compress_batches(np.stack([z.pad_chunk(image[z.chunk_slices(i)]) for i in g]) for g in groups)
+        sc = slide.SlideCoder(compressor, coder=coder)
+        stream = sc.compress_batches(np.stack([z.pad_chunk(image[z.chunk_slices(i)]) for i in g]) for g in groups)
         head = struct.pack('>QQ', patch_size, patch_size)  # chunk = '>QQ'(h, w) + rANS payload (_autoencoders.py:553-555)
         for group, payloads in zip(groups, stream):
             for idx, payload in zip(group, payloads):
@@ -315,9 +318,12 @@ def compress_image(codec: str, checkpoint, image: np.ndarray, output_filename: s
 
 
 def decompress_image(input_filename: str, data_group: str = '0/0', checkpoint=None, gpu: bool = True,
-                     batch_tiles: int = 32) -> np.ndarray:
+                     batch_tiles: int = 32, coder: str = 'host') -> np.ndarray:
     """decompress.py:40-96: open the zarr (chunk decode = the stored codec), and when `checkpoint` is given the
-    array holds 'cae_bn' latents that the decoder turns back into pixels (decompress.py:61-79)."""
+    array holds 'cae_bn' latents that the decoder turns back into pixels (decompress.py:61-79).  coder: 'host' or
+    'device' range decoder of the 'cae' chunks."""
+    from .entropy import check_coder
+    check_coder(coder)
     from .codec import ConvolutionalAutoencoder, _module, autoencoder_from_state_dict
     z = ZarrArray.open(input_filename, data_group)
     if checkpoint is None or (isinstance(checkpoint, str) and not len(checkpoint)):
@@ -338,8 +344,8 @@ def decompress_image(input_filename: str, data_group: str = '0/0', checkpoint=No
                         raise ValueError('chunk header does not match the chunk shape')
                 return [b[16:] for b in bufs]
 
-            coder = slide.SlideCoder(z.codec)
-            stream = coder.decompress_batches((payloads(g) for g in groups), ph, pw, to_host=True)
+            sc = slide.SlideCoder(z.codec, coder=coder)
+            stream = sc.decompress_batches((payloads(g) for g in groups), ph, pw, to_host=True)
             for group, rec in zip(groups, stream):  # rec: pinned ring buffer, copied out right away
                 for idx, chunk in zip(group, rec):
                     sl = z.chunk_slices(idx)

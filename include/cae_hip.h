@@ -436,6 +436,29 @@ int cae_rans_encode_packed(cae_model_t *m, const int32_t *symbols_host, int n_st
 int cae_rans_decode_batch(cae_model_t *m, const uint8_t *const *bufs, const size_t *lens, int n_streams,
                           int hw, int32_t *symbols_host, int threads);
 
+/* ---- device entropy coding (opt-in) -----------------------------------------------------------
+ * The same streams, byte for byte, coded by HIP kernels (csrc/cae_rans_device.hip): one stream per lane, the
+ * handle's tables (cae_model_set_entropy) kept on the device and re-uploaded into a fresh buffer after every table
+ * change.  Launches are asynchronous on `stream`; the per-stream results are valid once that stream's work is done.
+ * Shapes: n_streams >= 1, hw >= 1, CDF rows of at most 4096 entries (else CAE_ERR_UNSUPPORTED).  Argument errors
+ * return CAE_ERR_ARG before anything touches the device.
+ *
+ * Encode: symbols_dev (n_streams, channels, hw) int32 -> the streams packed densely into out_dev (stream i =
+ * out_dev[offsets_dev[i] .. offsets_dev[i+1]), offsets_dev int64 [n_streams + 1]); status_dev int32 [n_streams] per
+ * stream: CAE_OK, CAE_ERR_ARG (a symbol outside the codable range, as the host coder), CAE_ERR_NOMEM (the workspace's
+ * word region or out_capacity was too small: repeat with more).  out_dev and workspace_dev 16-byte aligned.  The
+ * workspace holds a header plus one capacity region of (exact coder steps + 2) words per stream;
+ * cae_rans_encode_workspace gives the size for one word per symbol (enough unless escapes are frequent). */
+int cae_rans_encode_workspace(cae_model_t *m, int n_streams, int hw, size_t *bytes);
+int cae_rans_encode_device(cae_model_t *m, const int32_t *symbols_dev, int n_streams, int hw, uint8_t *out_dev,
+                           size_t out_capacity, int64_t *offsets_dev, int32_t *status_dev, void *workspace_dev,
+                           size_t workspace_bytes, void *stream);
+/* Decode: bytes_dev[0 .. bytes_len) holds stream i at [offsets_dev[i], offsets_dev[i+1]) -> symbols_dev
+ * (n_streams, channels, hw) int32; status_dev per stream: CAE_OK or CAE_ERR_CORRUPT (shorter than the 8-byte coder
+ * state, a read past the stream's end, a bypass count above 8, or offsets outside the buffer). */
+int cae_rans_decode_device(cae_model_t *m, const uint8_t *bytes_dev, size_t bytes_len, const int64_t *offsets_dev,
+                           int n_streams, int hw, int32_t *symbols_dev, int32_t *status_dev, void *stream);
+
 /* ---- codec front door -------------------------------------------------------------------
  * The reference's numcodecs plugin contract as C entry points: ConvolutionalAutoencoder.encode
  * (_autoencoders.py:539-555: (h,w,c) uint8 chunk -> '>QQ' header + rANS payload) and .decode (:557-584: chunk bytes ->
