@@ -188,10 +188,13 @@ class ConvolutionalAutoencoder(_CodecBase):
         return [head + s for s in strings]
 
     @torch.no_grad()
-    def decode_batch(self, bufs: Sequence[bytes], coder: str = 'host') -> np.ndarray:
-        """chunk byte strings of equal tile size -> (n,h,w,c) uint8.  coder: 'host' or 'device' range decoder."""
+    def decode_batch(self, bufs: Sequence[bytes], coder: str = 'host', scale: int = 0) -> np.ndarray:
+        """chunk byte strings of equal tile size -> (n,h,w,c) uint8.  coder: 'host' or 'device' range decoder.
+        ``scale = s``: the tiles at 1 / 2^s of the resolution, (n,h/2^s,w/2^s,c): the synthesis stops at that level
+        and its colour layer writes the image (needs multiscale_analysis=True; Synthesizer.forward_scale)."""
         check_coder(coder)
         dec = _module(self._model['decoder'])
+        scale = dec._check_scale(scale)
         eb = _module(self._model['fact_ent'])
         level = len(dec.synthesis_track)
         hw = {struct.unpack('>QQ', bytes(b[:16])) for b in bufs}
@@ -203,12 +206,12 @@ class ConvolutionalAutoencoder(_CodecBase):
         if coder == 'device':
             with self._lock:
                 sym = eb.decode_symbols_device([bytes(b[16:]) for b in bufs], lh * lw)
-                out = dec.forward_symbols_u8(sym.reshape(len(bufs), eb.channels, lh, lw), eb)
+                out = dec.forward_symbols_u8(sym.reshape(len(bufs), eb.channels, lh, lw), eb, scale=scale)
                 return out.cpu().numpy()
         sym_host = eb.decode_symbols([bytes(b[16:]) for b in bufs], lh * lw)  # host range decoder: outside the lock
         with self._lock:
             sym = torch.from_numpy(sym_host).to(dev).reshape(len(bufs), eb.channels, lh, lw)
-            out = dec.forward_symbols_u8(sym, eb)
+            out = dec.forward_symbols_u8(sym, eb, scale=scale)
             return out.cpu().numpy()
 
     # ---- numcodecs contract ----------------------------------------------------------------------

@@ -63,6 +63,19 @@ static std::vector<float> pack_weights(const float *w, bool transposed, int cin,
     return out;
 }
 
+// colour layer to <= 4 channels (color_small_kernel) -> [chunk][ky][kx][8 channels][4 outputs], zero padded
+static std::vector<float> pack_color4(const float *w, int cin, int cout, int ks) {
+    const int chunks = (cin + 7) / 8;
+    std::vector<float> out((size_t)chunks * ks * ks * 32, 0.0f);
+    for (int ci = 0; ci < cin; ++ci)
+        for (int ky = 0; ky < ks; ++ky)
+            for (int kx = 0; kx < ks; ++kx)
+                for (int co = 0; co < cout; ++co)
+                    out[((((size_t)(ci >> 3) * ks + ky) * ks + kx) * 8 + (ci & 7)) * 4 + co] =
+                        w[(((size_t)co * cin + ci) * ks + ky) * ks + kx];
+    return out;
+}
+
 // gamma -> [jt][co][q][lane][jj]: value G(c = 32co + (lane&31), j = 32jt + row(4q+jj) + 4(lane>>5))
 static std::vector<float> pack_gamma(const float *g, int C, int ct) {
     std::vector<float> out((size_t)ct * ct * 4 * 256, 0.0f);
@@ -358,6 +371,7 @@ Model::~Model() {
             if (l.color_wp) (void)hipFree(l.color_wp);
             if (l.color_bias) (void)hipFree(l.color_bias);
             if (l.color_wp16) (void)hipFree(l.color_wp16);
+            if (l.color_w4) (void)hipFree(l.color_w4);
             if (l.wp16) (void)hipFree(l.wp16);
             if (l.gp16) (void)hipFree(l.gp16);
             if (l.wp_edge16) (void)hipFree(l.wp_edge16);
@@ -755,6 +769,11 @@ int cae_model_set_color_layer(cae_model_t *mm, int index, int cin, int cout, con
         l.color_bias = nullptr;
     }
     l.color_cout = cout;
+    if (l.color_w4) {
+        (void)hipFree(l.color_w4);
+        l.color_w4 = nullptr;
+    }
+    if (cin <= 128 && cout <= 4 && (rc = upload(pack_color4(w, cin, cout, m->ks), &l.color_w4))) return rc;
     if (l.color_wp16) {
         (void)hipFree(l.color_wp16);
         l.color_wp16 = nullptr;
@@ -1014,7 +1033,7 @@ static int analysis_impl(cae_model_t *mm, const void *tiles, int fmt, int n, int
 }
 
 static int synthesis_impl(cae_model_t *mm, const float *latents, const int32_t *symbols, int n, int lh, int lw, void *out,
-                          int fmt, float *const *bridges, float *const *colors, void *stream);
+                          int fmt, float *const *bridges, float *const *colors, void *stream, int scale = 0);
 
 int cae_synthesis(cae_model_t *mm, const float *latents, int n, int lh, int lw, void *out, int fmt,
                   float *const *bridges, void *stream) {
@@ -1034,10 +1053,35 @@ int cae_synthesis_symbols(cae_model_t *mm, const int32_t *symbols, int n, int lh
     return synthesis_impl(mm, nullptr, symbols, n, lh, lw, out, fmt, nullptr, nullptr, stream);
 }
 
+// Synthesis that stops at a level: units 0 .. L-1-scale, then colour layer L-1-scale into `out` (the image at 1 / 2^scale
+// of the resolution).  scale == 0 is cae_synthesis / cae_synthesis_symbols.
+static int check_scale(cae_model_t *mm, int scale) {
+    Model *m = reinterpret_cast<Model *>(mm);
+    if (!m) return fail(CAE_ERR_ARG, "NULL argument");
+    if (scale < 0 || scale >= m->L) return fail(CAE_ERR_ARG, "scale %d outside 0..%d", scale, m->L - 1);
+    return CAE_OK;
+}
+
+int cae_synthesis_scale(cae_model_t *mm, const float *latents, int n, int lh, int lw, int scale, void *out, int fmt,
+                        void *stream) {
+    if (!latents) return fail(CAE_ERR_ARG, "NULL argument");
+    CAE_TRY(check_scale(mm, scale));
+    return synthesis_impl(mm, latents, nullptr, n, lh, lw, out, fmt, nullptr, nullptr, stream, scale);
+}
+
+int cae_synthesis_symbols_scale(cae_model_t *mm, const int32_t *symbols, int n, int lh, int lw, int scale, void *out,
+                                int fmt, void *stream) {
+    if (!symbols) return fail(CAE_ERR_ARG, "NULL argument");
+    CAE_TRY(check_scale(mm, scale));
+    return synthesis_impl(mm, nullptr, symbols, n, lh, lw, out, fmt, nullptr, nullptr, stream, scale);
+}
+
 static int synthesis_impl(cae_model_t *mm, const float *latents, const int32_t *symbols, int n, int lh, int lw, void *out,
-                          int fmt, float *const *bridges, float *const *colors, void *stream) {
+                          int fmt, float *const *bridges, float *const *colors, void *stream, int scale) {
     Model *m = reinterpret_cast<Model *>(mm);
     if (!m || !out) return fail(CAE_ERR_ARG, "NULL argument");
+    // scale > 0 (cae_synthesis_scale): the track stops after unit `stop`, whose colour layer writes `out`
+    const int stop = m->L - 1 - scale, nrun = stop + 1;
     if (symbols && m->ent.channels == 0) return fail(CAE_ERR_ARG, "entropy model not set");
     if (n < 1 || lh < 1 || lw < 1) return fail(CAE_ERR_ARG, "bad latent batch %dx%dx%d", n, lh, lw);
     if (fmt != CAE_FMT_U8_HWC && fmt != CAE_FMT_F32_NCHW) return fail(CAE_ERR_ARG, "bad pixel format %d", fmt);
@@ -1048,11 +1092,20 @@ static int synthesis_impl(cae_model_t *mm, const float *latents, const int32_t *
         if (colors[i] && ((lh << (i + 1)) <= m->ks / 2 || (lw << (i + 1)) <= m->ks / 2))
             return fail(CAE_ERR_ARG, "colour layer %d input %d x %d too small for reflect padding %d", i, lh << (i + 1),
                         lw << (i + 1), m->ks / 2);
+    if (scale > 0) {
+        const Layer &l = m->dec[stop];
+        if (!l.color_wp) return fail(CAE_ERR_ARG, "colour layer %d not set", stop);
+        if ((lh << nrun) <= m->ks / 2 || (lw << nrun) <= m->ks / 2)
+            return fail(CAE_ERR_ARG, "colour layer %d input %d x %d too small for reflect padding %d", stop, lh << nrun,
+                        lw << nrun, m->ks / 2);
+    }
     hipStream_t st = (hipStream_t)stream;
     std::lock_guard<std::mutex> lk(m->mu);
     int rc;
     if ((rc = m->ensure_device()) || (rc = m->order_stream(stream))) return rc;
     const bool f16 = m->f16_usable();
+    if (scale > 0 && f16 && !m->dec[stop].color_w4 && !m->dec[stop].color_wp16)
+        return fail(CAE_ERR_UNSUPPORTED, "f16x3: colour layers to more than 32 channels run on the fp32 path: set precision 0");
     int64_t ticket = 0;
     g_last_ticket = 0;
     int *flag = f16 ? m->next_flag(&ticket) : m->flags_dev;
@@ -1067,7 +1120,7 @@ static int synthesis_impl(cae_model_t *mm, const float *latents, const int32_t *
     size_t maxact = 0;
     {
         int ch = lh, cw = lw;
-        for (int i = 0; i < m->L; ++i) {
+        for (int i = 0; i < nrun; ++i) {  // (the levels that run)
             if (!m->dec[i].stages.empty())
                 maxact = std::max(maxact, (size_t)n * round_ct(m->dec[i].cin) * 4 * ch * row_bytes(cw));
             ch *= 2;
@@ -1076,7 +1129,12 @@ static int synthesis_impl(cae_model_t *mm, const float *latents, const int32_t *
         }
     }
     bool need_third_slot = false;
-    for (auto &l : m->dec) need_third_slot |= l.stages.size() > 1 || (f16 && stages_need_fp32(l));
+    for (int i = 0; i < nrun; ++i)
+        need_third_slot |= m->dec[i].stages.size() > 1 || (f16 && stages_need_fp32(m->dec[i]));
+    if (scale > 0 && !m->dec[stop].color_w4 && fmt == CAE_FMT_U8_HWC) {
+        // generic colour launch: fp32 NCHW into a spare slot, then the uint8 conversion
+        maxact = std::max(maxact, (size_t)n * m->dec[stop].color_cout * (lh << nrun) * (lw << nrun) * sizeof(float));
+    }
     if ((rc = m->ensure_ws(0, in_bytes))) return rc;
     if (maxact && ((rc = m->ensure_ws(1, maxact)) || (rc = m->ensure_ws(2, maxact)))) return rc;
     if (maxact && need_third_slot && (rc = m->ensure_ws(3, maxact))) return rc;
@@ -1097,7 +1155,7 @@ static int synthesis_impl(cae_model_t *mm, const float *latents, const int32_t *
     // with the last layer's weights, the last layer is a gather.  Needs the f16x3 transposed-convolution kernel for
     // layer L-2, k = 3, at most 3 image channels, and nobody asking for layer L-2's own output (bridges / colours).
     bool use_pmap = false;
-    if (f16 && m->L >= 2 && m->ks == 3 && getenv("CAE_NO_PMAP") == nullptr) {
+    if (f16 && scale == 0 && m->L >= 2 && m->ks == 3 && getenv("CAE_NO_PMAP") == nullptr) {
         const Layer &lp = m->dec[m->L - 2], &ll = m->dec[m->L - 1];
         // (conv_f16-style LDS budget: two 33-KiB stages + the transpose buffers fit for k = 3 and up to 128 channels)
         use_pmap = ll.wp_pmap16 && !ll.gdn && ll.stages.empty() && lp.stages.empty() && lp.ct <= 4 && lp.cout == ll.cin &&
@@ -1109,7 +1167,7 @@ static int synthesis_impl(cae_model_t *mm, const float *latents, const int32_t *
     const float *cur = (const float *)m->ws[0];
     int cur_planes = p0, ch = lh, cw = lw;
     int cur_idx = 0;
-    for (int i = 0; i < m->L; ++i) {
+    for (int i = 0; i < nrun; ++i) {
         const Layer &l = m->dec[i];
         const bool last = i == m->L - 1;
         if (use_pmap && last) {  // the gather half of the product map
@@ -1228,6 +1286,50 @@ static int synthesis_impl(cae_model_t *mm, const float *latents, const int32_t *
         ch = a.OH;
         cw = a.OW;
         cur_idx = out_idx;
+    }
+    if (scale > 0) {  // colour layer of level `stop` on its activations `cur` (ch x cw), into `out`
+        const Layer &l = m->dec[stop];
+        const int ofmt = fmt == CAE_FMT_U8_HWC ? OUT_U8HWC : OUT_NCHW;
+        prof.begin();
+        if (l.color_w4) {
+            if ((rc = launch_color_small(m->ks, f16, cur, cur_planes, l.cout, l.color_w4, l.color_bias, n, ch, cw,
+                                         l.color_cout, out, ofmt, flag, st)))
+                return rc;
+        } else {
+            // more than 128 input or 4 image channels: the generic stride-1 launch (fp32 NCHW), + the uint8 conversion
+            float *img = ofmt == OUT_NCHW ? (float *)out : (float *)m->ws[pick_slot(cur_idx, cur_idx)];
+            LayerArgs c{};
+            c.in = cur;
+            c.out = img;
+            c.wp = l.color_wp;
+            c.bias = l.color_bias;
+            c.zero = m->zero;
+            c.medians = m->zero;
+            c.N = n;
+            c.H = ch;
+            c.W = cw;
+            c.OH = ch;
+            c.OW = cw;
+            c.in_planes = cur_planes;
+            c.cci = (l.cout + 7) / 8;
+            c.out_planes = round_ct(l.color_cout) * 4;
+            c.cout = l.color_cout;
+            c.tiles_x = (cw + 15) / 16;
+            c.tiles_y = (ch + 2 * CONV_NW - 1) / (2 * CONV_NW);
+            c.outfmt = OUT_NCHW;
+            c.act = 0;
+            if (f16) {
+                c.wp = (const float *)l.color_wp16;
+                c.cci = (l.cout + 15) / 16;
+                c.tiles_y = (ch + 15) / 16;
+                c.flag = flag;
+                if ((rc = launch_color_f16(m->ks, c, st))) return rc;
+            } else if ((rc = launch_conv_s1(m->ks, round_ct(l.color_cout), false, false, c, st))) {
+                return rc;
+            }
+            if (ofmt == OUT_U8HWC && (rc = launch_nchw_to_u8hwc(img, out, n, l.color_cout, (size_t)ch * cw, st))) return rc;
+        }
+        prof.end();
     }
     return CAE_OK;
 }

@@ -37,6 +37,7 @@ struct Layer {
     float *color_wp = nullptr;
     float *color_bias = nullptr;
     void *color_wp16 = nullptr;  // f16x3 path: packed hi/lo weights of the colour layer
+    float *color_w4 = nullptr;   // colour layer from <= 128 to <= 4 channels: weights of color_small_kernel (both paths)
     int color_cout = 0;
     int act = 0;               // activation after the pre-convolution and after this layer (0 none, 1 LeakyReLU, 2 ReLU)
     void *wp16 = nullptr;      // f16x3 path: packed hi/lo weights

@@ -76,6 +76,11 @@ int launch_conv_f16(int ks, int ct, bool gdn, const LayerArgs &a, hipStream_t st
 int launch_deconv_f16(int ks, int ct, bool gdn, const LayerArgs &a, hipStream_t st);
 int launch_conv_s1_f16(int ks, int ct, bool synthesis, bool gdn, const LayerArgs &a, hipStream_t st);
 int launch_color_f16(int ks, const LayerArgs &a, hipStream_t st);
+// colour layer from <= 128 channels (C8 rows, or C8SP rows when `split`) to <= 4 image channels, fp32 NCHW / uint8 HWC out
+int launch_color_small(int ks, bool split, const void *in, int in_planes, int cin, const float *w, const float *bias,
+                       int n, int h, int w_px, int cout, void *out, int outfmt, int *flag, hipStream_t st);
+// fp32 NCHW -> uint8 HWC with the x255 / clip / truncate epilogue
+int launch_nchw_to_u8hwc(const float *in, void *out, int n, int c, size_t hw, hipStream_t st);
 int launch_first_f16(int ks, int ct, bool gdn, const LayerArgs &a, const FirstArgs &f, hipStream_t st);
 int launch_last_f16(int ks, const LayerArgs &a, hipStream_t st);
 // GDN / IGDN in place on the split rows a.out (layers wider than 128 channels; a.outfmt must be OUT_C8)

@@ -741,10 +741,54 @@ class Synthesizer(_Track):
         out, _, _ = self._run(x, _lib.FMT_U8_HWC, False)
         return out
 
-    def forward_symbols_u8(self, sym: torch.Tensor, eb, defer: bool = False):
+    def _check_scale(self, scale) -> int:
+        """``scale = s``: the image at 1 / 2^s of the resolution, 0 .. compression_level - 1; s > 0 needs the colour
+        layers (multiscale_analysis=True).  Checked here, before anything is launched."""
+        L = self._dims[3]
+        if isinstance(scale, bool) or int(scale) != scale:
+            raise ValueError(f'scale must be an integer, got {scale!r}')
+        scale = int(scale)
+        if not 0 <= scale < L:
+            raise ValueError(f'scale {scale} outside 0..{L - 1}')
+        if scale > 0 and not self.multiscale_analysis:
+            raise ValueError('scale > 0 needs a model built with multiscale_analysis=True (colour layers)')
+        return scale
+
+    def _run_scale(self, x: torch.Tensor, scale: int, fmt: int):
+        scale = self._check_scale(scale)
+        dev = _lib.require_gpu()
+        if x.dim() != 4 or x.size(1) != self._dims[2]:
+            raise ValueError(f'expected (B,{self._dims[2]},h,w), got {tuple(x.shape)}')
+        hd = self._sync()
+        x = x.detach().to(device=dev, dtype=torch.float32).contiguous()
+        n, _, lh, lw = x.shape
+        up = 2 ** (self._dims[3] - scale)
+
+        def call():
+            if fmt == _lib.FMT_U8_HWC:
+                out = torch.empty((n, lh * up, lw * up, self._dims[0]), dtype=torch.uint8, device=dev)
+            else:
+                out = torch.empty((n, self._dims[0], lh * up, lw * up), dtype=torch.float32, device=dev)
+            _lib.check(_lib.lib().cae_synthesis_scale(hd.ptr, x.data_ptr(), n, lh, lw, scale, out.data_ptr(), fmt,
+                                                      _lib.stream_ptr()))
+            return out
+        return self._guarded(hd, call)
+
+    def forward_scale(self, x: torch.Tensor, scale: int) -> torch.Tensor:
+        """y_q -> the image at 1 / 2^scale of the resolution, (B,C,H/2^scale,W/2^scale) float: the track stops after unit
+        L-1-scale and that level's colour layer writes the image (cae_synthesis_scale).  scale 0 = the reconstruction."""
+        return self._run_scale(x, scale, _lib.FMT_F32_NCHW)
+
+    def forward_scale_u8(self, x: torch.Tensor, scale: int) -> torch.Tensor:
+        """forward_scale with the *255 / clip / truncate / HWC epilogue: (B,H/2^scale,W/2^scale,C) uint8."""
+        return self._run_scale(x, scale, _lib.FMT_U8_HWC)
+
+    def forward_symbols_u8(self, sym: torch.Tensor, eb, defer: bool = False, scale: int = 0):
         """int32 symbols (B,channels_bn,h,w) on the GPU -> (B,H,W,C) uint8 tiles: the dequantiser of `eb` fused into
         the layout conversion in front of the first layer (cae_synthesis_symbols); equals
-        self.forward_u8(eb.dequantize_symbols(sym)).  ``defer``: -> (tiles, RangeTicket), see _guarded."""
+        self.forward_u8(eb.dequantize_symbols(sym)).  ``defer``: -> (tiles, RangeTicket), see _guarded.
+        ``scale``: tiles at 1 / 2^scale of the resolution (cae_synthesis_symbols_scale; see forward_scale)."""
+        scale = self._check_scale(scale)
         dev = _lib.require_gpu()
         if sym.dim() != 4 or sym.size(1) != self._dims[2] or sym.dtype != torch.int32:
             raise ValueError(f'expected int32 (B,{self._dims[2]},h,w), got {sym.dtype} {tuple(sym.shape)}')
@@ -756,8 +800,13 @@ class Synthesizer(_Track):
         L = self._dims[3]
 
         def call():
-            out = torch.empty((n, lh * 2 ** L, lw * 2 ** L, self._dims[0]), dtype=torch.uint8, device=dev)
-            _lib.check(_lib.lib().cae_synthesis_symbols(hd.ptr, sym.data_ptr(), n, lh, lw, out.data_ptr(),
-                                                        _lib.FMT_U8_HWC, _lib.stream_ptr()))
+            up = 2 ** (L - scale)
+            out = torch.empty((n, lh * up, lw * up, self._dims[0]), dtype=torch.uint8, device=dev)
+            if scale == 0:
+                _lib.check(_lib.lib().cae_synthesis_symbols(hd.ptr, sym.data_ptr(), n, lh, lw, out.data_ptr(),
+                                                            _lib.FMT_U8_HWC, _lib.stream_ptr()))
+            else:
+                _lib.check(_lib.lib().cae_synthesis_symbols_scale(hd.ptr, sym.data_ptr(), n, lh, lw, scale,
+                                                                  out.data_ptr(), _lib.FMT_U8_HWC, _lib.stream_ptr()))
             return out
         return self._guarded(hd, call, defer)

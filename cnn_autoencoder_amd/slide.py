@@ -144,11 +144,13 @@ class SlideCoder:
         return self.eb.encode_symbols(sym_host, self.coder_threads)
 
     @torch.no_grad()
-    def decompress(self, payloads: Sequence[bytes], h: int, w: int) -> torch.Tensor:
-        """payloads -> (n,h,w,c) uint8 in HBM."""
+    def decompress(self, payloads: Sequence[bytes], h: int, w: int, scale: int = 0) -> torch.Tensor:
+        """payloads -> (n,h,w,c) uint8 in HBM; ``scale = s``: (n,h/2^s,w/2^s,c), the tiles at 1 / 2^s of the resolution
+        (Synthesizer.forward_scale_u8)."""
+        scale = self.dec._check_scale(scale)
         size = (h // 2 ** self.level, w // 2 ** self.level)
         y_q = self.eb.decompress(payloads, size, coder=self.coder)
-        return self.dec.forward_u8(y_q)
+        return self.dec.forward_scale_u8(y_q, scale) if scale else self.dec.forward_u8(y_q)
 
     # ---- device coder: kernels on a stream per batch in flight, called from worker threads ----------------------
     def _coder_stream(self, k):
@@ -218,9 +220,9 @@ class SlideCoder:
         done.synchronize()
         return sym
 
-    def _redo_synthesis(self, payloads, h, w, main):
+    def _redo_synthesis(self, payloads, h, w, main, scale=0):
         with torch.cuda.device(_dev()), torch.cuda.stream(main):
-            return self.decompress(payloads, h, w)  # guarded calls
+            return self.decompress(payloads, h, w, scale)  # guarded calls
 
     # (events are created with blocking=True: a host thread that waits for one sleeps instead of spinning on a core --
     #  on a CPU share of 16 per GPU the spinning waiters took cycles from the coder pools)
@@ -288,14 +290,16 @@ class SlideCoder:
                 yield inflight.pop(0).result()
 
     @torch.no_grad()
-    def decompress_batches(self, payload_batches, h: int, w: int, to_host: bool = False):
-        """Generator: for every list of rANS payloads (tiles of h x w pixels) the (n,h,w,c) uint8 reconstruction, in
+    def decompress_batches(self, payload_batches, h: int, w: int, to_host: bool = False, scale: int = 0):
+        """``scale = s``: reconstructions at 1 / 2^s of the resolution, (n,h/2^s,w/2^s,c) (Synthesizer.forward_scale_u8).
+        Generator: for every list of rANS payloads (tiles of h x w pixels) the (n,h,w,c) uint8 reconstruction, in
         order: a CUDA tensor, or with ``to_host`` a numpy array in a pinned ring buffer that stays valid until the
         generator has advanced two more times.  A host worker range-decodes up to `depth` batches ahead into pinned
         memory, H2D runs on a side stream beside the synthesis kernels, and with ``to_host`` a second worker pulls
         each reconstruction over the DMA engines while the next batch is synthesised."""
         from concurrent.futures import ThreadPoolExecutor
         from . import _lib
+        scale = self.dec._check_scale(scale)
         main = torch.cuda.current_stream(_dev())
         up = self._h2d_stream()
         depth = self.depth
@@ -325,7 +329,7 @@ class SlideCoder:
                 self._busy[key] = ev
                 main.wait_event(ev)
             sym.record_stream(main)
-            rec, guard = self.dec.forward_symbols_u8(sym.reshape(sym.size(0), C, lh, lw), self.eb, defer=True)
+            rec, guard = self.dec.forward_symbols_u8(sym.reshape(sym.size(0), C, lh, lw), self.eb, defer=True, scale=scale)
             done = torch.cuda.Event(blocking=True)
             done.record(main)
             return rec, guard, done
@@ -334,7 +338,7 @@ class SlideCoder:
             """the reconstruction once it is complete and known to be in range (f16x3 guard; rare fp32 repeat)"""
             done.synchronize()
             if guard.overflowed():
-                rec = self._redo_synthesis(payloads, h, w, main)
+                rec = self._redo_synthesis(payloads, h, w, main, scale)
                 torch.cuda.current_stream(rec.device).synchronize()
             return rec
 

@@ -199,15 +199,118 @@ class ZarrArray:
         for idx in self.chunk_indices():
             self.write_chunk(idx, value[self.chunk_slices(idx)])
 
-    def __getitem__(self, key) -> np.ndarray:
-        if key != slice(None) and key is not Ellipsis:
-            raise NotImplementedError('only whole-array reads are supported')
-        out = np.empty(self.shape, dtype=self.dtype)
-        for idx in self.chunk_indices():
-            sl = self.chunk_slices(idx)
-            chunk = self.read_chunk(idx)
-            out[sl] = chunk[tuple(slice(0, s.stop - s.start) for s in sl)]
+    # ---- region reads ------------------------------------------------------------------------
+    def normalize_key(self, key) -> List[Tuple[int, int, bool]]:
+        """numpy basic indexing with step 1 -> per dimension (start, stop, is_integer), bounds clipped as numpy does.
+        Integers, slices, one Ellipsis, negative bounds, fewer keys than dimensions; anything else raises (zarr's
+        wording where zarr has one)."""
+        keys = list(key) if isinstance(key, tuple) else [key]
+        if sum(1 for k in keys if k is Ellipsis) > 1:
+            raise IndexError("an index can only have a single ellipsis ('...')")
+        n_given = sum(1 for k in keys if k is not Ellipsis)
+        if n_given > len(self.shape):
+            raise IndexError(f'too many indices for array; expected {len(self.shape)}, got {n_given}')
+        if any(k is Ellipsis for k in keys):
+            at = [k is Ellipsis for k in keys].index(True)
+            keys[at:at + 1] = [slice(None)] * (len(self.shape) - n_given)
+        keys += [slice(None)] * (len(self.shape) - len(keys))
+        out = []
+        for k, n in zip(keys, self.shape):
+            if isinstance(k, slice):
+                if k.step not in (None, 1):
+                    raise NotImplementedError('only slices with step 1 are supported')
+                start, stop, _ = k.indices(n)  # raises TypeError on non-integer bounds, as numpy does
+                out.append((start, max(start, stop), False))
+            elif isinstance(k, (int, np.integer)) and not isinstance(k, (bool, np.bool_)):
+                i = int(k)
+                if i < -n or i >= n:
+                    raise IndexError(f'index out of bounds for dimension with length {n}')
+                i += n if i < 0 else 0
+                out.append((i, i + 1, True))
+            else:
+                raise IndexError('unsupported selection item for basic indexing; expected integer or slice, got '
+                                 f'{type(k)!r}')
         return out
+
+    def _gather(self, sel, cshape, fetch) -> np.ndarray:
+        """The region `sel` (normalize_key form, in the coordinates of an array whose chunks have shape `cshape`) from
+        the chunks it touches, each fetched once: fetch(list of chunk indices) yields their arrays in order."""
+        out = np.empty(tuple(b - a for a, b, _ in sel), dtype=self.dtype)
+        squeeze = tuple(slice(None) if not is_int else 0 for _, _, is_int in sel)
+        if out.size:
+            touched = [tuple(int(v) for v in i) for i in np.ndindex(*[(b - 1) // c - a // c + 1
+                                                                      for (a, b, _), c in zip(sel, cshape)])]
+            touched = [tuple(i + a // c for i, (a, _, _), c in zip(idx, sel, cshape)) for idx in touched]
+            for idx, chunk in zip(touched, fetch(touched)):
+                src, dst = [], []
+                for i, c, (a, b, _) in zip(idx, cshape, sel):
+                    lo, hi = max(a, i * c), min(b, (i + 1) * c)
+                    src.append(slice(lo - i * c, hi - i * c))
+                    dst.append(slice(lo - a, hi - a))
+                out[tuple(dst)] = chunk[tuple(src)]
+        return out[squeeze]
+
+    def __getitem__(self, key) -> np.ndarray:
+        """Region read: numpy basic indexing with step 1 (see normalize_key).  Only the chunks the key touches are read
+        and decoded, each once; a missing chunk file reads as fill_value."""
+        return self._gather(self.normalize_key(key), self.chunks, lambda idxs: (self.read_chunk(i) for i in idxs))
+
+    def read_region(self, key, scale: int = 0, batch_tiles: int = 32, coder: str = 'host') -> np.ndarray:
+        """``self[key]`` at 1 / 2^scale of the resolution; `key` is in full-resolution coordinates.  The scale-s image
+        of the array is the mosaic of its chunks' scale-s tiles; the result is rows floor(y0 / 2^s) : ceil(y1 / 2^s) of
+        that mosaic, likewise for columns, channel keys as given.  The touched chunks of a 'cae' array are decoded in
+        batches of `batch_tiles` (SlideCoder.decompress_batches: range decoder on `coder`, synthesis stopped at the
+        level); scale > 0 needs such an array (and colour layers: multiscale_analysis=True)."""
+        from .codec import ConvolutionalAutoencoder
+        from .entropy import check_coder
+        check_coder(coder)
+        if isinstance(scale, bool) or int(scale) != scale or scale < 0:
+            raise ValueError(f'scale must be a non-negative integer, got {scale!r}')
+        scale = int(scale)
+        sel = self.normalize_key(key)
+        if not isinstance(self.codec, ConvolutionalAutoencoder):
+            if scale > 0:
+                raise ValueError("scale > 0 needs an array whose codec is 'cae'")
+            return self[key]
+        import struct
+        f = 2 ** scale
+        ph, pw = self.chunks[0], self.chunks[1]
+        if len(self.shape) != 3 or ph % f or pw % f:
+            raise ValueError(f'chunks {self.chunks} cannot be read at scale {scale}')
+        def scaled(d, a, b, is_int):
+            if d >= 2:
+                return a, b, is_int
+            if is_int:  # the pixel of the scaled image that holds it
+                return a // f, a // f + 1, True
+            return a // f, (max(a // f, -(-b // f)) if b > a else a // f), False
+        sel = [scaled(d, *t) for d, t in enumerate(sel)]
+        cshape = (ph // f, pw // f, self.chunks[2])
+
+        def fetch(idxs):
+            from . import slide
+            sc = self.__dict__.setdefault('_slide_coders', {}).get(coder)
+            if sc is None:
+                sc = self._slide_coders[coder] = slide.SlideCoder(self.codec, coder=coder)
+            bufs = {i: self.read_chunk_bytes(i) for i in idxs}
+            have = [i for i in idxs if bufs[i] is not None]
+            for i in have:
+                if struct.unpack('>QQ', bufs[i][:16]) != (ph, pw):
+                    raise ValueError('chunk header does not match the chunk shape')
+            groups = list(_batches(have, batch_tiles))
+            stream = sc.decompress_batches(([bufs[i][16:] for i in g] for g in groups), ph, pw, to_host=True,
+                                           scale=scale)
+            done = {}
+            pending = iter(idxs)
+            for g, rec in zip(groups, stream):  # rec: pinned ring buffer, copied out before the generator advances
+                for i, tile in zip(g, rec):
+                    done[i] = tile
+                for i in pending:
+                    yield done.pop(i) if bufs[i] is not None else np.full(cshape, self.fill_value, self.dtype)
+                    if i == g[-1]:
+                        break
+            for i in pending:  # missing chunks behind the last decoded one
+                yield np.full(cshape, self.fill_value, self.dtype)
+        return self._gather(sel, cshape, fetch)
 
 
 # ---- the reference's compress / decompress flows ---------------------------------------------------
@@ -318,15 +421,29 @@ def compress_image(codec: str, checkpoint, image: np.ndarray, output_filename: s
 
 
 def decompress_image(input_filename: str, data_group: str = '0/0', checkpoint=None, gpu: bool = True,
-                     batch_tiles: int = 32, coder: str = 'host') -> np.ndarray:
+                     batch_tiles: int = 32, coder: str = 'host', roi=None, scale: int = 0) -> np.ndarray:
     """decompress.py:40-96: open the zarr (chunk decode = the stored codec), and when `checkpoint` is given the
     array holds 'cae_bn' latents that the decoder turns back into pixels (decompress.py:61-79).  coder: 'host' or
-    'device' range decoder of the 'cae' chunks."""
+    'device' range decoder of the 'cae' chunks.
+    roi = (y0, y1, x0, x1), full-resolution pixels: the reference's ROI flow (decompress.py:49-59, parse_roi applied
+    before anything is decoded) -- only the chunks under the rectangle are read and decoded.  scale = s: the image at
+    1 / 2^s of the resolution (ZarrArray.read_region: rows floor(y0 / 2^s) : ceil(y1 / 2^s) of the mosaic of scale-s
+    tiles); needs a 'cae' array or the 'cae_bn' + checkpoint branch, and a model with colour layers."""
     from .entropy import check_coder
     check_coder(coder)
     from .codec import ConvolutionalAutoencoder, _module, autoencoder_from_state_dict
     z = ZarrArray.open(input_filename, data_group)
+    if isinstance(scale, bool) or int(scale) != scale or scale < 0:
+        raise ValueError(f'scale must be a non-negative integer, got {scale!r}')
+    scale = int(scale)
+    if roi is not None:
+        y0, y1, x0, x1 = (int(v) for v in roi)
+        if not (0 <= y0 <= y1 and 0 <= x0 <= x1):
+            raise ValueError(f'roi must be (y0, y1, x0, x1) with 0 <= y0 <= y1 and 0 <= x0 <= x1, got {tuple(roi)}')
     if checkpoint is None or (isinstance(checkpoint, str) and not len(checkpoint)):
+        if roi is not None or scale:
+            key = Ellipsis if roi is None else (slice(y0, y1), slice(x0, x1))
+            return z.read_region(key, scale=scale, batch_tiles=batch_tiles, coder=coder)
         if isinstance(z.codec, ConvolutionalAutoencoder):
             # pipelined: a host worker range-decodes the next batches while the GPU synthesises
             import struct
@@ -355,15 +472,31 @@ def decompress_image(input_filename: str, data_group: str = '0/0', checkpoint=No
     import torch
     model = autoencoder_from_state_dict(checkpoint=checkpoint, gpu=gpu, train=False)
     dec = _module(model['decoder'])
-    scale = 2 ** dec.rec_level
-    lat = z[:]  # (gy*lat, gx*lat, C) float32 latents, decoded by the 'cae_bn' codec
+    scale = dec._check_scale(scale)
+    up = 2 ** (dec.rec_level - scale)  # pixels of the result per latent element
     ly, lx = z.chunks[0], z.chunks[1]
-    out = np.empty((lat.shape[0] * scale, lat.shape[1] * scale, dec._dims[0]), dtype=np.uint8)
-    idxs = z.chunk_indices()
+    gy, gx = z.grid[0], z.grid[1]
+    if roi is None:
+        ty0, ty1, tx0, tx1 = 0, gy, 0, gx
+    else:  # the tiles under the rectangle, and only their latent chunks
+        full = 2 ** dec.rec_level
+        y1, x1 = min(y1, gy * ly * full), min(x1, gx * lx * full)
+        y0, x0 = min(y0, y1), min(x0, x1)
+        ty0, tx0 = y0 // (ly * full), x0 // (lx * full)
+        ty1, tx1 = max(ty0, -(-y1 // (ly * full))), max(tx0, -(-x1 // (lx * full)))
+    # (ny*lat, nx*lat, C) float32 latents of those tiles, decoded by the 'cae_bn' codec
+    lat = z[ty0 * ly:ty1 * ly, tx0 * lx:tx1 * lx]
+    out = np.empty((lat.shape[0] * up, lat.shape[1] * up, dec._dims[0]), dtype=np.uint8)
+    idxs = [(i, j, 0) for i in range(ty1 - ty0) for j in range(tx1 - tx0)]
     for group in _batches(idxs, batch_tiles):
         batch = np.stack([lat[i * ly:(i + 1) * ly, j * lx:(j + 1) * lx] for i, j, _ in group])
         with torch.no_grad():
-            rec = dec.forward_u8(torch.from_numpy(batch).permute(0, 3, 1, 2).contiguous().cuda()).cpu().numpy()
+            y_q = torch.from_numpy(batch).permute(0, 3, 1, 2).contiguous().cuda()
+            rec = (dec.forward_scale_u8(y_q, scale) if scale else dec.forward_u8(y_q)).cpu().numpy()
         for (i, j, _), tile in zip(group, rec):
-            out[i * ly * scale:(i + 1) * ly * scale, j * lx * scale:(j + 1) * lx * scale] = tile
-    return out
+            out[i * ly * up:(i + 1) * ly * up, j * lx * up:(j + 1) * lx * up] = tile
+    if roi is None:
+        return out
+    f = 2 ** scale
+    oy, ox = ty0 * ly * up, tx0 * lx * up
+    return np.ascontiguousarray(out[y0 // f - oy:max(y0 // f, -(-y1 // f)) - oy, x0 // f - ox:max(x0 // f, -(-x1 // f)) - ox])

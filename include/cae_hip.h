@@ -168,6 +168,22 @@ int cae_analysis_symbols(cae_model_t *m, const void *tiles_dev, int fmt, int n, 
 int cae_synthesis_symbols(cae_model_t *m, const int32_t *symbols_dev, int n, int lh, int lw, void *out_dev, int fmt,
                           void *stream);
 
+/* Synthesis that stops at a level: the image at 1 / 2^scale of the resolution.  With L = compression_level, units
+ * 0 .. L-1-scale run, then colour layer L-1-scale on that level's activations, and nothing after it.
+ * out_dev: (n, C, lh*2^(L-scale), lw*2^(L-scale)) fp32 NCHW, or (n, lh*2^(L-scale), lw*2^(L-scale), C) uint8 HWC with
+ * the x255 / clip / truncate epilogue of the full decode (_autoencoders.py:576-580).  scale == 0 is cae_synthesis /
+ * cae_synthesis_symbols, unchanged; scale > 0 needs the colour layer of that level (cae_model_set_color_layer).  The
+ * workspace is sized for the levels that run.  The f16x3 range guard works as for every call (cae_range_check).
+ * Colour layers from at most 128 to at most 4 channels run on color_small_kernel (fp32 vector FMA on both precision
+ * paths, only the useful output channels computed; f16x3: on hi + lo of the split rows, fp32 weights, raises the range
+ * flag on a non-finite result); wider ones on the generic stride-1 launch followed by a uint8 conversion kernel.
+ * CAE_ERR_ARG, before any launch: scale outside 0 .. L-1, colour layer not set, the level k//2 rows or columns or
+ * fewer (reflect padding).  CAE_ERR_UNSUPPORTED: f16x3 with more than 32 image channels. */
+int cae_synthesis_scale(cae_model_t *m, const float *latents_dev, int n, int lh, int lw, int scale, void *out_dev,
+                        int fmt, void *stream);
+int cae_synthesis_symbols_scale(cae_model_t *m, const int32_t *symbols_dev, int n, int lh, int lw, int scale,
+                                void *out_dev, int fmt, void *stream);
+
 /* One GDN / IGDN layer on an NCHW tensor (compressai.layers.GDN.forward; reference call site
  * _autoencoders.py:29-30).  Uses the beta/gamma of layer `index` of `track`. */
 int cae_gdn_forward(cae_model_t *m, int track, int index, const float *x_dev, int n, int h, int w,
