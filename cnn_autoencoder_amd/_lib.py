@@ -108,6 +108,11 @@ SYMBOLS = {
     'cae_t_pointwise_acc': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p]),
     'cae_t_fold_acc': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     'cae_t_pyramid_down': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    'cae_t_msssim_level_fwd': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, ctypes.POINTER(ctypes.c_double), c_int, ctypes.c_double,
+                                       ctypes.c_double, c_void_p, c_void_p, c_size_t, c_void_p]),
+    'cae_t_msssim_level_bwd': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, ctypes.POINTER(ctypes.c_double), c_int, ctypes.c_double,
+                                       ctypes.c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    'cae_t_avgpool2_bwd': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     'cae_t_bn_moments': (c_int, [c_void_p, c_void_p, c_int, c_int, ctypes.c_long, c_void_p, c_void_p, c_void_p]),
     'cae_t_bn_affine': (c_int, [c_void_p, c_void_p, c_int, c_int, ctypes.c_long, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     'cae_t_colsum': (c_int, [c_void_p, ctypes.c_long, c_int, c_void_p, c_void_p]),

@@ -370,6 +370,27 @@ int cae_t_pointwise_acc(const void *x16, int n, int h, int w, int ck, const void
 int cae_t_fold_acc(const float *gext32, int n, int h, int w, int pad, int cp, float *out32, void *stream);
 int cae_t_pyramid_down(const float *x_nchw, int n, int c, int h, int w, float *out_nchw, void *stream);
 
+/* Differentiable MS-SSIM (DistMSSSIMLoss, _ratedist.py:66-90) on planar fp32 images: `planes` = N * C images of h x w,
+ * x the reconstruction (carries the gradient), y the target.  `taps_host` points to the `win` window taps in HOST memory
+ * (win odd, 1..11; they travel by value with the launch); the window is applied separably without padding, rows first.
+ * The images are float32; the local moments and the two index maps are formed in float64 (the variances cancel).
+ * cae_t_msssim_level_fwd: one scale -- ssim_cs_dev[2p] = mean ssim map, [2p+1] = mean contrast-structure map of plane p
+ * (float64) with the constants c1, c2; workspace_dev: 2 * planes * ceil((h-win+1)/32) * ceil((w-win+1)/32) doubles.
+ * cae_t_msssim_level_bwd: its adjoint with respect to x, ADDED to gx_dev (planes * h * w floats):
+ * gx += d/dx sum_p (g_ssim_dev[p] * ssim_p + g_cs_dev[p] * cs_p); g_ssim_dev or g_cs_dev may be NULL (zeros);
+ * workspace_dev: 3 * planes * (h-win+1) * (w-win+1) floats (the coefficient maps between its two launches).
+ * cae_t_avgpool2_bwd: the adjoint of cae_avgpool2 -- g_fine_dev (planes, h, w) = a quarter of the g_coarse_dev sample
+ * that covers each pixel (OVERWRITES g_fine_dev; coarse size as cae_avgpool2's output).
+ * planes must be 1..65535 for the two level calls (one grid row per plane; CAE_ERR_ARG otherwise): split larger batches.
+ * No atomics, fixed summation order: all three are bitwise reproducible. */
+int cae_t_msssim_level_fwd(const float *x_dev, const float *y_dev, int planes, int h, int w, const double *taps_host, int win,
+                           double c1, double c2, double *ssim_cs_dev, double *workspace_dev, size_t workspace_elems,
+                           void *stream);
+int cae_t_msssim_level_bwd(const float *x_dev, const float *y_dev, int planes, int h, int w, const double *taps_host, int win,
+                           double c1, double c2, const double *g_ssim_dev, const double *g_cs_dev, float *gx_dev,
+                           float *workspace_dev, size_t workspace_elems, void *stream);
+int cae_t_avgpool2_bwd(const float *g_coarse_dev, int planes, int h, int w, float *g_fine_dev, void *stream);
+
 /* Fused forms (csrc/cae_train_gdn.hpp; cp <= 128): the forward also saves the per-element factor f (y = z f: n^(-1/2),
  * IGDN n^(1/2)) in the register order the backward reads back -- f_saved holds cae_t_gdn_saved_elems(pixels, cp) floats
  * (0: shape not built) -- and the backward is ONE kernel: g_z (bf16), g_gamma, g_beta from z, f and the gradient with
