@@ -4,6 +4,7 @@
 #include "cae_kernels.hpp"
 #include "cae_kernels_f16.hpp"
 #include "cae_launch.hpp"
+#include "cae_pack.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -28,274 +29,29 @@ int fail(int code, const char *fmt, ...) {
     return code;
 }
 
-static int round_ct(int c) {
-    const int t = (c + 31) / 32;
-    if (t <= 1) return 1;
-    if (t <= 2) return 2;
-    if (t <= 4) return 4;
-    if (t <= 6) return 6;
-    return -1;
-}
+void dev_free(void *p) { (void)hipFree(p); }
 
-// ---- packing -----------------------------------------------------------------------------------
-// weights -> [chunk][ky][kx][ct][lane][j]:  value W(cout = 32ct + (lane&31), cin = 8chunk + 4(lane>>5) + j, ky, kx)
-static std::vector<float> pack_weights(const float *w, bool transposed, int cin, int cout, int ks, int ct,
-                                       bool flip = false) {
-    const int chunks = (cin + 7) / 8;
-    std::vector<float> out((size_t)chunks * ks * ks * ct * 256, 0.0f);
-    size_t o = 0;
-    for (int c = 0; c < chunks; ++c)
-        for (int ky = 0; ky < ks; ++ky)
-            for (int kx = 0; kx < ks; ++kx)
-                for (int t = 0; t < ct; ++t)
-                    for (int lane = 0; lane < 64; ++lane)
-                        for (int j = 0; j < 4; ++j, ++o) {
-                            const int co = 32 * t + (lane & 31);
-                            const int ci = 8 * c + 4 * (lane >> 5) + j;
-                            if (co < cout && ci < cin) {
-                                // conv: (cout,cin,k,k); transposed conv: (cin,cout,k,k)
-                                const int sy = flip ? ks - 1 - ky : ky, sx = flip ? ks - 1 - kx : kx;
-                                const size_t idx = transposed ? (((size_t)ci * cout + co) * ks + sy) * ks + sx
-                                                              : (((size_t)co * cin + ci) * ks + sy) * ks + sx;
-                                out[o] = w[idx];
-                            }
-                        }
-    return out;
-}
-
-// colour layer to <= 4 channels (color_small_kernel) -> [chunk][ky][kx][8 channels][4 outputs], zero padded
-static std::vector<float> pack_color4(const float *w, int cin, int cout, int ks) {
-    const int chunks = (cin + 7) / 8;
-    std::vector<float> out((size_t)chunks * ks * ks * 32, 0.0f);
-    for (int ci = 0; ci < cin; ++ci)
-        for (int ky = 0; ky < ks; ++ky)
-            for (int kx = 0; kx < ks; ++kx)
-                for (int co = 0; co < cout; ++co)
-                    out[((((size_t)(ci >> 3) * ks + ky) * ks + kx) * 8 + (ci & 7)) * 4 + co] =
-                        w[(((size_t)co * cin + ci) * ks + ky) * ks + kx];
-    return out;
-}
-
-// gamma -> [jt][co][q][lane][jj]: value G(c = 32co + (lane&31), j = 32jt + row(4q+jj) + 4(lane>>5))
-static std::vector<float> pack_gamma(const float *g, int C, int ct) {
-    std::vector<float> out((size_t)ct * ct * 4 * 256, 0.0f);
-    size_t o = 0;
-    for (int jt = 0; jt < ct; ++jt)
-        for (int co = 0; co < ct; ++co)
-            for (int q = 0; q < 4; ++q)
-                for (int lane = 0; lane < 64; ++lane)
-                    for (int jj = 0; jj < 4; ++jj, ++o) {
-                        const int s = 4 * q + jj;
-                        const int c = 32 * co + (lane & 31);
-                        const int j = 32 * jt + (s & 3) + 8 * (s >> 2) + 4 * (lane >> 5);
-                        if (c < C && j < C) out[o] = g[(size_t)c * C + j];
-                    }
-    return out;
-}
-
-// first analysis layer (cin <= 4): [tap][ct][lane][2]: W(cout = 32ct + (lane&31), ch = 2j + (lane>>5), tap)
-static std::vector<float> pack_first(const float *w, int cin, int cout, int ks, int ct) {
-    std::vector<float> out((size_t)ks * ks * ct * 128, 0.0f);
-    size_t o = 0;
-    for (int tap = 0; tap < ks * ks; ++tap)
-        for (int t = 0; t < ct; ++t)
-            for (int lane = 0; lane < 64; ++lane)
-                for (int j = 0; j < 2; ++j, ++o) {
-                    const int co = 32 * t + (lane & 31), ch = 2 * j + (lane >> 5);
-                    if (co < cout && ch < cin) out[o] = w[((size_t)co * cin + ch) * ks * ks + tap];
-                }
-    return out;
-}
-
-// last synthesis layer (cout <= 4): [nd][ndx][q][lane][s]:
-//   A(row = lane&15 = 4c + 2py + px, cin = 16q + 4(lane>>4) + s) = W[cin][c][2d+py+P][2dx+px+P]
-static std::vector<float> pack_last(const float *w, int cin, int cout, int ks) {
-    const int P = ks / 2, dlo = -((P + 1) / 2), dhi = (ks - 1 - P) / 2, nb = dhi - dlo + 1;
-    const int nq = (cin + 15) / 16;
-    std::vector<float> out((size_t)nb * nb * nq * 256, 0.0f);
-    size_t o = 0;
-    for (int nd = 0; nd < nb; ++nd)
-        for (int ndx = 0; ndx < nb; ++ndx)
-            for (int q = 0; q < nq; ++q)
-                for (int lane = 0; lane < 64; ++lane)
-                    for (int s2 = 0; s2 < 4; ++s2, ++o) {
-                        const int row = lane & 15, c = row >> 2, py = (row >> 1) & 1, px = row & 1;
-                        const int ci = 16 * q + 4 * (lane >> 4) + s2;
-                        const int ky = 2 * (dlo + nd) + py + P, kx = 2 * (dlo + ndx) + px + P;
-                        if (c < cout && ci < cin && ky >= 0 && ky < ks && kx >= 0 && kx < ks)
-                            out[o] = w[(((size_t)ci * cout + c) * ks + ky) * ks + kx];
-                    }
-    return out;
-}
-
-// ---- f16x3 packing -------------------------------------------------------------------------------
-static inline void split_half(float v, _Float16 &hi, _Float16 &lo) {
-    hi = (_Float16)v;
-    lo = (_Float16)(v - (float)hi);
-}
-
-// every entry representable in the split format (finite, |v| <= 65504)?
-static bool fits_f16(const float *v, size_t n) {
-    for (size_t i = 0; i < n; ++i)
-        if (!(std::fabs(v[i]) <= 65504.0f)) return false;
-    return true;
-}
-
-// weights -> [q][ky][kx][ct][hl][lane][8]: W(cout = 32ct + (lane&31), cin = 16q + 8(lane>>5) + j, ky, kx)
-static std::vector<_Float16> pack_weights_f16(const float *w, bool transposed, int cin, int cout, int ks, int ct,
-                                              bool flip = false) {
-    const int nq = (cin + 15) / 16;
-    std::vector<_Float16> out((size_t)nq * ks * ks * ct * 2 * 512, (_Float16)0.0f);
-    for (int q = 0; q < nq; ++q)
-        for (int ky = 0; ky < ks; ++ky)
-            for (int kx = 0; kx < ks; ++kx)
-                for (int t = 0; t < ct; ++t)
-                    for (int lane = 0; lane < 64; ++lane)
-                        for (int j = 0; j < 8; ++j) {
-                            const int co = 32 * t + (lane & 31);
-                            const int ci = 16 * q + 8 * (lane >> 5) + j;
-                            float v = 0.0f;
-                            if (co < cout && ci < cin) {
-                                const int sy = flip ? ks - 1 - ky : ky, sx = flip ? ks - 1 - kx : kx;
-                                v = transposed ? w[(((size_t)ci * cout + co) * ks + sy) * ks + sx]
-                                               : w[(((size_t)co * cin + ci) * ks + sy) * ks + sx];
-                            }
-                            _Float16 hi, lo;
-                            split_half(v, hi, lo);
-                            const size_t base = (((((size_t)q * ks + ky) * ks + kx) * ct + t) * 2) * 512;
-                            out[base + (size_t)lane * 8 + j] = hi;
-                            out[base + 512 + (size_t)lane * 8 + j] = lo;
-                        }
-    return out;
-}
-
-// gamma -> [jt][co][s][hl][lane][8]: G(c = 32co + (lane&31), j = 32jt + row(8s+e) + 4(lane>>5))
-static std::vector<_Float16> pack_gamma_f16(const float *g, int C, int ct) {
-    std::vector<_Float16> out((size_t)ct * ct * 2 * 2 * 512, (_Float16)0.0f);
-    for (int jt = 0; jt < ct; ++jt)
-        for (int co = 0; co < ct; ++co)
-            for (int s2 = 0; s2 < 2; ++s2)
-                for (int lane = 0; lane < 64; ++lane)
-                    for (int e = 0; e < 8; ++e) {
-                        const int r = 8 * s2 + e;
-                        const int c = 32 * co + (lane & 31);
-                        const int j = 32 * jt + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-                        const float v = (c < C && j < C) ? g[(size_t)c * C + j] : 0.0f;
-                        _Float16 hi, lo;
-                        split_half(v, hi, lo);
-                        const size_t base = ((((size_t)jt * ct + co) * 2 + s2) * 2) * 512;
-                        out[base + (size_t)lane * 8 + e] = hi;
-                        out[base + 512 + (size_t)lane * 8 + e] = lo;
-                    }
-    return out;
-}
-
-// first layer f16x3: [s][ct][hl][lane][8]: W(cout = 32ct + (lane&31), tap = 4s + 2(lane>>5) + (j>>2), ch = j&3)
-static std::vector<_Float16> pack_first_f16(const float *w, int cin, int cout, int ks, int ct) {
-    const int ns = (ks * ks + 3) / 4;
-    std::vector<_Float16> out((size_t)ns * ct * 2 * 512, (_Float16)0.0f);
-    for (int s2 = 0; s2 < ns; ++s2)
-        for (int t = 0; t < ct; ++t)
-            for (int lane = 0; lane < 64; ++lane)
-                for (int j = 0; j < 8; ++j) {
-                    const int co = 32 * t + (lane & 31), tap = 4 * s2 + 2 * (lane >> 5) + (j >> 2), ch = j & 3;
-                    float v = 0.0f;
-                    if (co < cout && ch < cin && tap < ks * ks) v = w[((size_t)co * cin + ch) * ks * ks + tap];
-                    _Float16 hi, lo;
-                    split_half(v, hi, lo);
-                    const size_t base = (((size_t)s2 * ct + t) * 2) * 512;
-                    out[base + (size_t)lane * 8 + j] = hi;
-                    out[base + 512 + (size_t)lane * 8 + j] = lo;
-                }
-    return out;
-}
-
-// last layer f16x3: [nd][ndx][q][hl][lane][8]: A(row = lane&15 = 4c + 2py + px, cin = 32q + 8(lane>>4) + j)
-static std::vector<_Float16> pack_last_f16(const float *w, int cin, int cout, int ks) {
-    const int P = ks / 2, dlo = -((P + 1) / 2), dhi = (ks - 1 - P) / 2, nb = dhi - dlo + 1;
-    const int nq = (cin + 31) / 32;
-    std::vector<_Float16> out((size_t)nb * nb * nq * 2 * 512, (_Float16)0.0f);
-    for (int nd = 0; nd < nb; ++nd)
-        for (int ndx = 0; ndx < nb; ++ndx)
-            for (int q = 0; q < nq; ++q)
-                for (int lane = 0; lane < 64; ++lane)
-                    for (int j = 0; j < 8; ++j) {
-                        const int row = lane & 15, c = row >> 2, py = (row >> 1) & 1, px = row & 1;
-                        const int ci = 32 * q + 8 * (lane >> 4) + j;
-                        const int ky = 2 * (dlo + nd) + py + P, kx = 2 * (dlo + ndx) + px + P;
-                        float v = 0.0f;
-                        if (c < cout && ci < cin && ky >= 0 && ky < ks && kx >= 0 && kx < ks)
-                            v = w[(((size_t)ci * cout + c) * ks + ky) * ks + kx];
-                        _Float16 hi, lo;
-                        split_half(v, hi, lo);
-                        const size_t base = ((((size_t)nd * nb + ndx) * nq + q) * 2) * 512;
-                        out[base + (size_t)lane * 8 + j] = hi;
-                        out[base + 512 + (size_t)lane * 8 + j] = lo;
-                    }
-    return out;
-}
-
-// last layer as a product map (cae_kernels_f16.hpp, pmap): [jt][s][hl][lane][8]:
-//   A(row = lane&31 = 3 tap + c, k = 32jt + row(8s+e) + 4(lane>>5)) = W[cin = k][c][ky][kx], tap = 3 ky + kx  (k = 3)
-static std::vector<_Float16> pack_pmap_f16(const float *w, int cin, int cout, int njt) {
-    // njt = channel tiles of the PRODUCING layer's accumulators (round_ct(cin): 96 channels live in 4 tiles), zero padded
-    std::vector<_Float16> out((size_t)njt * 2 * 2 * 512, (_Float16)0.0f);
-    for (int jt = 0; jt < njt; ++jt)
-        for (int s2 = 0; s2 < 2; ++s2)
-            for (int lane = 0; lane < 64; ++lane)
-                for (int e = 0; e < 8; ++e) {
-                    const int r = 8 * s2 + e;
-                    // map row (lane & 31) = slot of the record as pmap_gather_kernel reads it (cae_kernels_f16.hpp):
-                    // [taps 4, 5, 7, 8 | taps 3, 6, pad 2 | taps 1, 2, pad 2 | tap 0, pad 1] x 3 channels
-                    static const int slot_tap[32] = {4, 4, 4, 5, 5, 5, 7, 7, 7, 8, 8, 8, 3, 3, 3, 6, 6, 6, -1, -1,
-                                                     1, 1, 1, 2, 2, 2, -1, -1, 0, 0, 0, -1};
-                    static const int slot_c[32] = {0, 1, 2, 0, 1, 2, 0, 1, 2, 0, 1, 2, 0, 1, 2, 0, 1, 2, 0, 0,
-                                                   0, 1, 2, 0, 1, 2, 0, 0, 0, 1, 2, 0};
-                    const int row = lane & 31, tap = slot_tap[row], c = slot_c[row];
-                    const int j = 32 * jt + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-                    float v = 0.0f;
-                    if (tap >= 0 && c < cout && j < cin) v = w[((size_t)j * cout + c) * 9 + tap];
-                    _Float16 hi, lo;
-                    split_half(v, hi, lo);
-                    const size_t base = (((size_t)jt * 2 + s2) * 2) * 512;
-                    out[base + (size_t)lane * 8 + e] = hi;
-                    out[base + 512 + (size_t)lane * 8 + e] = lo;
-                }
-    return out;
-}
-
-static int upload_raw(const void *src, size_t bytes, void **dev) {
-    if (*dev) {
-        (void)hipFree(*dev);
-        *dev = nullptr;
-    }
-    HIP_TRY(hipMalloc(dev, bytes));
-    HIP_TRY(hipMemcpy(*dev, src, bytes, hipMemcpyHostToDevice));
+int DevBuf::alloc(size_t n) {
+    reset();
+    HIP_TRY(hipMalloc(&p, n));
+    bytes = n;
     return CAE_OK;
 }
 
-static int upload(const std::vector<float> &v, float **dev) {
-    if (*dev) {
-        (void)hipFree(*dev);
-        *dev = nullptr;
-    }
-    HIP_TRY(hipMalloc((void **)dev, v.size() * sizeof(float)));
-    HIP_TRY(hipMemcpy(*dev, v.data(), v.size() * sizeof(float), hipMemcpyHostToDevice));
+int DevBuf::upload(const void *src, size_t n) {
+    CAE_TRY(alloc(n));
+    HIP_TRY(hipMemcpy(p, src, n, hipMemcpyHostToDevice));
     return CAE_OK;
 }
 
 int Model::ensure_ws(int which, size_t bytes) {
-    if (ws_bytes[which] >= bytes) return CAE_OK;
-    if (ws[which]) {
+    DevBuf &b = ws[which];
+    if (b.bytes >= bytes) return CAE_OK;
+    if (b) {
         HIP_TRY(hipDeviceSynchronize());
-        (void)hipFree(ws[which]);
-        ws[which] = nullptr;
-        ws_bytes[which] = 0;
+        b.reset();
     }
-    bytes = (bytes + (1u << 20)) & ~(size_t)((1u << 20) - 1);
-    HIP_TRY(hipMalloc(&ws[which], bytes));
-    ws_bytes[which] = bytes;
-    return CAE_OK;
+    return b.alloc((bytes + (1u << 20)) & ~(size_t)((1u << 20) - 1));
 }
 
 int Model::order_stream(void *stream) {
@@ -311,17 +67,15 @@ int Model::order_stream(void *stream) {
 
 int Model::ensure_device() {
     if (!zero) {
-        HIP_TRY(hipMalloc((void **)&zero, 1024));  // zero page: out-of-range halo source, null medians (192 floats)
-        HIP_TRY(hipMemset(zero, 0, 1024));
+        CAE_TRY(zero.alloc(1024));  // zero page: out-of-range halo source, null medians (192 floats)
+        HIP_TRY(hipMemset(zero.p, 0, 1024));
     }
     if (medians_dirty && ent.channels > 0) {
-        int rc = upload(ent.medians, &medians_dev);
-        if (rc) return rc;
+        CAE_TRY(medians_dev.upload(ent.medians));
         medians_dirty = false;
     }
     if (density_dirty && !density.empty()) {
-        int rc = upload(density, &density_dev);
-        if (rc) return rc;
+        CAE_TRY(density_dev.upload(density));
         density_dirty = false;
     }
     if (!flags) {
@@ -348,45 +102,9 @@ bool Model::f16_usable() const {
     return true;
 }
 
-static void free_stages(Layer &l) {
-    for (auto &sg : l.stages) {
-        if (sg.wp16) (void)hipFree(sg.wp16);
-        if (sg.gp16) (void)hipFree(sg.gp16);
-        for (float *q : {sg.wp, sg.bias, sg.gp, sg.beta})
-            if (q) (void)hipFree(q);
-    }
-    l.stages.clear();
-}
-
-Model::~Model() {
+Model::~Model() {  // (every device buffer frees itself)
     if (order_event) (void)hipEventDestroy((hipEvent_t)order_event);
-    for (auto *tr : {&enc, &dec})
-        for (auto &l : *tr) {
-            if (l.wp) (void)hipFree(l.wp);
-            if (l.bias) (void)hipFree(l.bias);
-            if (l.gp) (void)hipFree(l.gp);
-            if (l.beta) (void)hipFree(l.beta);
-            if (l.wp_edge) (void)hipFree(l.wp_edge);
-            free_stages(l);
-            if (l.color_wp) (void)hipFree(l.color_wp);
-            if (l.color_bias) (void)hipFree(l.color_bias);
-            if (l.color_wp16) (void)hipFree(l.color_wp16);
-            if (l.color_w4) (void)hipFree(l.color_w4);
-            if (l.wp16) (void)hipFree(l.wp16);
-            if (l.gp16) (void)hipFree(l.gp16);
-            if (l.wp_edge16) (void)hipFree(l.wp_edge16);
-            if (l.wp_pmap16) (void)hipFree(l.wp_pmap16);
-        }
-    for (int i = 0; i < 4; ++i)
-        if (ws[i]) (void)hipFree(ws[i]);
-    for (int i = 0; i < 2; ++i)
-        if (ws16[i]) (void)hipFree(ws16[i]);
-    if (zero) (void)hipFree(zero);
     if (flags) (void)hipHostFree(flags);
-    if (medians_dev) (void)hipFree(medians_dev);
-    if (density_dev) (void)hipFree(density_dev);
-    if (bits_ws) (void)hipFree(bits_ws);
-    if (ent_dev.buf) (void)hipFree(ent_dev.buf);
 }
 
 // ---- kernel dispatch ---------------------------------------------------------------------------
@@ -422,6 +140,46 @@ static unsigned ew_grid(size_t total) {
     return (unsigned)std::min<size_t>(std::max<size_t>(b, 1), 256 * 8 * 4);
 }
 
+// The layer a (track, index) pair names, into `l`.
+static int layer_of(Model *m, int track, int index, Layer *&l) {
+    if (track != CAE_ANALYSIS && track != CAE_SYNTHESIS) return fail(CAE_ERR_ARG, "bad track %d", track);
+    if (index < 0 || index >= m->L) return fail(CAE_ERR_ARG, "layer index %d out of range", index);
+    l = &(track == CAE_ANALYSIS ? m->enc : m->dec)[index];
+    return CAE_OK;
+}
+
+// A per-channel vector (bias: fill 0, beta: fill 1) padded to ct*32 entries on the device; no vector, no buffer.
+static int upload_channels(DevBuf &d, const float *v, int c, int ct, float fill) {
+    if (!v) {
+        d.reset();
+        return CAE_OK;
+    }
+    return d.upload(pad_channels(v, c, ct, fill));
+}
+
+// What every launch site fills the same way; the site adds its weights and whatever else is special about it.  (Tile
+// grid and contraction chunks are the launcher's business: cae_launch_*.hip.)
+static LayerArgs layer_args(const Model *m, const float *in, int in_planes, void *out, int n, int h, int w, int oh, int ow,
+                            int ct, int cout, int outfmt, int act, int *flag) {
+    LayerArgs a{};
+    a.in = in;
+    a.out = out;
+    a.zero = m->zero.get<float>();
+    a.medians = m->zero.get<float>();
+    a.flag = flag;
+    a.N = n;
+    a.H = h;
+    a.W = w;
+    a.OH = oh;
+    a.OW = ow;
+    a.in_planes = in_planes;
+    a.out_planes = ct * 4;
+    a.cout = cout;
+    a.outfmt = outfmt;
+    a.act = act;
+    return a;
+}
+
 }  // namespace cae
 
 using namespace cae;
@@ -429,8 +187,9 @@ using namespace cae;
 template <int R>
 static void launch_likelihood(Model *m, const float *y, int n, int hw, float *yhat, float *lik, double *part,
                               hipStream_t st) {
-    hipLaunchKernelGGL(likelihood_kernel<R>, dim3(m->c_bn, n), dim3(256), 0, st, y, m->medians_dev, m->density_dev,
-                       m->density_per_channel, m->density_k, m->density_bound, m->likelihood_plain, m->c_bn, hw, yhat, lik, part);
+    hipLaunchKernelGGL(likelihood_kernel<R>, dim3(m->c_bn, n), dim3(256), 0, st, y, m->medians_dev.get<float>(),
+                       m->density_dev.get<float>(), m->density_per_channel, m->density_k, m->density_bound,
+                       m->likelihood_plain, m->c_bn, hw, yhat, lik, part);
 }
 
 // (re)builds stage `stage` of a unit: a stride-1 (transposed) convolution cin -> cin with its epilogue
@@ -442,41 +201,27 @@ static int set_stage(Model *m, int track, Layer &l, int stage, const float *w, c
     Layer::Stage &sg = l.stages[stage];
     // synthesis: ConvTranspose2d(stride 1, padding k//2) == zero-padded correlation with the flipped kernel
     const bool tr = track == CAE_SYNTHESIS;
-    int rc = upload(pack_weights(w, tr, l.cin, l.cin, m->ks, ctin, tr), &sg.wp);
-    if (rc) return rc;
-    if (bias) {
-        std::vector<float> b(ctin * 32, 0.0f);
-        std::copy(bias, bias + l.cin, b.begin());
-        if ((rc = upload(b, &sg.bias))) return rc;
-    } else if (sg.bias) {
-        (void)hipFree(sg.bias);
-        sg.bias = nullptr;
-    }
+    CAE_TRY(sg.wp.upload(pack_weights(w, tr, l.cin, l.cin, m->ks, ctin, tr)));
+    CAE_TRY(upload_channels(sg.bias, bias, l.cin, ctin, 0.0f));
     sg.gdn = beta != nullptr;
     if (sg.gdn) {
-        std::vector<float> b(ctin * 32, 1.0f);
-        std::copy(beta, beta + l.cin, b.begin());
-        if ((rc = upload(b, &sg.beta))) return rc;
-        if ((rc = upload(pack_gamma(gamma, l.cin, ctin), &sg.gp))) return rc;
+        CAE_TRY(upload_channels(sg.beta, beta, l.cin, ctin, 1.0f));
+        CAE_TRY(sg.gp.upload(pack_gamma(gamma, l.cin, ctin)));
     }
     sg.act = act;
     sg.add_res = add_residual != 0;
     sg.post_act = post_act;
     if (m->precision == 1) {  // f16x3: the stage's weights as split halves (same packing as the strided layers)
         if (!fits_f16(w, (size_t)l.cin * l.cin * m->ks * m->ks)) l.f16_bad = true;
-        auto w16 = pack_weights_f16(w, tr, l.cin, l.cin, m->ks, ctin, tr);
-        if ((rc = upload_raw(w16.data(), w16.size() * sizeof(_Float16), &sg.wp16))) return rc;
+        CAE_TRY(sg.wp16.upload(pack_weights_f16(w, tr, l.cin, l.cin, m->ks, ctin, tr)));
         if (sg.gdn) {
             if (!fits_f16(gamma, (size_t)l.cin * l.cin)) l.f16_bad = true;
-            auto g16 = pack_gamma_f16(gamma, l.cin, ctin);
-            if ((rc = upload_raw(g16.data(), g16.size() * sizeof(_Float16), &sg.gp16))) return rc;
+            CAE_TRY(sg.gp16.upload(pack_gamma_f16(gamma, l.cin, ctin)));
         }
     }
     if (track == CAE_ANALYSIS) {  // the fused first-layer kernels read the raw tile; a stage sits in between
-        if (l.wp_edge) (void)hipFree(l.wp_edge);
-        if (l.wp_edge16) (void)hipFree(l.wp_edge16);
-        l.wp_edge = nullptr;
-        l.wp_edge16 = nullptr;
+        l.wp_edge.reset();
+        l.wp_edge16.reset();
     }
     return CAE_OK;
 }
@@ -508,69 +253,50 @@ static int run_stages(Model *m, const Layer &l, bool synthesis, int n, int ch, i
         const size_t rows = (size_t)n * cur_planes * ch;
         if (synthesis)
             hipLaunchKernelGGL(c8s_to_c8_kernel<true>, dim3(ew_grid(rows * cw)), dim3(256), 0, st, (const char *)cur,
-                               (float *)m->ws[tmp], rows, cw);
+                               (float *)m->ws[tmp].p, rows, cw);
         else
             hipLaunchKernelGGL(c8s_to_c8_kernel<false>, dim3(ew_grid(rows * cw)), dim3(256), 0, st, (const char *)cur,
-                               (float *)m->ws[tmp], rows, cw);
+                               (float *)m->ws[tmp].p, rows, cw);
         HIP_TRY(hipGetLastError());
-        cur = (const float *)m->ws[tmp];
+        cur = (const float *)m->ws[tmp].p;
         cur_idx = tmp;
         int rc = run_stages(m, l, synthesis, n, ch, cw, cur, cur_idx, cur_planes, st, false, nullptr);
         if (rc) return rc;
         const int back = pick_slot(cur_idx, cur_idx);
         const size_t orows = (size_t)n * cur_planes * ch;
         if (synthesis)
-            hipLaunchKernelGGL(c8_to_c8s_kernel<true>, dim3(ew_grid(orows * cw)), dim3(256), 0, st, cur, (char *)m->ws[back],
+            hipLaunchKernelGGL(c8_to_c8s_kernel<true>, dim3(ew_grid(orows * cw)), dim3(256), 0, st, cur, (char *)m->ws[back].p,
                                orows, cw, flag);
         else
-            hipLaunchKernelGGL(c8_to_c8s_kernel<false>, dim3(ew_grid(orows * cw)), dim3(256), 0, st, cur, (char *)m->ws[back],
+            hipLaunchKernelGGL(c8_to_c8s_kernel<false>, dim3(ew_grid(orows * cw)), dim3(256), 0, st, cur, (char *)m->ws[back].p,
                                orows, cw, flag);
         HIP_TRY(hipGetLastError());
-        cur = (const float *)m->ws[back];
+        cur = (const float *)m->ws[back].p;
         cur_idx = back;
         return CAE_OK;
     }
     const float *unit_in = cur;
     const int unit_idx = cur_idx, unit_planes = cur_planes;
     for (const Layer::Stage &sg : l.stages) {
-        LayerArgs b{};
         const int ctin = round_ct(l.cin);
         const int out_idx = pick_slot(unit_idx, cur_idx);
-        b.in = cur;
-        b.out = m->ws[out_idx];
-        b.wp = sg.wp;
-        b.bias = sg.bias;
-        b.gp = sg.gp;
-        b.beta = sg.beta;
-        b.zero = m->zero;
-        b.medians = m->zero;
-        b.N = n;
-        b.H = ch;
-        b.W = cw;
-        b.OH = ch;
-        b.OW = cw;
-        b.in_planes = cur_planes;
-        b.cci = l.chunks;
-        b.out_planes = ctin * 4;
-        b.cout = l.cin;
-        b.tiles_x = (cw + 15) / 16;
-        b.tiles_y = (ch + 2 * CONV_NW - 1) / (2 * CONV_NW);
-        b.outfmt = OUT_C8;
-        b.act = sg.act;
+        LayerArgs b = layer_args(m, cur, cur_planes, m->ws[out_idx].p, n, ch, cw, ch, cw, ctin, l.cin, OUT_C8, sg.act,
+                                 f16 ? flag : nullptr);
+        b.bias = sg.bias.get<float>();
+        b.beta = sg.beta.get<float>();
         b.res = sg.add_res ? unit_in : nullptr;
         b.res_planes = unit_planes;
         b.post_act = sg.post_act;
         int rc;
         if (f16) {
             if (!sg.wp16 || (sg.gdn && !sg.gp16)) return fail(CAE_ERR_ARG, "stage uploaded before precision 1 was selected");
-            b.wp = (const float *)sg.wp16;
-            b.gp = (const float *)sg.gp16;
-            b.cci = (l.cin + 15) / 16;
-            b.tiles_y = (ch + 15) / 16;
-            b.flag = flag;
-            rc = launch_conv_s1_f16(m->ks, ctin, synthesis, sg.gdn, b, st);
+            b.wp = sg.wp16.get<float>();
+            b.gp = sg.gp16.get<float>();
+            rc = launch_conv_s1_f16(m->ks, ctin, synthesis, sg.gdn, l.cin, b, st);
         } else {
-            rc = launch_conv_s1(m->ks, ctin, synthesis, sg.gdn, b, st);
+            b.wp = sg.wp.get<float>();
+            b.gp = sg.gp.get<float>();
+            rc = launch_conv_s1(m->ks, ctin, synthesis, sg.gdn, l.cin, b, st);
         }
         if (rc) return rc;
         cur = (const float *)b.out;
@@ -580,23 +306,19 @@ static int run_stages(Model *m, const Layer &l, bool synthesis, int n, int ch, i
     return CAE_OK;
 }
 
-// LDS need of conv_s2_f16_kernel<KS,CT,GDN> (same formula as the kernel's constexprs): two stage buffers of
-// weights + halo.  k=5 with 192 output channels needs 192 KiB: such a layer runs on the fp32 kernel instead.
-// LDS need of deconv_last_f16_kernel (LastGeomF16: <3, 8, 3> and <5, 4, 2>): halo ring + all weights resident.  A last
-// layer with more than 160 input channels does not fit and runs on the generic transposed-convolution kernel.
-static bool last_f16_fits(int ks, int cin) {
-    const int nq = (cin + 31) / 32;
-    const int nb = ks == 3 ? 2 : 3, nw = ks == 3 ? 8 : 4, depth = ks == 3 ? 3 : 2;
-    const int halo_instr = (8 * (nw + nb - 1) * (32 + nb - 1) + 63) / 64;
-    const int stage = ((halo_instr + nw - 1) / nw) * nw * 1024;
-    return depth * stage + nb * nb * nq * 2048 <= 160 * 1024;
-}
-
-static bool conv_f16_fits(int ks, int ct, bool gdn) {
-    if (gdn && ct > 4) gdn = false;  // wider than 128 channels: convolution without the epilogue + gdn_f16_kernel
-    const int halo_instr = (4 * 16 * (2 * 16 + ks - 2) + 63) / 64;
-    const int stage = std::max(ks * ct * 2048 + halo_instr * 1024, gdn ? ct * 4096 : 0);
-    return 2 * stage <= 160 * 1024;
+// Colour layer of a synthesis level: the reflect-padded stride-1 convolution of the level's activations `in` (h x w,
+// fp32 C8 rows, or C8SP split rows on the f16x3 path) to its image channels, fp32 NCHW in `out`.
+static int launch_color(Model *m, const Layer &l, bool f16, const float *in, int in_planes, int n, int h, int w, float *out,
+                        int *flag, hipStream_t st) {
+    const int ct = round_ct(l.color_cout);
+    LayerArgs c = layer_args(m, in, in_planes, out, n, h, w, h, w, ct, l.color_cout, OUT_NCHW, 0, f16 ? flag : nullptr);
+    c.bias = l.color_bias.get<float>();
+    if (f16) {
+        c.wp = l.color_wp16.get<float>();
+        return launch_color_f16(m->ks, l.cout, c, st);
+    }
+    c.wp = l.color_wp.get<float>();
+    return launch_conv_s1(m->ks, ct, false, false, l.cout, c, st);
 }
 
 extern "C" {
@@ -639,74 +361,47 @@ int cae_model_set_layer(cae_model_t *mm, int track, int index, int cin, int cout
                         const float *beta, const float *gamma) {
     Model *m = reinterpret_cast<Model *>(mm);
     if (!m || !w) return fail(CAE_ERR_ARG, "NULL model or weight");
-    if (track != CAE_ANALYSIS && track != CAE_SYNTHESIS) return fail(CAE_ERR_ARG, "bad track %d", track);
-    if (index < 0 || index >= m->L) return fail(CAE_ERR_ARG, "layer index %d out of range", index);
+    Layer *lp;
+    CAE_TRY(layer_of(m, track, index, lp));
     if ((beta == nullptr) != (gamma == nullptr)) return fail(CAE_ERR_ARG, "beta and gamma must come together");
     const int ct = round_ct(cout);
     if (ct < 0 || round_ct(cin) < 0) return fail(CAE_ERR_UNSUPPORTED, "more than 192 channels not supported");
     std::lock_guard<std::mutex> lk(m->mu);
-    Layer &l = (track == CAE_ANALYSIS ? m->enc : m->dec)[index];
+    Layer &l = *lp;
     l.cin = cin;
     l.cout = cout;
     l.ct = ct;
     l.chunks = (cin + 7) / 8;
     l.set = true;
-    int rc = upload(pack_weights(w, track == CAE_SYNTHESIS, cin, cout, m->ks, ct), &l.wp);
-    if (rc) return rc;
-    if (bias) {
-        std::vector<float> b(ct * 32, 0.0f);
-        std::copy(bias, bias + cout, b.begin());
-        if ((rc = upload(b, &l.bias))) return rc;
-    } else if (l.bias) {
-        (void)hipFree(l.bias);
-        l.bias = nullptr;
-    }
-    if (l.wp_edge) {
-        (void)hipFree(l.wp_edge);
-        l.wp_edge = nullptr;
-    }
-    if (track == CAE_ANALYSIS && index == 0 && cin <= 4) {
-        if ((rc = upload(pack_first(w, cin, cout, m->ks, ct), &l.wp_edge))) return rc;
-    } else if (track == CAE_SYNTHESIS && index == m->L - 1 && cout <= 4 && beta == nullptr) {
-        if ((rc = upload(pack_last(w, cin, cout, m->ks), &l.wp_edge))) return rc;
-    }
+    CAE_TRY(l.wp.upload(pack_weights(w, track == CAE_SYNTHESIS, cin, cout, m->ks, ct)));
+    CAE_TRY(upload_channels(l.bias, bias, cout, ct, 0.0f));
+    // the layers with a kernel of their own: the first analysis layer, the last synthesis layer
+    const bool first = track == CAE_ANALYSIS && index == 0 && cin <= 4;
+    const bool last = track == CAE_SYNTHESIS && index == m->L - 1 && cout <= 4 && beta == nullptr;
+    l.wp_edge.reset();
+    if (first)
+        CAE_TRY(l.wp_edge.upload(pack_first(w, cin, cout, m->ks, ct)));
+    else if (last)
+        CAE_TRY(l.wp_edge.upload(pack_last(w, cin, cout, m->ks)));
     l.f16_bad = false;
     if (m->precision == 1) {
         // the split format holds |v| <= 65504: a model with larger (or non-finite) weights runs on the fp32 kernels
         const size_t nw = (size_t)cin * cout * m->ks * m->ks;
         l.f16_bad = !fits_f16(w, nw) || (gamma && !fits_f16(gamma, (size_t)cout * cout));
-        if (l.wp_edge16) {
-            (void)hipFree(l.wp_edge16);
-            l.wp_edge16 = nullptr;
-        }
-        if (track == CAE_ANALYSIS && index == 0 && cin <= 4) {
-            auto e16 = pack_first_f16(w, cin, cout, m->ks, ct);
-            if ((rc = upload_raw(e16.data(), e16.size() * sizeof(_Float16), &l.wp_edge16))) return rc;
-        } else if (track == CAE_SYNTHESIS && index == m->L - 1 && cout <= 4 && beta == nullptr) {
-            auto e16 = pack_last_f16(w, cin, cout, m->ks);
-            if ((rc = upload_raw(e16.data(), e16.size() * sizeof(_Float16), &l.wp_edge16))) return rc;
-        }
-        if (l.wp_pmap16) {
-            (void)hipFree(l.wp_pmap16);
-            l.wp_pmap16 = nullptr;
-        }
-        if (track == CAE_SYNTHESIS && index == m->L - 1 && m->ks == 3 && cout <= 3 && beta == nullptr) {
-            auto pm16 = pack_pmap_f16(w, cin, cout, round_ct(cin));
-            if ((rc = upload_raw(pm16.data(), pm16.size() * sizeof(_Float16), &l.wp_pmap16))) return rc;
-        }
-        auto w16 = pack_weights_f16(w, track == CAE_SYNTHESIS, cin, cout, m->ks, ct);
-        if ((rc = upload_raw(w16.data(), w16.size() * sizeof(_Float16), &l.wp16))) return rc;
-        if (gamma) {
-            auto g16 = pack_gamma_f16(gamma, cout, ct);
-            if ((rc = upload_raw(g16.data(), g16.size() * sizeof(_Float16), &l.gp16))) return rc;
-        }
+        l.wp_edge16.reset();
+        if (first)
+            CAE_TRY(l.wp_edge16.upload(pack_first_f16(w, cin, cout, m->ks, ct)));
+        else if (last)
+            CAE_TRY(l.wp_edge16.upload(pack_last_f16(w, cin, cout, m->ks)));
+        l.wp_pmap16.reset();
+        if (last && m->ks == 3 && cout <= 3) CAE_TRY(l.wp_pmap16.upload(pack_pmap_f16(w, cin, cout, round_ct(cin))));
+        CAE_TRY(l.wp16.upload(pack_weights_f16(w, track == CAE_SYNTHESIS, cin, cout, m->ks, ct)));
+        if (gamma) CAE_TRY(l.gp16.upload(pack_gamma_f16(gamma, cout, ct)));
     }
     l.gdn = beta != nullptr;
     if (l.gdn) {
-        std::vector<float> b(ct * 32, 1.0f);
-        std::copy(beta, beta + cout, b.begin());
-        if ((rc = upload(b, &l.beta))) return rc;
-        if ((rc = upload(pack_gamma(gamma, cout, ct), &l.gp))) return rc;
+        CAE_TRY(upload_channels(l.beta, beta, cout, ct, 1.0f));
+        CAE_TRY(l.gp.upload(pack_gamma(gamma, cout, ct)));
     }
     return CAE_OK;
 }
@@ -714,16 +409,16 @@ int cae_model_set_layer(cae_model_t *mm, int track, int index, int cin, int cout
 int cae_model_set_layer_act(cae_model_t *mm, int track, int index, int act, const float *pre_w, const float *pre_b) {
     Model *m = reinterpret_cast<Model *>(mm);
     if (!m) return fail(CAE_ERR_ARG, "NULL model");
-    if (track != CAE_ANALYSIS && track != CAE_SYNTHESIS) return fail(CAE_ERR_ARG, "bad track %d", track);
-    if (index < 0 || index >= m->L) return fail(CAE_ERR_ARG, "layer index %d out of range", index);
+    Layer *lp;
+    CAE_TRY(layer_of(m, track, index, lp));
     if (act < 0 || act > 2) return fail(CAE_ERR_ARG, "bad activation %d", act);
     std::lock_guard<std::mutex> lk(m->mu);
-    Layer &l = (track == CAE_ANALYSIS ? m->enc : m->dec)[index];
+    Layer &l = *lp;
     if (!l.set) return fail(CAE_ERR_ARG, "set the layer before its activation");
     if (l.gdn && (act != 0 || pre_w)) return fail(CAE_ERR_ARG, "a GDN unit has no other activation");
     if (pre_b && !pre_w) return fail(CAE_ERR_ARG, "pre-convolution bias without weight");
     l.act = act;
-    free_stages(l);
+    l.stages.clear();
     if (pre_w) {
         int rc = set_stage(m, track, l, 0, pre_w, pre_b, nullptr, nullptr, act, 0, 0);
         if (rc) return rc;
@@ -735,14 +430,14 @@ int cae_model_set_layer_stage(cae_model_t *mm, int track, int index, int stage, 
                               const float *beta, const float *gamma, int act, int add_residual, int post_act) {
     Model *m = reinterpret_cast<Model *>(mm);
     if (!m || !w) return fail(CAE_ERR_ARG, "NULL model or weight");
-    if (track != CAE_ANALYSIS && track != CAE_SYNTHESIS) return fail(CAE_ERR_ARG, "bad track %d", track);
-    if (index < 0 || index >= m->L) return fail(CAE_ERR_ARG, "layer index %d out of range", index);
+    Layer *lp;
+    CAE_TRY(layer_of(m, track, index, lp));
     if (stage < 0 || stage > 1) return fail(CAE_ERR_ARG, "a unit has at most two stride-1 stages");
     if (act < 0 || act > 2 || post_act < 0 || post_act > 2) return fail(CAE_ERR_ARG, "bad activation");
     if ((beta == nullptr) != (gamma == nullptr)) return fail(CAE_ERR_ARG, "beta and gamma must come together");
     if (beta && act != 0) return fail(CAE_ERR_ARG, "a GDN stage has no other activation");
     std::lock_guard<std::mutex> lk(m->mu);
-    Layer &l = (track == CAE_ANALYSIS ? m->enc : m->dec)[index];
+    Layer &l = *lp;
     if (!l.set) return fail(CAE_ERR_ARG, "set the layer before its stages");
     if (stage > (int)l.stages.size()) return fail(CAE_ERR_ARG, "set stage 0 before stage 1");
     return set_stage(m, track, l, stage, w, bias, beta, gamma, act, add_residual, post_act);
@@ -758,30 +453,15 @@ int cae_model_set_color_layer(cae_model_t *mm, int index, int cin, int cout, con
     if (!l.set) return fail(CAE_ERR_ARG, "set the synthesis layer before its colour layer");
     if (cin != l.cout) return fail(CAE_ERR_ARG, "colour layer %d expects %d input channels, the level produces %d", index, cin, l.cout);
     const int ct = round_ct(cout);
-    int rc = upload(pack_weights(w, false, cin, cout, m->ks, ct), &l.color_wp);
-    if (rc) return rc;
-    if (bias) {
-        std::vector<float> b(ct * 32, 0.0f);
-        std::copy(bias, bias + cout, b.begin());
-        if ((rc = upload(b, &l.color_bias))) return rc;
-    } else if (l.color_bias) {
-        (void)hipFree(l.color_bias);
-        l.color_bias = nullptr;
-    }
+    CAE_TRY(l.color_wp.upload(pack_weights(w, false, cin, cout, m->ks, ct)));
+    CAE_TRY(upload_channels(l.color_bias, bias, cout, ct, 0.0f));
     l.color_cout = cout;
-    if (l.color_w4) {
-        (void)hipFree(l.color_w4);
-        l.color_w4 = nullptr;
-    }
-    if (cin <= 128 && cout <= 4 && (rc = upload(pack_color4(w, cin, cout, m->ks), &l.color_w4))) return rc;
-    if (l.color_wp16) {
-        (void)hipFree(l.color_wp16);
-        l.color_wp16 = nullptr;
-    }
+    l.color_w4.reset();
+    if (cin <= 128 && cout <= 4) CAE_TRY(l.color_w4.upload(pack_color4(w, cin, cout, m->ks)));
+    l.color_wp16.reset();
     if (m->precision == 1 && ct == 1) {  // f16x3: colour layers to at most 32 channels (wider: the fp32 path)
         if (!fits_f16(w, (size_t)cin * cout * m->ks * m->ks)) l.f16_bad = true;
-        auto w16 = pack_weights_f16(w, false, cin, cout, m->ks, ct);
-        if ((rc = upload_raw(w16.data(), w16.size() * sizeof(_Float16), &l.color_wp16))) return rc;
+        CAE_TRY(l.color_wp16.upload(pack_weights_f16(w, false, cin, cout, m->ks, ct)));
     }
     return CAE_OK;
 }
@@ -884,7 +564,7 @@ static int analysis_impl(cae_model_t *mm, const void *tiles, int fmt, int n, int
     std::lock_guard<std::mutex> lk(m->mu);
     if ((rc = m->ensure_device()) || (rc = m->order_stream(stream))) return rc;
     const bool f16 = m->f16_usable();
-    const bool first_fused = f16 ? m->enc[0].wp_edge16 != nullptr : m->enc[0].wp_edge != nullptr;
+    const bool first_fused = f16 ? (bool)m->enc[0].wp_edge16 : (bool)m->enc[0].wp_edge;
     int64_t ticket = 0;
     g_last_ticket = 0;
     int *flag = f16 ? m->next_flag(&ticket) : m->flags_dev;  // (fp32 kernels never write it)
@@ -923,85 +603,65 @@ static int analysis_impl(cae_model_t *mm, const void *tiles, int fmt, int n, int
             if (fmt == CAE_FMT_U8_HWC) {
                 // rare (more than 4 input channels): uint8 -> fp32 C8 (exact /255) in ws[1] -> split rows in ws[0]
                 hipLaunchKernelGGL(u8hwc_to_c8_kernel, dim3(ew_grid(tot)), dim3(256), 0, st, (const uint8_t *)tiles,
-                                   (float *)m->ws[1], n, h, w, m->c_org, p0);
-                hipLaunchKernelGGL(c8_to_c8s_kernel<false>, dim3(ew_grid(tot)), dim3(256), 0, st, (const float *)m->ws[1],
-                                   (char *)m->ws[0], (size_t)n * p0 * h, w, flag);
+                                   (float *)m->ws[1].p, n, h, w, m->c_org, p0);
+                hipLaunchKernelGGL(c8_to_c8s_kernel<false>, dim3(ew_grid(tot)), dim3(256), 0, st, (const float *)m->ws[1].p,
+                                   (char *)m->ws[0].p, (size_t)n * p0 * h, w, flag);
             } else {
                 hipLaunchKernelGGL(nchw_to_c8s_kernel<false>, dim3(ew_grid(tot)), dim3(256), 0, st,
-                                   (const float *)tiles, (char *)m->ws[0], n, m->c_org, h, w, p0, flag);
+                                   (const float *)tiles, (char *)m->ws[0].p, n, m->c_org, h, w, p0, flag);
             }
         } else if (fmt == CAE_FMT_U8_HWC) {
             hipLaunchKernelGGL(u8hwc_to_c8_kernel, dim3(ew_grid(tot)), dim3(256), 0, st, (const uint8_t *)tiles,
-                               (float *)m->ws[0], n, h, w, m->c_org, p0);
+                               (float *)m->ws[0].p, n, h, w, m->c_org, p0);
         } else {
             hipLaunchKernelGGL(nchw_to_c8_kernel, dim3(ew_grid(tot)), dim3(256), 0, st, (const float *)tiles,
-                               (float *)m->ws[0], n, m->c_org, h * w, p0);
+                               (float *)m->ws[0].p, n, m->c_org, h * w, p0);
         }
         HIP_TRY(hipGetLastError());
     }
     prof.end();
 
-    const float *cur = (const float *)m->ws[0];
+    const float *cur = (const float *)m->ws[0].p;
     int cur_planes = p0, ch = h, cw = w;
     int cur_idx = 0;  // workspace slot holding `cur` (0 = converted input; 1..3 rotate)
     for (int i = 0; i < m->L; ++i) {
         const Layer &l = m->enc[i];
         const bool last = i == m->L - 1;
         if (!l.stages.empty() && (rc = run_stages(m, l, false, n, ch, cw, cur, cur_idx, cur_planes, st, f16, flag))) return rc;
-        LayerArgs a{};
-        a.in = cur;
         const int out_idx = pick_slot(cur_idx, cur_idx);
-        a.out = last ? latents : m->ws[out_idx];
-        a.act = l.act;
-        a.wp = l.wp;
-        a.bias = l.bias;
-        a.gp = l.gp;
-        a.beta = l.beta;
-        a.zero = m->zero;
-        a.medians = m->zero;
-        a.flag = flag;
-        a.N = n;
-        a.H = ch;
-        a.W = cw;
-        a.OH = (ch + 1) / 2;
-        a.OW = (cw + 1) / 2;
-        a.in_planes = cur_planes;
-        a.cci = l.chunks;
-        a.out_planes = l.ct * 4;
-        a.cout = l.cout;
-        a.tiles_x = (a.OW + 15) / 16;
-        a.tiles_y = (a.OH + 2 * CONV_NW - 1) / (2 * CONV_NW);
-        a.outfmt = last ? (symbols ? OUT_SYM : OUT_NCHW) : OUT_C8;
-        if (last && symbols) a.medians = m->medians_dev;
+        LayerArgs a = layer_args(m, cur, cur_planes, last ? latents : m->ws[out_idx].p, n, ch, cw, (ch + 1) / 2, (cw + 1) / 2,
+                                 l.ct, l.cout, last ? (symbols ? OUT_SYM : OUT_NCHW) : OUT_C8, l.act, flag);
+        a.wp = l.wp.get<float>();
+        a.bias = l.bias.get<float>();
+        a.gp = l.gp.get<float>();
+        a.beta = l.beta.get<float>();
+        if (last && symbols) a.medians = m->medians_dev.get<float>();
         prof.begin();
         if (i == 0 && first_fused) {
             FirstArgs f{tiles, fmt == CAE_FMT_U8_HWC ? 1 : 0, l.cin};
-            a.tiles_y = (a.OH + 7) / 8;
             if (f16) {
-                a.wp = (const float *)l.wp_edge16;
-                a.gp = (const float *)l.gp16;
+                a.wp = l.wp_edge16.get<float>();
+                a.gp = l.gp16.get<float>();
                 if ((rc = launch_first_f16(m->ks, l.ct, l.gdn, a, f, st))) return rc;
             } else {
-                a.wp = l.wp_edge;
+                a.wp = l.wp_edge.get<float>();
                 if ((rc = launch_first(m->ks, l.ct, l.gdn, a, f, st))) return rc;
             }
         } else if (f16 && conv_f16_fits(m->ks, l.ct, l.gdn) && !(l.gdn && l.ct > 4 && last)) {
-            a.wp = (const float *)l.wp16;
-            a.gp = (const float *)l.gp16;
-            a.cci = (l.cin + 15) / 16;
-            a.tiles_y = (a.OH + 15) / 16;
-            if ((rc = launch_conv_f16(m->ks, l.ct, l.gdn, a, st))) return rc;
+            a.wp = l.wp16.get<float>();
+            a.gp = l.gp16.get<float>();
+            if ((rc = launch_conv_f16(m->ks, l.ct, l.gdn, l.cin, a, st))) return rc;
         } else if (f16) {
             // this layer on the exact-fp32 kernel: split rows -> fp32 C8, convolution, (fp32 C8 -> split rows)
             const int tmp_in = pick_slot(cur_idx, out_idx);
             const size_t rows = (size_t)n * cur_planes * ch;
             hipLaunchKernelGGL(c8s_to_c8_kernel<false>, dim3(ew_grid(rows * cw)), dim3(256), 0, st, (const char *)cur,
-                               (float *)m->ws[tmp_in], rows, cw);
+                               (float *)m->ws[tmp_in].p, rows, cw);
             HIP_TRY(hipGetLastError());
-            a.in = (const float *)m->ws[tmp_in];
+            a.in = (const float *)m->ws[tmp_in].p;
             void *final_out = a.out;
-            if (!last) a.out = m->ws[cur_idx == 0 ? pick_slot(tmp_in, out_idx) : cur_idx];  // the input slot is free now
-            if ((rc = launch_conv(m->ks, l.ct, l.gdn, a, st))) return rc;
+            if (!last) a.out = m->ws[cur_idx == 0 ? pick_slot(tmp_in, out_idx) : cur_idx].p;  // the input slot is free now
+            if ((rc = launch_conv(m->ks, l.ct, l.gdn, l.cin, a, st))) return rc;
             if (!last) {
                 const size_t orows = (size_t)n * l.ct * 4 * a.OH;
                 hipLaunchKernelGGL(c8_to_c8s_kernel<false>, dim3(ew_grid(orows * a.OW)), dim3(256), 0, st, (const float *)a.out,
@@ -1010,7 +670,7 @@ static int analysis_impl(cae_model_t *mm, const void *tiles, int fmt, int n, int
                 a.out = final_out;
             }
         } else {
-            if ((rc = launch_conv(m->ks, l.ct, l.gdn, a, st))) return rc;
+            if ((rc = launch_conv(m->ks, l.ct, l.gdn, l.cin, a, st))) return rc;
         }
         prof.end();
         if (!last && levels && levels[i]) {  // the unit's output as the next unit reads it (split: exactly hi + lo)
@@ -1143,11 +803,11 @@ static int synthesis_impl(cae_model_t *mm, const float *latents, const int32_t *
     prof.begin();
     const size_t tot = (size_t)n * p0 * lh * lw;
     if (f16)
-        hipLaunchKernelGGL(nchw_to_c8s_kernel<true>, dim3(ew_grid(tot)), dim3(256), 0, st, latents, (char *)m->ws[0], n,
-                           m->c_bn, lh, lw, p0, flag, symbols, (const float *)m->medians_dev);
+        hipLaunchKernelGGL(nchw_to_c8s_kernel<true>, dim3(ew_grid(tot)), dim3(256), 0, st, latents, (char *)m->ws[0].p, n,
+                           m->c_bn, lh, lw, p0, flag, symbols, m->medians_dev.get<float>());
     else
-        hipLaunchKernelGGL(nchw_to_c8_kernel, dim3(ew_grid(tot)), dim3(256), 0, st, latents, (float *)m->ws[0], n,
-                           m->c_bn, lh * lw, p0, symbols, (const float *)m->medians_dev);
+        hipLaunchKernelGGL(nchw_to_c8_kernel, dim3(ew_grid(tot)), dim3(256), 0, st, latents, (float *)m->ws[0].p, n,
+                           m->c_bn, lh * lw, p0, symbols, m->medians_dev.get<float>());
     HIP_TRY(hipGetLastError());
     prof.end();
 
@@ -1164,7 +824,7 @@ static int synthesis_impl(cae_model_t *mm, const float *latents, const int32_t *
     if (use_pmap) maxact = std::max(maxact, (size_t)n * (lh << (m->L - 1)) * (lw << (m->L - 1)) * 128);
     if (use_pmap && ((rc = m->ensure_ws(1, maxact)) || (rc = m->ensure_ws(2, maxact)))) return rc;
 
-    const float *cur = (const float *)m->ws[0];
+    const float *cur = (const float *)m->ws[0].p;
     int cur_planes = p0, ch = lh, cw = lw;
     int cur_idx = 0;
     for (int i = 0; i < nrun; ++i) {
@@ -1174,102 +834,49 @@ static int synthesis_impl(cae_model_t *mm, const float *latents, const int32_t *
             prof.begin();
             const int gtx = (cw + 15) / 16, gty = (ch + 15) / 16;
             hipLaunchKernelGGL(pmap_gather_kernel, dim3((unsigned)((size_t)n * gtx * gty)), dim3(256), 0, st, cur,
-                               (const float *)l.bias, out, n, ch, cw, l.cout, fmt == CAE_FMT_U8_HWC ? OUT_U8HWC : OUT_NCHW, gtx,
+                               l.bias.get<float>(), out, n, ch, cw, l.cout, fmt == CAE_FMT_U8_HWC ? OUT_U8HWC : OUT_NCHW, gtx,
                                gty);
             HIP_TRY(hipGetLastError());
             prof.end();
             break;
         }
         if (!l.stages.empty() && (rc = run_stages(m, l, true, n, ch, cw, cur, cur_idx, cur_planes, st, f16, flag))) return rc;
-        LayerArgs a{};
-        a.in = cur;
         const int out_idx = pick_slot(cur_idx, cur_idx);
-        a.out = last ? out : m->ws[out_idx];
-        a.act = l.act;
-        a.wp = l.wp;
-        a.bias = l.bias;
-        a.gp = l.gp;
-        a.beta = l.beta;
-        a.zero = m->zero;
-        a.medians = m->zero;
-        a.flag = flag;
-        a.N = n;
-        a.H = ch;
-        a.W = cw;
-        a.OH = 2 * ch;
-        a.OW = 2 * cw;
-        a.in_planes = cur_planes;
-        a.cci = l.chunks;
-        a.out_planes = l.ct * 4;
-        a.cout = l.cout;
-        a.tiles_x = (cw + 31) / 32;
-        a.tiles_y = (ch + DECONV_NW - 1) / DECONV_NW;
-        a.outfmt = last ? (fmt == CAE_FMT_U8_HWC ? OUT_U8HWC : OUT_NCHW) : OUT_C8;
+        LayerArgs a = layer_args(m, cur, cur_planes, last ? out : m->ws[out_idx].p, n, ch, cw, 2 * ch, 2 * cw, l.ct, l.cout,
+                                 last ? (fmt == CAE_FMT_U8_HWC ? OUT_U8HWC : OUT_NCHW) : OUT_C8, l.act, flag);
+        a.wp = l.wp.get<float>();
+        a.bias = l.bias.get<float>();
+        a.gp = l.gp.get<float>();
+        a.beta = l.beta.get<float>();
         if (use_pmap && i == m->L - 2) {
             a.outfmt = OUT_PMAP;
-            a.pm = m->dec[m->L - 1].wp_pmap16;
+            a.pm = m->dec[m->L - 1].wp_pmap16.p;
         }
         prof.begin();
         if (f16) {
-            a.gp = (const float *)l.gp16;
+            a.gp = l.gp16.get<float>();
             if (last && l.wp_edge16 && last_f16_fits(m->ks, l.cin)) {
-                a.wp = (const float *)l.wp_edge16;
-                a.cci = (l.cin + 31) / 32;
-                a.tiles_x = (cw + 31) / 32;
-                a.tiles_y = (ch + 3) / 4;
-                if ((rc = launch_last_f16(m->ks, a, st))) return rc;
+                a.wp = l.wp_edge16.get<float>();
+                if ((rc = launch_last_f16(m->ks, l.cin, a, st))) return rc;
             } else {
                 if (l.act && l.ct > 4)  // (the 192-channel transposed-convolution kernel carries no activation: registers)
                     return fail(CAE_ERR_UNSUPPORTED, "f16x3: LeakyReLU / ReLU synthesis layers wider than 128 channels run "
                                                      "on the fp32 path: set precision 0");
-                a.wp = (const float *)l.wp16;
-                a.cci = (l.cin + 15) / 16;
-                a.tiles_y = (ch + 7) / 8;
-                if ((rc = launch_deconv_f16(m->ks, l.ct, l.gdn, a, st))) return rc;
+                a.wp = l.wp16.get<float>();
+                if ((rc = launch_deconv_f16(m->ks, l.ct, l.gdn, l.cin, a, st))) return rc;
             }
         } else if (last && l.wp_edge) {
-            a.wp = l.wp_edge;
-            a.cci = (l.cin + 15) / 16;
-            a.tiles_x = (cw + 63) / 64;
-            a.tiles_y = (ch + 3) / 4;
-            if ((rc = launch_last(m->ks, a, st))) return rc;
+            a.wp = l.wp_edge.get<float>();
+            if ((rc = launch_last(m->ks, l.cin, a, st))) return rc;
         } else {
-            if ((rc = launch_deconv(m->ks, l.ct, l.gdn, a, st))) return rc;
+            if ((rc = launch_deconv(m->ks, l.ct, l.gdn, l.cin, a, st))) return rc;
         }
         prof.end();
         if (!last && colors && colors[i]) {  // colour layer of this level (_autoencoders.py:417-436, :448-449)
             if (!l.color_wp) return fail(CAE_ERR_ARG, "colour layer %d not set", i);
             if (f16 && !l.color_wp16)
                 return fail(CAE_ERR_UNSUPPORTED, "f16x3: colour layers to more than 32 channels run on the fp32 path: set precision 0");
-            LayerArgs c{};
-            c.in = (const float *)a.out;
-            c.out = colors[i];
-            c.wp = l.color_wp;
-            c.bias = l.color_bias;
-            c.zero = m->zero;
-            c.medians = m->zero;
-            c.N = n;
-            c.H = a.OH;
-            c.W = a.OW;
-            c.OH = a.OH;
-            c.OW = a.OW;
-            c.in_planes = l.ct * 4;
-            c.cci = (l.cout + 7) / 8;
-            c.out_planes = round_ct(l.color_cout) * 4;
-            c.cout = l.color_cout;
-            c.tiles_x = (a.OW + 15) / 16;
-            c.tiles_y = (a.OH + 2 * CONV_NW - 1) / (2 * CONV_NW);
-            c.outfmt = OUT_NCHW;
-            c.act = 0;
-            if (f16) {  // split rows in (C8SP), reflect padding, NCHW fp32 out
-                c.wp = (const float *)l.color_wp16;
-                c.cci = (l.cout + 15) / 16;
-                c.tiles_y = (a.OH + 15) / 16;
-                c.flag = flag;
-                if ((rc = launch_color_f16(m->ks, c, st))) return rc;
-            } else if ((rc = launch_conv_s1(m->ks, round_ct(l.color_cout), false, false, c, st))) {
-                return rc;
-            }
+            if ((rc = launch_color(m, l, f16, (const float *)a.out, l.ct * 4, n, a.OH, a.OW, colors[i], flag, st))) return rc;
         }
         if (!last && bridges && bridges[i]) {
             const size_t t2 = (size_t)n * l.cout * a.OH * a.OW;
@@ -1292,41 +899,13 @@ static int synthesis_impl(cae_model_t *mm, const float *latents, const int32_t *
         const int ofmt = fmt == CAE_FMT_U8_HWC ? OUT_U8HWC : OUT_NCHW;
         prof.begin();
         if (l.color_w4) {
-            if ((rc = launch_color_small(m->ks, f16, cur, cur_planes, l.cout, l.color_w4, l.color_bias, n, ch, cw,
-                                         l.color_cout, out, ofmt, flag, st)))
+            if ((rc = launch_color_small(m->ks, f16, cur, cur_planes, l.cout, l.color_w4.get<float>(),
+                                         l.color_bias.get<float>(), n, ch, cw, l.color_cout, out, ofmt, flag, st)))
                 return rc;
         } else {
             // more than 128 input or 4 image channels: the generic stride-1 launch (fp32 NCHW), + the uint8 conversion
-            float *img = ofmt == OUT_NCHW ? (float *)out : (float *)m->ws[pick_slot(cur_idx, cur_idx)];
-            LayerArgs c{};
-            c.in = cur;
-            c.out = img;
-            c.wp = l.color_wp;
-            c.bias = l.color_bias;
-            c.zero = m->zero;
-            c.medians = m->zero;
-            c.N = n;
-            c.H = ch;
-            c.W = cw;
-            c.OH = ch;
-            c.OW = cw;
-            c.in_planes = cur_planes;
-            c.cci = (l.cout + 7) / 8;
-            c.out_planes = round_ct(l.color_cout) * 4;
-            c.cout = l.color_cout;
-            c.tiles_x = (cw + 15) / 16;
-            c.tiles_y = (ch + 2 * CONV_NW - 1) / (2 * CONV_NW);
-            c.outfmt = OUT_NCHW;
-            c.act = 0;
-            if (f16) {
-                c.wp = (const float *)l.color_wp16;
-                c.cci = (l.cout + 15) / 16;
-                c.tiles_y = (ch + 15) / 16;
-                c.flag = flag;
-                if ((rc = launch_color_f16(m->ks, c, st))) return rc;
-            } else if ((rc = launch_conv_s1(m->ks, round_ct(l.color_cout), false, false, c, st))) {
-                return rc;
-            }
+            float *img = ofmt == OUT_NCHW ? (float *)out : (float *)m->ws[pick_slot(cur_idx, cur_idx)].p;
+            if ((rc = launch_color(m, l, f16, cur, cur_planes, n, ch, cw, img, flag, st))) return rc;
             if (ofmt == OUT_U8HWC && (rc = launch_nchw_to_u8hwc(img, out, n, l.color_cout, (size_t)ch * cw, st))) return rc;
         }
         prof.end();
@@ -1337,37 +916,24 @@ static int synthesis_impl(cae_model_t *mm, const float *latents, const int32_t *
 int cae_gdn_forward(cae_model_t *mm, int track, int index, const float *x, int n, int h, int w, float *y, void *stream) {
     Model *m = reinterpret_cast<Model *>(mm);
     if (!m || !x || !y) return fail(CAE_ERR_ARG, "NULL argument");
-    if (track != CAE_ANALYSIS && track != CAE_SYNTHESIS) return fail(CAE_ERR_ARG, "bad track %d", track);
-    if (index < 0 || index >= m->L) return fail(CAE_ERR_ARG, "layer index %d out of range", index);
+    Layer *lp;
+    CAE_TRY(layer_of(m, track, index, lp));
     if (n < 1 || h < 1 || w < 1) return fail(CAE_ERR_ARG, "bad tensor shape");
     hipStream_t st = (hipStream_t)stream;
     std::lock_guard<std::mutex> lk(m->mu);
-    const Layer &l = (track == CAE_ANALYSIS ? m->enc : m->dec)[index];
+    const Layer &l = *lp;
     if (!l.set || !l.gdn) return fail(CAE_ERR_ARG, "layer has no GDN");
     const int planes = l.ct * 4;
     int rc;
     if ((rc = m->ensure_device()) || (rc = m->order_stream(stream))) return rc;
     if ((rc = m->ensure_ws(0, (size_t)n * planes * h * w * 32))) return rc;
     const size_t tot = (size_t)n * planes * h * w;
-    hipLaunchKernelGGL(nchw_to_c8_kernel, dim3(ew_grid(tot)), dim3(256), 0, st, x, (float *)m->ws[0], n, l.cout, h * w,
+    hipLaunchKernelGGL(nchw_to_c8_kernel, dim3(ew_grid(tot)), dim3(256), 0, st, x, (float *)m->ws[0].p, n, l.cout, h * w,
                        planes);
     HIP_TRY(hipGetLastError());
-    LayerArgs a{};
-    a.in = (const float *)m->ws[0];
-    a.out = y;
-    a.gp = l.gp;
-    a.beta = l.beta;
-    a.N = n;
-    a.H = h;
-    a.W = w;
-    a.OH = h;
-    a.OW = w;
-    a.in_planes = planes;
-    a.out_planes = planes;
-    a.cout = l.cout;
-    a.outfmt = OUT_NCHW;
-    a.zero = m->zero;
-    a.medians = m->zero;
+    LayerArgs a = layer_args(m, (const float *)m->ws[0].p, planes, y, n, h, w, h, w, l.ct, l.cout, OUT_NCHW, 0, nullptr);
+    a.gp = l.gp.get<float>();
+    a.beta = l.beta.get<float>();
     return launch_gdn(l.ct, track == CAE_SYNTHESIS, a, st);
 }
 
@@ -1500,7 +1066,7 @@ int cae_quantize(cae_model_t *mm, const float *latents, int n, int hw, int32_t *
     }
     const size_t total = (size_t)n * m->c_bn * hw;
     hipLaunchKernelGGL(quantize_kernel, dim3(ew_grid(total)), dim3(256), 0, (hipStream_t)stream, latents,
-                       m->medians_dev, symbols, m->c_bn, hw, total);
+                       m->medians_dev.get<float>(), symbols, m->c_bn, hw, total);
     HIP_TRY(hipGetLastError());
     return CAE_OK;
 }
@@ -1580,18 +1146,15 @@ int cae_likelihood(cae_model_t *mm, const float *latents, int n, int hw, float *
     if (rc) return rc;
     double *part = nullptr;
     if (bits) {
-        const size_t need = (size_t)n * m->c_bn;
-        if (m->bits_ws_elems < need) {
+        const size_t need = (size_t)n * m->c_bn * sizeof(double);
+        if (m->bits_ws.bytes < need) {
             if (m->bits_ws) {
                 HIP_TRY(hipDeviceSynchronize());
-                (void)hipFree(m->bits_ws);
-                m->bits_ws = nullptr;
-                m->bits_ws_elems = 0;
+                m->bits_ws.reset();
             }
-            HIP_TRY(hipMalloc((void **)&m->bits_ws, need * sizeof(double)));
-            m->bits_ws_elems = need;
+            CAE_TRY(m->bits_ws.alloc(need));
         }
-        part = m->bits_ws;
+        part = m->bits_ws.get<double>();
     }
     switch (m->density_r) {
         case 1: launch_likelihood<1>(m, latents, n, hw, y_hat, likelihood, part, st); break;
@@ -1630,10 +1193,10 @@ int cae_quantize_export(cae_model_t *mm, const float *latents, int n, int hw, in
         const size_t total4 = total / 4;
         const unsigned blocks = (unsigned)std::min<size_t>((total4 + 1023) / 1024, (size_t)cap);
         hipLaunchKernelGGL(quantize_export4_kernel, dim3(blocks), dim3(1024), 0, (hipStream_t)stream, latents,
-                           m->medians_dev, symbols_host, m->c_bn, hw / 4, total4);
+                           m->medians_dev.get<float>(), symbols_host, m->c_bn, hw / 4, total4);
     } else {
         const unsigned blocks = (unsigned)std::min<size_t>((total + 1023) / 1024, (size_t)cap);
-        hipLaunchKernelGGL(quantize_kernel, dim3(blocks), dim3(1024), 0, (hipStream_t)stream, latents, m->medians_dev,
+        hipLaunchKernelGGL(quantize_kernel, dim3(blocks), dim3(1024), 0, (hipStream_t)stream, latents, m->medians_dev.get<float>(),
                            symbols_host, m->c_bn, hw, total);
     }
     HIP_TRY(hipGetLastError());
@@ -1652,7 +1215,7 @@ int cae_dequantize(cae_model_t *mm, const int32_t *symbols, int n, int hw, float
     }
     const size_t total = (size_t)n * m->c_bn * hw;
     hipLaunchKernelGGL(dequantize_kernel, dim3(ew_grid(total)), dim3(256), 0, (hipStream_t)stream, symbols,
-                       m->medians_dev, latents, m->c_bn, hw, total);
+                       m->medians_dev.get<float>(), latents, m->c_bn, hw, total);
     HIP_TRY(hipGetLastError());
     return CAE_OK;
 }

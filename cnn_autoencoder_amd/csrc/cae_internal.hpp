@@ -11,22 +11,59 @@ namespace cae {
 
 int fail(int code, const char *fmt, ...);
 
+// hipFree; defined with the HIP half of the library (cae_api.hip) so that this header needs no HIP include
+void dev_free(void *p);
+
+// Owner of one device allocation: move-only, frees in its destructor.
+struct DevBuf {
+    void *p = nullptr;
+    size_t bytes = 0;
+    DevBuf() = default;
+    DevBuf(DevBuf &&o) noexcept : p(o.p), bytes(o.bytes) {
+        o.p = nullptr;
+        o.bytes = 0;
+    }
+    DevBuf &operator=(DevBuf &&o) noexcept {
+        if (this != &o) {
+            reset();
+            std::swap(p, o.p);
+            std::swap(bytes, o.bytes);
+        }
+        return *this;
+    }
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf() { reset(); }
+    void reset() {
+        if (p) dev_free(p);
+        p = nullptr;
+        bytes = 0;
+    }
+    explicit operator bool() const { return p != nullptr; }
+    template <class T>
+    T *get() const { return static_cast<T *>(p); }
+    int alloc(size_t n);                    // a fresh, uninitialised allocation of n bytes (frees the previous one first)
+    int upload(const void *src, size_t n);  // a fresh allocation holding a copy of src[0..n) (blocking)
+    template <class T>
+    int upload(const std::vector<T> &v) { return upload(v.data(), v.size() * sizeof(T)); }
+};
+
 struct Layer {
     bool set = false;
     int cin = 0, cout = 0, ct = 0, chunks = 0;
     bool gdn = false;
-    float *wp = nullptr;    // packed weights (device)
-    float *bias = nullptr;  // [ct*32] (device) or null
-    float *gp = nullptr;    // packed gamma (device)
-    float *beta = nullptr;  // [ct*32] (device)
-    float *wp_edge = nullptr;  // packed weights of the specialised first-conv / last-deconv kernel, or null
+    DevBuf wp;       // packed weights
+    DevBuf bias;     // [ct*32] or null
+    DevBuf gp;       // packed gamma
+    DevBuf beta;     // [ct*32]
+    DevBuf wp_edge;  // packed weights of the specialised first-conv / last-deconv kernel, or null
     // LeakyReLU / ReLU units: stride-1 convolution (cin -> cin) + activation in front of the strided one
     // stride-1 (transposed) convolutions cin -> cin in front of the strided layer: the pre-convolution of the
     // LeakyReLU / ReLU units and the res_model of the residual units (_autoencoders.py:62-76, :104-174, :230-304)
     struct Stage {
-        float *wp = nullptr, *bias = nullptr, *gp = nullptr, *beta = nullptr;
-        void *wp16 = nullptr;  // f16x3 path: packed hi/lo weights
-        void *gp16 = nullptr;  // f16x3 path: packed hi/lo gamma (GDN / IGDN stages of residual units)
+        DevBuf wp, bias, gp, beta;
+        DevBuf wp16;           // f16x3 path: packed hi/lo weights
+        DevBuf gp16;           // f16x3 path: packed hi/lo gamma (GDN / IGDN stages of residual units)
         bool gdn = false;      // GDN (analysis) / IGDN (synthesis) after the convolution, else `act`
         int act = 0;
         bool add_res = false;  // + the unit's input after the activation (residual units)
@@ -34,16 +71,16 @@ struct Layer {
     };
     std::vector<Stage> stages;
     // multiscale colour layer on this synthesis level's output (stride-1 reflect conv to the image channels), or null
-    float *color_wp = nullptr;
-    float *color_bias = nullptr;
-    void *color_wp16 = nullptr;  // f16x3 path: packed hi/lo weights of the colour layer
-    float *color_w4 = nullptr;   // colour layer from <= 128 to <= 4 channels: weights of color_small_kernel (both paths)
+    DevBuf color_wp;
+    DevBuf color_bias;
+    DevBuf color_wp16;  // f16x3 path: packed hi/lo weights of the colour layer
+    DevBuf color_w4;    // colour layer from <= 128 to <= 4 channels: weights of color_small_kernel (both paths)
     int color_cout = 0;
     int act = 0;               // activation after the pre-convolution and after this layer (0 none, 1 LeakyReLU, 2 ReLU)
-    void *wp16 = nullptr;      // f16x3 path: packed hi/lo weights
-    void *gp16 = nullptr;      // f16x3 path: packed hi/lo gamma
-    void *wp_edge16 = nullptr; // f16x3 path: packed weights of the first-conv / last-deconv kernel
-    void *wp_pmap16 = nullptr; // f16x3 path, last synthesis layer (k = 3, cout <= 3): its weights as the product map
+    DevBuf wp16;               // f16x3 path: packed hi/lo weights
+    DevBuf gp16;               // f16x3 path: packed hi/lo gamma
+    DevBuf wp_edge16;          // f16x3 path: packed weights of the first-conv / last-deconv kernel
+    DevBuf wp_pmap16;          // f16x3 path, last synthesis layer (k = 3, cout <= 3): its weights as the product map
     bool f16_bad = false;      // a weight / gamma entry is not finite in f16: the model runs on the fp32 kernels
 };
 
@@ -77,7 +114,7 @@ int rans_decode_chunk_pair(const EntropyTables &T, const uint8_t *const *bufs, c
 
 // Device copy of EntropyTables for the device coder (cae_rans_device.hip): one buffer, byte offsets of its parts.
 struct DevEntropy {
-    void *buf = nullptr;
+    DevBuf buf;
     uint64_t version = 0;  // Model::ent_version it was uploaded from
     size_t enc = 0, cdf = 0, lut = 0, len = 0, off = 0;
 };
@@ -89,25 +126,21 @@ struct Model {
     uint64_t ent_version = 0;  // bumped by every cae_model_set_entropy
     DevEntropy ent_dev;
     int ensure_ent_device();   // (under `mu`)
-    float *medians_dev = nullptr;
+    DevBuf medians_dev;
     bool medians_dirty = false;
     // factorized density network (cae_model_set_density): effective parameters, uniform width
     std::vector<float> density;
     int density_r = 0, density_k = 0, density_per_channel = 0;
     float density_bound = 0.f;
     int likelihood_plain = 1;  // cae_model_set_likelihood_form
-    float *density_dev = nullptr;
+    DevBuf density_dev;
     bool density_dirty = false;
-    double *bits_ws = nullptr;
-    size_t bits_ws_elems = 0;
-    float *zero = nullptr;
-    void *ws[4] = {nullptr, nullptr, nullptr, nullptr};  // converted input + three activation buffers
-    size_t ws_bytes[4] = {0, 0, 0, 0};
+    DevBuf bits_ws;  // [n * c_bn] doubles (cae_likelihood)
+    DevBuf zero;
+    DevBuf ws[4];    // converted input + three activation buffers
     std::mutex mu;
     // profiling: per track, per profiled call, the event pairs of every launched kernel
     int precision = 0;  // 0 = fp32 MFMA, 1 = f16x3 split MFMA
-    void *ws16[2] = {nullptr, nullptr};
-    size_t ws16_bytes[2] = {0, 0};
     bool profiling = false;
     std::vector<std::vector<std::pair<void *, void *>>> prof[2];
     // f16x3 range guard: ring of overflow words in pinned host memory (device-visible), one per call (ticket % kFlagSlots)

@@ -6,8 +6,8 @@
 #include "cae_kernels.hpp"
 namespace cae {
 template <int KS, int CT, bool GDN>
-static int launch_deconv_t(const LayerArgs &a, hipStream_t st) {
-    constexpr int NW = DECONV_NW;
+static int launch_deconv_t(int cin, const LayerArgs &args, hipStream_t st) {
+    constexpr int NW = 4;  // waves per block of deconv_s2_kernel; its tile is 32 x NW input pixels, its chunk 8 channels
     constexpr int P = KS / 2;
     constexpr int WH = 32 + (KS - 1 - P) / 2 + (P + 1) / 2;
     constexpr int HALO_INSTR = (NW * WH * 2 + 63) / 64;
@@ -16,6 +16,7 @@ static int launch_deconv_t(const LayerArgs &a, hipStream_t st) {
     constexpr int LDS = 2 * (CONV_STAGE > G_BYTES ? CONV_STAGE : G_BYTES);
     auto kern = deconv_s2_kernel<KS, CT, NW, GDN>;
     CAE_TRY(ensure_lds((const void *)kern, LDS));
+    const LayerArgs a = with_launch_facts(args, args.W, args.H, 32, NW, (cin + 7) / 8);
     const unsigned grid = (unsigned)((size_t)a.N * a.tiles_x * a.tiles_y);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(NW * 64), LDS, st, a);
     HIP_TRY(hipGetLastError());
@@ -24,14 +25,14 @@ static int launch_deconv_t(const LayerArgs &a, hipStream_t st) {
 
 #define DISPATCH_CT(FN, KS_, GDN_)                                               \
     switch (ct) {                                                                \
-        case 1: return FN<KS_, 1, GDN_>(a, st);                                  \
-        case 2: return FN<KS_, 2, GDN_>(a, st);                                  \
-        case 4: return FN<KS_, 4, GDN_>(a, st);                                  \
-        case 6: return FN<KS_, 6, GDN_>(a, st);                                  \
+        case 1: return FN<KS_, 1, GDN_>(cin, a, st);                             \
+        case 2: return FN<KS_, 2, GDN_>(cin, a, st);                             \
+        case 4: return FN<KS_, 4, GDN_>(cin, a, st);                             \
+        case 6: return FN<KS_, 6, GDN_>(cin, a, st);                             \
         default: return fail(CAE_ERR_UNSUPPORTED, "unsupported channel tiles %d", ct); \
     }
 
-int launch_deconv_k5(int ct, bool gdn, const LayerArgs &a, hipStream_t st) {
+int launch_deconv_k5(int ct, bool gdn, int cin, const LayerArgs &a, hipStream_t st) {
     if (gdn) { DISPATCH_CT(launch_deconv_t, 5, true) } else { DISPATCH_CT(launch_deconv_t, 5, false) }
 }
 

@@ -6,12 +6,13 @@
 #include "cae_kernels.hpp"
 namespace cae {
 template <int KS, int CT, bool GDN>
-static int launch_first_t(const LayerArgs &a, const FirstArgs &f, hipStream_t st) {
-    constexpr int NW = 4;
+static int launch_first_t(const LayerArgs &args, const FirstArgs &f, hipStream_t st) {
+    constexpr int NW = 4;  // conv_first_kernel: tiles of 16 x 2 NW output pixels
     constexpr int WH = 2 * 16 + KS - 2, HH = 4 * NW + KS - 2;
     constexpr int LDS = 2 * (GDN ? CT * 4096 : 0) + KS * KS * CT * 512 + ((HH * WH * 16 + 1023) / 1024) * 1024 + 1024;
     auto kern = conv_first_kernel<KS, CT, NW, GDN>;
     CAE_TRY(ensure_lds((const void *)kern, LDS));
+    const LayerArgs a = with_launch_facts(args, args.OW, args.OH, 16, 2 * NW, (f.cin + 7) / 8);
     const unsigned grid = (unsigned)((size_t)a.N * a.tiles_x * a.tiles_y);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(NW * 64), LDS, st, a, f);
     HIP_TRY(hipGetLastError());
@@ -19,11 +20,12 @@ static int launch_first_t(const LayerArgs &a, const FirstArgs &f, hipStream_t st
 }
 
 template <int KS>
-static int launch_last_t(const LayerArgs &a, hipStream_t st) {
-    constexpr int NW = 4;
+static int launch_last_t(int cin, const LayerArgs &args, hipStream_t st) {
+    constexpr int NW = 4;  // deconv_last_kernel: tiles of 64 x NW input pixels, 16-channel contraction groups
     constexpr int P = KS / 2;
     constexpr int NB = (KS - 1 - P) / 2 + (P + 1) / 2 + 1;
     constexpr int HALO_INSTR = (4 * (NW + NB - 1) * (64 + NB - 1) + 63) / 64;
+    const LayerArgs a = with_launch_facts(args, args.W, args.H, 64, NW, (cin + 15) / 16);
     const int lds = 2 * HALO_INSTR * 1024 + NB * NB * a.cci * 1024;
     auto kern = deconv_last_kernel<KS, NW>;
     CAE_TRY(ensure_lds((const void *)kern, 160 * 1024));
@@ -63,9 +65,9 @@ int launch_first(int ks, int ct, bool gdn, const LayerArgs &a, const FirstArgs &
     return fail(CAE_ERR_UNSUPPORTED, "kernel_size %d not supported (3 or 5)", ks);
 }
 
-int launch_last(int ks, const LayerArgs &a, hipStream_t st) {
-    if (ks == 3) return launch_last_t<3>(a, st);
-    if (ks == 5) return launch_last_t<5>(a, st);
+int launch_last(int ks, int cin, const LayerArgs &a, hipStream_t st) {
+    if (ks == 3) return launch_last_t<3>(cin, a, st);
+    if (ks == 5) return launch_last_t<5>(cin, a, st);
     return fail(CAE_ERR_UNSUPPORTED, "kernel_size %d not supported (3 or 5)", ks);
 }
 

@@ -20,9 +20,7 @@ static int launch_first_f16_t(const LayerArgs &a, const FirstArgs &f, hipStream_
         CAE_TRY(ensure_lds((const void *)kern_u8, LDS));
         CAE_TRY(ensure_lds((const void *)kern_f32, LDS));
         CAE_TRY(device_cus(n_cu));
-        LayerArgs b = a;
-        b.tiles_x = (a.OW + G::TX - 1) / G::TX;
-        b.tiles_y = (a.OH + G::TY - 1) / G::TY;
+        const LayerArgs b = with_launch_facts(a, a.OW, a.OH, G::TX, G::TY, (f.cin + 7) / 8);
         const size_t total = (size_t)b.N * b.tiles_x * b.tiles_y;
         if (total > 0x7fffffff) return fail(CAE_ERR_ARG, "batch too large");
         // persistent: one block per CU walks over the tiles
@@ -73,18 +71,28 @@ int launch_gdn_f16(int ct, bool inverse, const LayerArgs &a, hipStream_t st) {
     return fail(CAE_ERR_UNSUPPORTED, "stand-alone GDN is built for 192-channel layers (channel tiles %d)", ct);
 }
 
-template <int KS, int NW, int DEPTH>
-static int launch_last_f16_t(const LayerArgs &a, hipStream_t st) {
-    using G = LastGeomF16<KS, NW, DEPTH>;
-    const int lds = G::lds_bytes(a.cci);
+// deconv_last_f16_kernel as it is built per kernel size: <3, 8, 3>: 3 x 40 KiB ring + 32 KiB weights (128 channels);
+// <5, 4, 2>: 3x3 neighbours, 72 KiB of weights, shallower ring.  Halo ring + all weights resident: a last layer with
+// more than 160 input channels does not fit
+using LastF16K3 = LastGeomF16<3, 8, 3>;
+using LastF16K5 = LastGeomF16<5, 4, 2>;
+
+bool last_f16_fits(int ks, int cin) {
+    const int nq = (cin + 31) / 32;
+    return (ks == 3 ? LastF16K3::lds_bytes(nq) : LastF16K5::lds_bytes(nq)) <= 160 * 1024;
+}
+
+template <int KS, class G>
+static int launch_last_f16_t(int cin, const LayerArgs &a, hipStream_t st) {
+    constexpr int NW = G::NW, DEPTH = G::DEPTH;
+    // tiles of TXC x NW input pixels, 32-channel contraction groups
+    const LayerArgs b = with_launch_facts(a, a.W, a.H, G::TXC, NW, (cin + 31) / 32);
+    const int lds = G::lds_bytes(b.cci);
     if (lds > 160 * 1024) return fail(CAE_ERR_UNSUPPORTED, "last-layer weights do not fit the LDS");
     auto kern = deconv_last_f16_kernel<KS, NW, DEPTH>;
     int n_cu = 0;
     CAE_TRY(ensure_lds((const void *)kern, 160 * 1024));
     CAE_TRY(device_cus(n_cu));
-    LayerArgs b = a;
-    b.tiles_x = (a.W + G::TXC - 1) / G::TXC;
-    b.tiles_y = (a.H + NW - 1) / NW;
     const size_t total = (size_t)b.N * b.tiles_x * b.tiles_y;
     if (total > 0x7fffffff) return fail(CAE_ERR_ARG, "batch too large");
     const unsigned grid = (unsigned)std::min<size_t>(total, (size_t)std::max(n_cu, 1));  // persistent
@@ -93,9 +101,9 @@ static int launch_last_f16_t(const LayerArgs &a, hipStream_t st) {
     return CAE_OK;
 }
 
-int launch_last_f16(int ks, const LayerArgs &a, hipStream_t st) {
-    if (ks == 3) return launch_last_f16_t<3, 8, 3>(a, st);  // 3 x 40 KiB ring + 32 KiB weights (128 channels)
-    if (ks == 5) return launch_last_f16_t<5, 4, 2>(a, st);  // 3x3 neighbours: 72 KiB of weights, shallower ring
+int launch_last_f16(int ks, int cin, const LayerArgs &a, hipStream_t st) {
+    if (ks == 3) return launch_last_f16_t<3, LastF16K3>(cin, a, st);
+    if (ks == 5) return launch_last_f16_t<5, LastF16K5>(cin, a, st);
     return fail(CAE_ERR_UNSUPPORTED, "kernel_size %d not supported (3 or 5)", ks);
 }
 

@@ -460,18 +460,10 @@ int Model::ensure_ent_device() {
     memcpy(host.data() + d.lut, T.lut.data(), (C << kLutBits) * sizeof(uint16_t));
     memcpy(host.data() + d.len, T.len.data(), C * sizeof(int32_t));
     memcpy(host.data() + d.off, T.off.data(), C * sizeof(int32_t));
-    HIP_TRY(hipMalloc(&d.buf, bytes));
-    const hipError_t e = hipMemcpy(d.buf, host.data(), bytes, hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        (void)hipFree(d.buf);
-        return fail(CAE_ERR_HIP, "hipMemcpy (coder tables): %s", hipGetErrorString(e));
-    }
-    if (ent_dev.buf) {
-        HIP_TRY(hipDeviceSynchronize());  // coder kernels may still read the previous tables
-        (void)hipFree(ent_dev.buf);
-    }
+    CAE_TRY(d.buf.upload(host.data(), bytes));
+    if (ent_dev.buf) HIP_TRY(hipDeviceSynchronize());  // coder kernels may still read the previous tables
     d.version = ent_version;
-    ent_dev = d;
+    ent_dev = std::move(d);  // (frees the previous buffer)
     return CAE_OK;
 }
 
@@ -519,7 +511,7 @@ int cae_rans_encode_device(cae_model_t *mm, const int32_t *symbols, int n, int h
     hipStream_t st = (hipStream_t)stream;
     unsigned char *ws = (unsigned char *)workspace;
     const DevEntropy &d = m->ent_dev;
-    const unsigned char *tb = (const unsigned char *)d.buf;
+    const unsigned char *tb = d.buf.get<unsigned char>();
     const EncSym *enc = (const EncSym *)(tb + d.enc);
     const int32_t *len = (const int32_t *)(tb + d.len), *off = (const int32_t *)(tb + d.off);
     int64_t *part_steps = (int64_t *)(ws + L.steps), *cap_off = (int64_t *)(ws + L.cap_off), *lens = (int64_t *)(ws + L.lens);
@@ -556,7 +548,7 @@ int cae_rans_decode_device(cae_model_t *mm, const uint8_t *bytes, size_t bytes_l
     const int C = m->ent.channels, S = m->ent.stride;
     CAE_TRY(m->ensure_ent_device());
     const DevEntropy &d = m->ent_dev;
-    const unsigned char *tb = (const unsigned char *)d.buf;
+    const unsigned char *tb = d.buf.get<unsigned char>();
     const int dec_lds = kStage * (int)sizeof(int32_t) + ((int)sizeof(uint16_t) << kLutBits) + S * (int)sizeof(int32_t);
     CAE_TRY(ensure_lds((const void *)rans_decode_kernel, dec_lds));
     hipLaunchKernelGGL(rans_decode_kernel, dim3((n + kLanes - 1) / kLanes), dim3(kLanes), dec_lds, (hipStream_t)stream,

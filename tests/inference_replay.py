@@ -3,7 +3,7 @@
 A unit is replayed from the GPU's own input to it: the tile, an analysis level (cae_analysis_levels) or a synthesis
 bridge.  On the f16x3 path that input is exactly hi + lo of the stored split value, so the host re-splits it with
 numpy's round-to-nearest-even float16 conversion (xh = f16(v), xl = f16(v - xh): what the kernels do to a float tile,
-and exactly (hi, lo) for a stored value).  Weights and gamma are split the way split_half does it (csrc/cae_api.hip).
+and exactly (hi, lo) for a stored value).  Weights and gamma are split the way pack_split does it (csrc/cae_pack.cpp).
 
 Bounds, per element:
   * a convolution whose input the kernel read exactly as given (fp32 path: op(x, w); f16x3: op(xh, wh) + op(xh, wl) +
@@ -142,8 +142,8 @@ def stages_need_fp32(cin, stages):
 
 
 def conv_main_on_fp32(ks, cout, synthesis):
-    """csrc/cae_api.hip conv_f16_fits false: the analysis layer runs on the exact-fp32 kernel (the k = 5, 192-channel
-    detour); the transposed convolutions always have a split-f16 kernel"""
+    """csrc/cae_launch_conv_f16.hip conv_f16_fits false: the analysis layer runs on the exact-fp32 kernel (the k = 5,
+    192-channel detour); the transposed convolutions always have a split-f16 kernel"""
     if synthesis:
         return False
     ct = _round_ct(cout)

@@ -27,6 +27,7 @@ int fail(int code, const char *fmt, ...) {
 }
 // (the device half of the handle is not part of this build: a host-only Model never owns device memory)
 Model::~Model() {}
+void dev_free(void *) {}
 }  // namespace cae
 extern "C" const char *cae_last_error(void) { return cae::g_err.c_str(); }
 
