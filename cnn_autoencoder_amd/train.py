@@ -5,8 +5,8 @@ What the reference's training step does (``src/train_cae_ms.py:189-262``) and wh
 * ``forward_func`` (``models/tasks/_taskutils.py:95-108``): encoder -> fact_ent (train mode: additive U(-1/2, 1/2)
   noise) -> decoder.  ``Analyzer.forward`` / ``Synthesizer.forward`` switch to the differentiable track functions of
   this module whenever autograd is recording: bf16 convolutions with fp32 accumulation
-  (``cae_t_conv_forward`` / ``cae_t_deconv_forward``), fp32 GDN / IGDN (``cae_t_gdn_forward``), and hand-written
-  backward kernels (data gradients, weight gradients, GDN gradient) instead of ATen / cuDNN autograd.
+  (``cae_t_conv_forward_act`` / ``cae_t_deconv_forward_act``), fp32 GDN / IGDN (``cae_t_gdn_forward_save``), and
+  hand-written backward kernels (data gradients, weight gradients, GDN gradient) instead of ATen / cuDNN autograd.
 * ``GeneralLoss`` (``models/criteria/_lossutils.py:54-109``): ``criteria.GeneralLoss`` (scalar reductions, torch ops).
 * compressai's ``NonNegativeParametrizer`` / ``LowerBound`` gradient rule of the GDN parameters: the kernels
   differentiate with respect to the EFFECTIVE beta / gamma, the reparametrisation stays a torch autograd graph
@@ -25,11 +25,17 @@ statistics updated as ``nn.BatchNorm2d`` does), grouped layers (dense kernels on
 grouped weight) and ``Dropout2d``.  Multiscale colour layers (``multiscale_analysis``, _autoencoders.py:417-452) train
 on both forms: inside ``SynthesisFn`` (their data gradient summed with the next unit's before the level's IGDN / activation
 backward) and as ``_ColourFn`` behind the units of a composed track; ``criteria.DistMSEPyramidLoss`` scores them.
+
+The host layer, top down: ONE launch wrapper per ``cae_t_*`` entry point, its only call site (tensors and the few real
+choices in; every integer derived from tensor shapes, a convolution's channel counts and kernel size from the packed weight
+of ``_pack``; outputs allocated and returned); the steps, each written once (``_conv_s1_forward`` / ``_conv_s1_backward``,
+``_conv_s2_backward``, ``_layer_forward``, ``_hand_down``); the autograd functions of the fused and the composed tracks as
+drivers over the steps.
 """
 from __future__ import annotations
 
 import ctypes
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import os
 
@@ -37,6 +43,8 @@ import torch
 import torch.nn as nn
 
 from . import _lib
+
+BF16, F32, F64 = torch.bfloat16, torch.float32, torch.float64
 
 
 def _pad32(c: int) -> int:
@@ -55,6 +63,10 @@ def _st():
     return _lib.stream_ptr()
 
 
+def _new(ref: torch.Tensor, shape, dtype) -> torch.Tensor:
+    return torch.empty(shape, dtype=dtype, device=ref.device)
+
+
 class LayerSpec:
     """Static description of one unit for the track functions."""
 
@@ -71,69 +83,31 @@ class LayerSpec:
         return (1 + int(self.has_bias)) * (1 + int(self.has_pre)) + 2 * int(self.has_gdn)
 
 
-def _pack(weight: torch.Tensor, contract_dim: int, ks: int) -> torch.Tensor:
-    """fp32 (d0, d1, k, k) -> bf16 MFMA B fragments on the device (cae_t_pack_weights)."""
-    d0, d1 = weight.shape[0], weight.shape[1]
-    kc, nc = (d0, d1) if contract_dim == 0 else (d1, d0)
-    nbytes = _L().cae_t_packed_bytes(kc, nc, ks)
-    out = torch.empty(nbytes // 2, dtype=torch.bfloat16, device=weight.device)
-    w = weight.detach().float().contiguous()
-    _lib.check(_L().cae_t_pack_weights(w.data_ptr(), d0, d1, ks, contract_dim, out.data_ptr(), _st()))
-    return out
+class ColourSpec:
+    """One multiscale colour layer: Conv2d(cin -> cout, ks, stride 1, reflect padding ks//2) (_autoencoders.py:417-428)."""
+
+    def __init__(self, cin: int, cout: int, ks: int, has_bias: bool):
+        self.cin, self.cout, self.ks, self.has_bias = int(cin), int(cout), int(ks), bool(has_bias)
+        self.cin_p = _pad32(cin)
+        self.K = self.ks * self.ks * self.cout  # GEMM columns (tap, channel) of the edge form
+        self.kp = _pad32(self.K)
+
+    @property
+    def n_tensors(self) -> int:
+        return 1 + int(self.has_bias)
 
 
 def _split_params(specs: Sequence[LayerSpec], tensors: Sequence[torch.Tensor]):
     """-> per layer (w, b, beta, gamma, pre_w, pre_b); flat order: [pre_w, pre_b?]? w, b?, [beta, gamma]?"""
-    out, k = [], 0
+    out, it = [], iter(tensors)
     for s in specs:
-        pw = pb = None
-        if s.has_pre:
-            pw = tensors[k]
-            k += 1
-            if s.has_bias:
-                pb = tensors[k]
-                k += 1
-        w = tensors[k]
-        k += 1
-        b = beta = gamma = None
-        if s.has_bias:
-            b = tensors[k]
-            k += 1
-        if s.has_gdn:
-            beta, gamma = tensors[k], tensors[k + 1]
-            k += 2
+        pw = next(it) if s.has_pre else None
+        pb = next(it) if s.has_pre and s.has_bias else None
+        w = next(it)
+        b = next(it) if s.has_bias else None
+        beta, gamma = (next(it), next(it)) if s.has_gdn else (None, None)
         out.append((w, b, beta, gamma, pw, pb))
     return out
-
-
-def _bias_p(b: Optional[torch.Tensor], cp: int, dev) -> Optional[torch.Tensor]:
-    if b is None:
-        return None
-    out = torch.zeros(cp, dtype=torch.float32, device=dev)
-    out[:b.numel()] = b.detach().float()
-    return out
-
-
-def _edge_ok(spec: 'LayerSpec', c_img: int) -> bool:
-    """the 3-channel edge of a track as a pointwise GEMM over K = (tap, channel) <= 32 (cae_t_im2col_s2 / cae_t_col2im_s2):
-    no stride-1 pre-convolution at that edge, k^2 * channels fits one 32-deep chunk; CAE_EDGE_GEMM=0 keeps the padded form"""
-    return (not spec.has_pre and spec.ks * spec.ks * c_img <= 32 and os.environ.get('CAE_EDGE_GEMM', '1') != '0')
-
-
-def _act_backward(g16, gext32, pad, y16, act):
-    """gradient through LeakyReLU / ReLU: g * (y > 0 ? 1 : slope), y = the activation's output; g bf16, or the fp32
-    extended-domain gradient (folded in place first) -> bf16"""
-    n, h, w, cp = y16.shape
-    out = torch.empty_like(y16)
-    _lib.check(_L().cae_t_act_backward(_ptr(g16), _ptr(gext32), pad, y16.data_ptr(), n, h, w, cp, act, out.data_ptr(), _st()))
-    return out
-
-
-def _colsum(g16, c):
-    n, h, w, cp = g16.shape
-    gb = torch.empty(cp, dtype=torch.float32, device=g16.device)
-    _lib.check(_L().cae_t_colsum(g16.data_ptr(), n * h * w, cp, gb.data_ptr(), _st()))
-    return gb[:c].clone()
 
 
 def _flat_grads(specs, per_layer):
@@ -152,19 +126,293 @@ def _flat_grads(specs, per_layer):
     return out
 
 
+def _split_colour(colour, tensors):
+    """flat colour tensors -> per level (w, b | None)"""
+    out, k = [], 0
+    for cs in colour:
+        out.append((tensors[k], tensors[k + 1] if cs.has_bias else None))
+        k += cs.n_tensors
+    return out
+
+
+def _detached(layers):
+    return [tuple(t.detach() if t is not None else None for t in l) for l in layers]
+
+
+# ---- weights as the kernels read them ---------------------------------------------------------------------------------
+
+def _pack(weight: torch.Tensor, contract_dim: int, ks: int) -> torch.Tensor:
+    """fp32 (d0, d1, k, k) -> bf16 MFMA B fragments on the device (cae_t_pack_weights), shaped [k*k][kc_p][nc_p] (kc the
+    contracted, nc the produced channels, padded to 32: the element count; the order inside is the kernels' own).  The
+    launch wrappers read the kernel size and both channel counts of a convolution from this shape."""
+    d0, d1 = weight.shape[0], weight.shape[1]
+    kc, nc = (d0, d1) if contract_dim == 0 else (d1, d0)
+    out = torch.empty((ks * ks, _pad32(kc), _pad32(nc)), dtype=BF16, device=weight.device)
+    if _L().cae_t_packed_bytes(kc, nc, ks) != 2 * out.numel():
+        raise ValueError(f'packed size of a ({d0}, {d1}, {ks}, {ks}) weight is not that of {tuple(out.shape)} bf16')
+    w = weight.detach().float().contiguous()
+    _lib.check(_L().cae_t_pack_weights(w.data_ptr(), d0, d1, ks, contract_dim, out.data_ptr(), _st()))
+    return out
+
+
+def _packed_dims(wp: torch.Tensor, contracted: int):
+    """-> (ks, produced padded channels) of a packed weight that must contract over `contracted` padded channels"""
+    kk, kc_p, nc_p = wp.shape
+    ks = int(round(kk ** 0.5))
+    if kc_p != contracted or ks * ks != kk:
+        raise ValueError(f'packed weight {tuple(wp.shape)} does not contract over {contracted} channels')
+    return ks, nc_p
+
+
+def _bias_p(b: Optional[torch.Tensor], cp: int, dev) -> Optional[torch.Tensor]:
+    if b is None:
+        return None
+    out = torch.zeros(cp, dtype=F32, device=dev)
+    out[:b.numel()] = b.detach().float()
+    return out
+
+
+def _pack_bias(w: torch.Tensor, b: Optional[torch.Tensor], contract_dim: int, ks: int):
+    """-> (packed weight, bias padded to its produced channels | None)"""
+    wp = _pack(w, contract_dim, ks)
+    return wp, _bias_p(b, wp.shape[2], w.device)
+
+
+def _edge_ok(spec: 'LayerSpec', c_img: int) -> bool:
+    """the 3-channel edge of a track as a pointwise GEMM over K = (tap, channel) <= 32 (cae_t_im2col_s2 / cae_t_col2im_s2):
+    no stride-1 pre-convolution at that edge, k^2 * channels fits one 32-deep chunk; CAE_EDGE_GEMM=0 keeps the padded form"""
+    return (not spec.has_pre and spec.ks * spec.ks * c_img <= 32 and os.environ.get('CAE_EDGE_GEMM', '1') != '0')
+
+
+def _colour_edge(cs: ColourSpec) -> bool:
+    """the colour layer as a pointwise GEMM over K = (tap, channel) <= 96 (cae_t_col2im_s1r / cae_t_im2col_s1r); else, or with
+    CAE_EDGE_GEMM=0, the padded stride-1 form on the convolution kernels (cae_t_corr_s1 / cae_t_wgrad_s1)"""
+    return cs.cout <= 3 and cs.kp <= 96 and os.environ.get('CAE_EDGE_GEMM', '1') != '0'
+
+
+def _pack_1x1(m: torch.Tensor, rows: int, cols: int, again_at: Optional[int] = None) -> torch.Tensor:
+    """the matrix m (produced, contracted), zero-padded to (rows, cols), as the packed weight of a 1 x 1 GEMM; again_at: a
+    second copy of m from that column on (the (hi, lo) halves of the colour layer's gradient columns)"""
+    w1 = torch.zeros((rows, cols, 1, 1), dtype=F32, device=m.device)
+    w1[:m.shape[0], :m.shape[1], 0, 0] = m
+    if again_at is not None:
+        w1[:m.shape[0], again_at:again_at + m.shape[1], 0, 0] = m
+    return _pack(w1, 1, 1)
+
+
+def _first_layer_1x1(wt: torch.Tensor, s: LayerSpec) -> torch.Tensor:
+    """analysis edge: (cout, cin, k, k) contracting over the im2col columns (tap, ci), 27 of 32"""
+    return _pack_1x1(wt.detach().float().permute(0, 2, 3, 1).reshape(s.cout, -1), s.cout, 32)
+
+
+def _last_layer_1x1(wt: torch.Tensor, s: LayerSpec, dgrad: bool) -> torch.Tensor:
+    """synthesis edge: (cin, cout, k, k) producing the col2im columns j = (tap, co) from the channels, or (dgrad) the
+    channels' gradient from the columns of the output gradient's im2col"""
+    K = s.ks * s.ks * s.cout
+    if dgrad:
+        return _pack_1x1(wt.detach().float().permute(0, 2, 3, 1).reshape(s.cin, K), s.cin, 32)
+    return _pack_1x1(wt.detach().float().permute(2, 3, 1, 0).reshape(K, s.cin), 32, s.cin)
+
+
+def _colour_1x1(wt: torch.Tensor, cs: ColourSpec, dgrad: bool) -> torch.Tensor:
+    """colour edge form: (cout, cin, k, k) producing the kp columns j = (tap, co), or (dgrad) the channels' gradient from
+    the 2 kp (hi, lo) gradient columns, the weights repeated over both halves"""
+    if dgrad:
+        return _pack_1x1(wt.detach().float().permute(1, 2, 3, 0).reshape(cs.cin, cs.K), cs.cin, 2 * cs.kp, again_at=cs.kp)
+    return _pack_1x1(wt.detach().float().permute(2, 3, 0, 1).reshape(cs.K, cs.cin), cs.kp, cs.cin)
+
+
+# ---- launch wrappers: one per cae_t_* entry point, every integer from tensor shapes -----------------------------------
+
 def _from_nchw(x: torch.Tensor, cp: int, want16=True, want32=False):
     n, c, h, w = x.shape
     x = x.detach().float().contiguous()
-    o16 = torch.empty((n, h, w, cp), dtype=torch.bfloat16, device=x.device) if want16 else None
-    o32 = torch.empty((n, h, w, cp), dtype=torch.float32, device=x.device) if want32 else None
+    o16 = _new(x, (n, h, w, cp), BF16) if want16 else None
+    o32 = _new(x, (n, h, w, cp), F32) if want32 else None
     _lib.check(_L().cae_t_from_nchw(x.data_ptr(), n, c, h, w, cp, _ptr(o16), _ptr(o32), _st()))
     return o16, o32
 
 
 def _to_nchw(t32: torch.Tensor, c: int) -> torch.Tensor:
     n, h, w, cp = t32.shape
-    out = torch.empty((n, c, h, w), dtype=torch.float32, device=t32.device)
+    out = _new(t32, (n, c, h, w), F32)
     _lib.check(_L().cae_t_to_nchw(t32.data_ptr(), n, c, h, w, cp, out.data_ptr(), _st()))
+    return out
+
+
+def _colsum(g16, c):
+    n, h, w, cp = g16.shape
+    gb = _new(g16, cp, F32)
+    _lib.check(_L().cae_t_colsum(g16.data_ptr(), n * h * w, cp, gb.data_ptr(), _st()))
+    return gb[:c].clone()
+
+
+def _act_backward(g16, gext32, pad, y16, act):
+    """gradient through LeakyReLU / ReLU: g * (y > 0 ? 1 : slope), y = the activation's output; g bf16, or the fp32
+    extended-domain gradient (folded in place first) -> bf16"""
+    n, h, w, cp = y16.shape
+    out = torch.empty_like(y16)
+    _lib.check(_L().cae_t_act_backward(_ptr(g16), _ptr(gext32), pad, y16.data_ptr(), n, h, w, cp, act, out.data_ptr(), _st()))
+    return out
+
+
+def _fold_to_bf16(t32: torch.Tensor, pad: int = 0) -> torch.Tensor:
+    """fp32 [n][h + 2 pad][w + 2 pad][cp], the reflect border folded onto the interior (in place) -> bf16 [n][h][w][cp];
+    pad 0: the plain rounding"""
+    n, hp, wp, cp = t32.shape
+    h, w = hp - 2 * pad, wp - 2 * pad
+    out = torch.empty_like(t32, dtype=BF16) if pad == 0 else _new(t32, (n, h, w, cp), BF16)
+    _lib.check(_L().cae_t_fold_to_bf16(t32.data_ptr(), n, h, w, pad, cp, out.data_ptr(), _st()))
+    return out
+
+
+def _fold_acc(gext32: torch.Tensor, pad: int, acc32: torch.Tensor) -> None:
+    """acc32 += the reflect fold of gext32 (extended by pad)"""
+    n, h, w, cp = acc32.shape
+    assert gext32.shape == (n, h + 2 * pad, w + 2 * pad, cp)
+    _lib.check(_L().cae_t_fold_acc(gext32.data_ptr(), n, h, w, pad, cp, acc32.data_ptr(), _st()))
+
+
+def _two_outputs(ref, shape, want32, want16):
+    return (_new(ref, shape, F32) if want32 else None), (_new(ref, shape, BF16) if want16 else None)
+
+
+def _conv_fwd(a16, wp, bias_p, act, want32):
+    """reflect convolution, stride 2 (+ bias): -> (fp32 output, None) or (None, bf16 output behind the activation)"""
+    n, h, w, cin_p = a16.shape
+    ks, cout_p = _packed_dims(wp, cin_p)
+    z32, z16 = _two_outputs(a16, (n, (h + 1) // 2, (w + 1) // 2, cout_p), want32, not want32)
+    _lib.check(_L().cae_t_conv_forward_act(a16.data_ptr(), n, h, w, cin_p, wp.data_ptr(), ks, _ptr(z32), _ptr(z16), cout_p,
+                                           _ptr(bias_p), act, _st()))
+    return z32, z16
+
+
+def _deconv_fwd(a16, wp, bias_p, act, want32):
+    """transposed convolution, stride 2 (+ bias): outputs as _conv_fwd"""
+    n, h, w, cin_p = a16.shape
+    ks, cout_p = _packed_dims(wp, cin_p)
+    z32, z16 = _two_outputs(a16, (n, 2 * h, 2 * w, cout_p), want32, not want32)
+    _lib.check(_L().cae_t_deconv_forward_act(a16.data_ptr(), n, h, w, cin_p, wp.data_ptr(), ks, _ptr(z32), _ptr(z16), cout_p,
+                                             _ptr(bias_p), act, _st()))
+    return z32, z16
+
+
+def _pointwise(a16, wp, bias_p, act, want32):
+    """1 x 1 GEMM over the channels (+ bias): outputs as _conv_fwd"""
+    n, h, w, cp = a16.shape
+    _, cn = _packed_dims(wp, cp)
+    o32, o16 = _two_outputs(a16, (n, h, w, cn), want32, not want32)
+    _lib.check(_L().cae_t_pointwise(a16.data_ptr(), n, h, w, cp, wp.data_ptr(), _ptr(o32), _ptr(o16), cn, _ptr(bias_p), act,
+                                    _st()))
+    return o32, o16
+
+
+def _pointwise_acc(a16, wp, acc32) -> None:
+    """acc32 += the 1 x 1 GEMM of a16"""
+    n, h, w, cp = a16.shape
+    _, cn = _packed_dims(wp, cp)
+    assert acc32.shape == (n, h, w, cn)
+    _lib.check(_L().cae_t_pointwise_acc(a16.data_ptr(), n, h, w, cp, wp.data_ptr(), acc32.data_ptr(), cn, _st()))
+
+
+def _corr_s1(a16, wp, mode, bias_p=None, act=0, want32=True, want16=False):
+    """stride-1 correlation.  mode 0: reflect convolution, 2: transposed convolution (padding k//2), 3: its data gradient,
+    1: the reflect convolution's data gradient on the EXTENDED domain (k//2 more on every side, to be folded).
+    -> (fp32 output | None, bf16 output behind the activation | None)"""
+    n, h, w, cp = a16.shape
+    ks, cn = _packed_dims(wp, cp)
+    ext = ks // 2 if mode == 1 else 0
+    o32, o16 = _two_outputs(a16, (n, h + 2 * ext, w + 2 * ext, cn), want32, want16)
+    _lib.check(_L().cae_t_corr_s1(a16.data_ptr(), n, h, w, cp, wp.data_ptr(), ks, mode, _ptr(o32), _ptr(o16), cn, _ptr(bias_p),
+                                  act, _st()))
+    return o32, o16
+
+
+def _wgrad(fine16, coarse16, ks, reflect):
+    """weight gradient of a stride-2 layer from its fine-resolution and coarse-resolution operands -> [k*k][c fine][c coarse];
+    reflect 1: the convolution (input fine, output gradient coarse), 0: the transposed one (output gradient fine)"""
+    n, h, w, cf = fine16.shape
+    _, oh, ow, cc = coarse16.shape
+    assert (oh, ow) == ((h + 1) // 2, (w + 1) // 2) and coarse16.shape[0] == n
+    gw = _new(fine16, (ks * ks, cf, cc), F32)
+    _lib.check(_L().cae_t_wgrad(fine16.data_ptr(), n, h, w, cf, coarse16.data_ptr(), oh, ow, cc, ks, reflect, gw.data_ptr(), _st()))
+    return gw
+
+
+def _wgrad_s1(a16, b16, ks, reflect):
+    """weight gradient of a stride-1 layer -> [k*k][ca][cb]; reflect 1: (input, output gradient) of the reflect convolution,
+    0: (output gradient, input) of the transposed one"""
+    n, h, w, ca = a16.shape
+    assert b16.shape[:3] == (n, h, w)
+    gw = _new(a16, (ks * ks, ca, b16.shape[3]), F32)
+    _lib.check(_L().cae_t_wgrad_s1(a16.data_ptr(), n, h, w, ca, b16.data_ptr(), b16.shape[3], ks, reflect, gw.data_ptr(), _st()))
+    return gw
+
+
+def _wgrad_pointwise(a16, g16):
+    """weight gradient of a 1 x 1 GEMM -> [1][ca][cg]"""
+    n, h, w, ca = a16.shape
+    assert g16.shape[:3] == (n, h, w)
+    gw = _new(a16, (1, ca, g16.shape[3]), F32)
+    _lib.check(_L().cae_t_wgrad_pointwise(a16.data_ptr(), g16.data_ptr(), n, h, w, ca, g16.shape[3], gw.data_ptr(), _st()))
+    return gw
+
+
+def _conv_dgrad_ext(g16, wp, hw):
+    """data gradient of the stride-2 reflect convolution of an h x w input, on the extended domain (fp32, to be folded)"""
+    n, oh, ow, cout_p = g16.shape
+    (h, w), (ks, cin_p) = hw, _packed_dims(wp, cout_p)
+    assert (oh, ow) == ((h + 1) // 2, (w + 1) // 2)
+    gext = _new(g16, (n, h + 2 * (ks // 2), w + 2 * (ks // 2), cin_p), F32)
+    _lib.check(_L().cae_t_conv_dgrad_ext(g16.data_ptr(), n, oh, ow, cout_p, wp.data_ptr(), ks, h, w, gext.data_ptr(), cin_p, _st()))
+    return gext
+
+
+def _deconv_dgrad(g16, wp, want32):
+    """data gradient of the stride-2 transposed convolution -> (fp32 | None, bf16 | None)"""
+    n, h2, w2, cout_p = g16.shape
+    ks, cin_p = _packed_dims(wp, cout_p)
+    gx32, gx16 = _two_outputs(g16, (n, h2 // 2, w2 // 2, cin_p), want32, not want32)
+    _lib.check(_L().cae_t_deconv_dgrad(g16.data_ptr(), n, h2 // 2, w2 // 2, cout_p, wp.data_ptr(), ks, _ptr(gx32), _ptr(gx16),
+                                       cin_p, _st()))
+    return gx32, gx16
+
+
+def _im2col_s2(x: torch.Tensor, ks: int, reflect: int) -> torch.Tensor:
+    """contiguous fp32 NCHW (n, c, h, w), k*k*c <= 32 -> bf16 columns [n][(h+1)/2][(w+1)/2][32] of its stride-2 windows (reflect
+    1: the image under the reflect convolution; 0: an output gradient under the transposed one, zeros outside)"""
+    n, c, h, w = x.shape
+    assert ks * ks * c <= 32
+    cols = _new(x, (n, (h + 1) // 2, (w + 1) // 2, 32), BF16)
+    _lib.check(_L().cae_t_im2col_s2(x.data_ptr(), n, c, h, w, (h + 1) // 2, (w + 1) // 2, ks, reflect, cols.data_ptr(), _st()))
+    return cols
+
+
+def _col2im_s2(u32, bias_c, cout, ks):
+    """fp32 columns [n][h][w][32] of the transposed stride-2 layer (+ bias, contiguous fp32 | None) -> NCHW (n, cout, 2h, 2w)"""
+    n, h, w, cols = u32.shape
+    assert cols == 32 and ks * ks * cout <= 32
+    out = _new(u32, (n, cout, 2 * h, 2 * w), F32)
+    _lib.check(_L().cae_t_col2im_s2(u32.data_ptr(), _ptr(bias_c), n, cout, h, w, ks, out.data_ptr(), _st()))
+    return out
+
+
+def _im2col_s1r(g: torch.Tensor, ks: int, kp: int) -> torch.Tensor:
+    """contiguous fp32 NCHW output gradient of a colour layer -> its reflect-folded columns as a bf16 (hi, lo) pair,
+    [n][h][w][2 kp]"""
+    n, c, h, w = g.shape
+    assert ks * ks * c <= kp
+    gu16 = _new(g, (n, h, w, 2 * kp), BF16)
+    _lib.check(_L().cae_t_im2col_s1r(g.data_ptr(), n, c, h, w, ks, kp, gu16.data_ptr(), _st()))
+    return gu16
+
+
+def _col2im_s1r(u32, bias_c, cout, ks):
+    """fp32 columns [n][h][w][kp] of a colour layer (+ bias) -> NCHW (n, cout, h, w) under reflect padding"""
+    n, h, w, kp = u32.shape
+    assert ks * ks * cout <= kp
+    out = _new(u32, (n, cout, h, w), F32)
+    _lib.check(_L().cae_t_col2im_s1r(u32.data_ptr(), _ptr(bias_c), n, cout, h, w, ks, kp, out.data_ptr(), _st()))
     return out
 
 
@@ -177,10 +425,10 @@ def _gdn_fused(cp: int) -> bool:
 def _gdn_forward(z32: torch.Tensor, beta_p: torch.Tensor, gamma_p: torch.Tensor, inverse: bool):
     """-> (y16, saved factor f | None)"""
     n, h, w, cp = z32.shape
-    y16 = torch.empty_like(z32, dtype=torch.bfloat16)
+    y16 = torch.empty_like(z32, dtype=BF16)
     beta, gamma = beta_p.detach().float().contiguous(), gamma_p.detach().float().contiguous()  # (alive across the call)
     if _gdn_fused(cp):
-        f = torch.empty(_L().cae_t_gdn_saved_elems(n * h * w, cp), dtype=torch.float32, device=z32.device)
+        f = _new(z32, _L().cae_t_gdn_saved_elems(n * h * w, cp), F32)
         _lib.check(_L().cae_t_gdn_forward_save(z32.data_ptr(), n * h * w, cp, beta.data_ptr(), gamma.data_ptr(),
                                                int(inverse), y16.data_ptr(), f.data_ptr(), _st()))
         return y16, f
@@ -192,22 +440,15 @@ def _gdn_forward(z32: torch.Tensor, beta_p: torch.Tensor, gamma_p: torch.Tensor,
 def _gdn_backward(z32, gext32, pad, beta_p, gamma_p, inverse, f=None):
     """-> (gz16, g_beta_p, g_gamma_p)"""
     n, h, w, cp = z32.shape
-    dev = z32.device
+    gz16 = torch.empty_like(z32, dtype=BF16)
+    gg, gb = _new(z32, (cp, cp), F32), _new(z32, (cp,), F32)
+    gamma = gamma_p.detach().float().contiguous()
     if f is not None:
-        gz16 = torch.empty_like(z32, dtype=torch.bfloat16)
-        gg = torch.empty((cp, cp), dtype=torch.float32, device=dev)
-        gb = torch.empty((cp,), dtype=torch.float32, device=dev)
-        gamma = gamma_p.detach().float().contiguous()
         _lib.check(_L().cae_t_gdn_backward_fused(z32.data_ptr(), f.data_ptr(), gext32.data_ptr(), n, h, w, pad, cp,
                                                  gamma.data_ptr(), int(inverse), gz16.data_ptr(), gg.data_ptr(),
                                                  gb.data_ptr(), _st()))
         return gz16, gb, gg
-    gn = torch.empty_like(z32)
-    gzd = torch.empty_like(z32)
-    gz16 = torch.empty_like(z32, dtype=torch.bfloat16)
-    gg = torch.empty((cp, cp), dtype=torch.float32, device=dev)
-    gb = torch.empty((cp,), dtype=torch.float32, device=dev)
-    gamma = gamma_p.detach().float().contiguous()
+    gn, gzd = torch.empty_like(z32), torch.empty_like(z32)
     gamma_t = gamma.t().contiguous()
     beta = beta_p.detach().float().contiguous()
     _lib.check(_L().cae_t_gdn_backward(z32.data_ptr(), gext32.data_ptr(), n, h, w, pad, cp,
@@ -217,110 +458,126 @@ def _gdn_backward(z32, gext32, pad, beta_p, gamma_p, inverse, f=None):
     return gz16, gb, gg
 
 
+def _bn_moments(a: torch.Tensor, b: torch.Tensor):
+    """contiguous fp32 NCHW a, b -> per channel (sum a, sum a b) in float64"""
+    n, c, h, w = a.shape
+    assert b.shape == a.shape
+    s1, s2 = _new(a, c, F64), _new(a, c, F64)
+    _lib.check(_L().cae_t_bn_moments(a.data_ptr(), b.data_ptr(), n, c, h * w, s1.data_ptr(), s2.data_ptr(), _st()))
+    return s1, s2
+
+
+def _bn_affine(a: torch.Tensor, b: Optional[torch.Tensor], A: torch.Tensor, B: Optional[torch.Tensor], C: torch.Tensor):
+    """-> a A + b B + C with per-channel fp32 coefficients (b, B: None without the second term)"""
+    n, c, h, w = a.shape
+    assert (b is None) == (B is None) and (b is None or b.shape == a.shape) and A.numel() == C.numel() == c
+    out = torch.empty_like(a)
+    _lib.check(_L().cae_t_bn_affine(a.data_ptr(), _ptr(b), n, c, h * w, A.data_ptr(), _ptr(B), C.data_ptr(), out.data_ptr(), _st()))
+    return out
+
+
 def _weight_grad(gw: torch.Tensor, spec_shape: Tuple[int, int], ks: int) -> torch.Tensor:
     """gw [k*k][ca][cb] -> gradient of a (d0 = b, d1 = a, k, k) weight"""
     d0, d1 = spec_shape
     return gw.permute(2, 1, 0)[:d0, :d1].reshape(d0, d1, ks, ks).contiguous()
 
 
-class ColourSpec:
-    """One multiscale colour layer: Conv2d(cin -> cout, ks, stride 1, reflect padding ks//2) (_autoencoders.py:417-428)."""
+# ---- steps shared by the fused tracks and the composed functions ------------------------------------------------------
 
-    def __init__(self, cin: int, cout: int, ks: int, has_bias: bool):
-        self.cin, self.cout, self.ks, self.has_bias = int(cin), int(cout), int(ks), bool(has_bias)
-        self.cin_p = _pad32(cin)
-        self.K = self.ks * self.ks * self.cout  # GEMM columns (tap, channel) of the edge form
-        self.kp = _pad32(self.K)
-
-    @property
-    def n_tensors(self) -> int:
-        return 1 + int(self.has_bias)
+def _conv_s1_forward(a16, w, b, ks, act, synthesis, want32, want16):
+    """stride-1 convolution (+ bias) (+ activation): reflect Conv2d (analysis) or ConvTranspose2d(padding k//2)
+    (synthesis) -> (fp32 output | None, bf16 output behind the activation | None)"""
+    wp, bp = _pack_bias(w, b, 0 if synthesis else 1, ks)
+    return _corr_s1(a16, wp, 2 if synthesis else 0, bp, act, want32, want16)
 
 
-def _colour_edge(cs: ColourSpec) -> bool:
-    """the colour layer as a pointwise GEMM over K = (tap, channel) <= 96 (cae_t_col2im_s1r / cae_t_im2col_s1r); else, or with
-    CAE_EDGE_GEMM=0, the padded stride-1 form on the convolution kernels (cae_t_corr_s1 / cae_t_wgrad_s1)"""
-    return cs.cout <= 3 and cs.kp <= 96 and os.environ.get('CAE_EDGE_GEMM', '1') != '0'
+def _conv_s1_backward(gu16, a16, w, has_bias, synthesis, dgrad=True, want32=True):
+    """backward of _conv_s1_forward from the bf16 gradient gu16 at its (pre-activation) output and its input a16
+    -> (g_w, g_b | None, fp32 data gradient | None, bf16 data gradient | None); the analysis form's data gradient is fp32 on
+    the extended domain (to be folded); dgrad False: the parameter gradients only"""
+    ks = w.shape[2]
+    gwp = _wgrad_s1(gu16, a16, ks, 0) if synthesis else _wgrad_s1(a16, gu16, ks, 1)
+    g_w = _weight_grad(gwp, tuple(w.shape[:2]), ks)
+    g_b = _colsum(gu16, w.shape[1 if synthesis else 0]) if has_bias else None
+    if not dgrad:
+        return g_w, g_b, None, None
+    return (g_w, g_b) + _corr_s1(gu16, _pack(w, 1 if synthesis else 0, ks), 3 if synthesis else 1, want32=want32,
+                                 want16=not want32)
 
 
-def _to_bf16(t32: torch.Tensor) -> torch.Tensor:
-    n, h, w, cp = t32.shape
-    out = torch.empty_like(t32, dtype=torch.bfloat16)
-    _lib.check(_L().cae_t_fold_to_bf16(t32.data_ptr(), n, h, w, 0, cp, out.data_ptr(), _st()))
-    return out
+def _conv_s2_backward(g16, x16, w, has_bias, dgrad=True):
+    """backward of the strided reflect convolution (cout, cin, k, k) from the bf16 gradient at its output and its bf16 input
+    -> (g_w, g_b | None, fp32 data gradient on the extended domain | None)"""
+    cout, cin, ks = w.shape[0], w.shape[1], w.shape[2]
+    g_w = _weight_grad(_wgrad(x16, g16, ks, 1), (cout, cin), ks)
+    g_b = _colsum(g16, cout) if has_bias else None
+    return g_w, g_b, (_conv_dgrad_ext(g16, _pack(w, 0, ks), x16.shape[1:3]) if dgrad else None)
+
+
+class _Saved(NamedTuple):
+    """what one unit of a fused track keeps for its backward"""
+    a_in: torch.Tensor            # bf16 input of the unit (edge first layer: the im2col columns of the image)
+    p: Optional[torch.Tensor]     # bf16 output of the stride-1 pre-convolution (behind its activation)
+    z: Optional[torch.Tensor]     # fp32 input of the GDN / IGDN
+    f: Optional[torch.Tensor]     # the factor the fused GDN forward saved
+    out: Optional[torch.Tensor]   # bf16 output behind the LeakyReLU / ReLU of a non-last unit
+    edge: bool = False            # the 3-channel edge layer as a pointwise GEMM
+
+
+def _layer_forward(conv, x16, wp, bias_p, s: LayerSpec, beta, gamma, last: bool, inverse: bool, a_in, p16, edge=False):
+    """the strided layer `conv` (_conv_fwd / _deconv_fwd / _pointwise on x16) and what follows it: fp32 into a GDN / IGDN or
+    out of the track, else bf16 behind the activation -> (bf16 input of the next unit, fp32 output | None, _Saved)"""
+    need32 = s.has_gdn or last
+    z32, z16 = conv(x16, wp, bias_p, 0 if need32 else s.act, need32)
+    a16, f = _gdn_forward(z32, beta, gamma, inverse) if s.has_gdn else (z16, None)
+    return a16, z32, _Saved(a_in, p16, z32 if s.has_gdn else None, f, z16 if s.act else None, edge)
+
+
+def _hand_down(gx32, gx16, pad, prev: LayerSpec, sv: _Saved, beta_p, gamma_p, inverse: bool, colour=None):
+    """a level's data gradient -> the bf16 gradient at the previous unit's strided layer.  gx32: fp32, extended by `pad`
+    (analysis: the reflect border is folded by whichever kernel reads it; synthesis: 0), or None with gx16 already rounded
+    (nothing between the two layers).  colour = (g, a16, cs, w, has_bias) of the level's colour layer: its data gradient is
+    added to gx32 first, so the level's gradient is rounded once.  Through the previous unit's GDN / IGDN, or its
+    LeakyReLU / ReLU mask, or the plain fold / rounding -> (g16, g_beta | None, g_gamma | None, colour (g_w, g_b) | None)"""
+    col = _colour_backward(*colour, gx32) if colour is not None else None
+    if prev.has_gdn:
+        return _gdn_backward(sv.z, gx32, pad, beta_p, gamma_p, inverse, sv.f) + (col,)
+    if sv.out is not None:
+        return _act_backward(None, gx32, pad, sv.out, prev.act), None, None, col
+    return (gx16 if gx32 is None else _fold_to_bf16(gx32, pad)), None, None, col
 
 
 def _colour_forward(a16: torch.Tensor, cs: ColourSpec, wt: torch.Tensor, b: Optional[torch.Tensor]) -> torch.Tensor:
     """colour layer on a level's bf16 activation [n][h][w][cin_p] -> NCHW fp32 (n, cout, h, w)"""
-    L = _L()
     n, h, w, cp = a16.shape
-    P, dev = cs.ks // 2, a16.device
+    P = cs.ks // 2
     if h <= P or w <= P:
         raise ValueError(f'colour layer: a {h} x {w} level is too small for reflect padding {P}')
     if _colour_edge(cs):
         # u[q][(tap, co)] = sum_ci a[q][ci] W[co][ci][tap] (1 x 1 GEMM, N = kp), then the reflect col2im + bias
-        w1 = torch.zeros((cs.kp, cs.cin, 1, 1), dtype=torch.float32, device=dev)  # (j = tap * cout + co, ci)
-        w1[:cs.K, :, 0, 0] = wt.detach().float().permute(2, 3, 0, 1).reshape(cs.K, cs.cin)
-        wp = _pack(w1, 1, 1)
-        u32 = torch.empty((n, h, w, cs.kp), dtype=torch.float32, device=dev)
-        _lib.check(L.cae_t_pointwise(a16.data_ptr(), n, h, w, cp, wp.data_ptr(), u32.data_ptr(), None, cs.kp, None, 0, _st()))
-        out = torch.empty((n, cs.cout, h, w), dtype=torch.float32, device=dev)
-        bias_c = None if b is None else b.detach().float().contiguous()
-        _lib.check(L.cae_t_col2im_s1r(u32.data_ptr(), _ptr(bias_c), n, cs.cout, h, w, cs.ks, cs.kp, out.data_ptr(), _st()))
-        return out
-    cn = _pad32(cs.cout)
-    wp = _pack(wt, 1, cs.ks)
-    o32 = torch.empty((n, h, w, cn), dtype=torch.float32, device=dev)
-    _lib.check(L.cae_t_corr_s1(a16.data_ptr(), n, h, w, cp, wp.data_ptr(), cs.ks, 0, o32.data_ptr(), None, cn,
-                               _ptr(_bias_p(b, cn, dev)), 0, _st()))
-    return _to_nchw(o32, cs.cout)
+        u32, _ = _pointwise(a16, _colour_1x1(wt, cs, False), None, 0, True)
+        return _col2im_s1r(u32, None if b is None else b.detach().float().contiguous(), cs.cout, cs.ks)
+    return _to_nchw(_conv_s1_forward(a16, wt, b, cs.ks, 0, False, True, False)[0], cs.cout)
 
 
 def _colour_backward(g: torch.Tensor, a16: torch.Tensor, cs: ColourSpec, wt: torch.Tensor, has_bias: bool,
                      acc32: torch.Tensor):
     """gradient of a colour layer's NCHW output g: its data gradient is ADDED to acc32 (fp32 [n][h][w][cin_p], the level's
     gradient); -> (g_w, g_b | None)"""
-    L = _L()
-    n, h, w, cp = a16.shape
-    P, kk, dev = cs.ks // 2, cs.ks * cs.ks, a16.device
     gc = g.detach().float().contiguous()
     g_b = gc.bfloat16().float().sum(dim=(0, 2, 3)) if has_bias else None
     if _colour_edge(cs):
         # gu = the folded output gradient as a bf16 (hi, lo) pair: 2 kp GEMM columns, the weights repeated over both halves
-        k2 = 2 * cs.kp
-        gu16 = torch.empty((n, h, w, k2), dtype=torch.bfloat16, device=dev)
-        _lib.check(L.cae_t_im2col_s1r(gc.data_ptr(), n, cs.cout, h, w, cs.ks, cs.kp, gu16.data_ptr(), _st()))
-        gw1 = torch.empty((1, cp, k2), dtype=torch.float32, device=dev)
-        _lib.check(L.cae_t_wgrad_pointwise(a16.data_ptr(), gu16.data_ptr(), n, h, w, cp, k2, gw1.data_ptr(), _st()))
+        gu16 = _im2col_s1r(gc, cs.ks, cs.kp)
+        gw1 = _wgrad_pointwise(a16, gu16)
         gw = gw1[0, :cs.cin, :cs.K] + gw1[0, :cs.cin, cs.kp:cs.kp + cs.K]
         g_w = gw.reshape(cs.cin, cs.ks, cs.ks, cs.cout).permute(3, 0, 1, 2).contiguous()
-        w1d = torch.zeros((cs.cin, k2, 1, 1), dtype=torch.float32, device=dev)  # (ci, j)
-        wd = wt.detach().float().permute(1, 2, 3, 0).reshape(cs.cin, cs.K)
-        w1d[:, :cs.K, 0, 0] = wd
-        w1d[:, cs.kp:cs.kp + cs.K, 0, 0] = wd
-        wp_d = _pack(w1d, 1, 1)
-        _lib.check(L.cae_t_pointwise_acc(gu16.data_ptr(), n, h, w, k2, wp_d.data_ptr(), acc32.data_ptr(), cp, _st()))
+        _pointwise_acc(gu16, _colour_1x1(wt, cs, True), acc32)
         return g_w, g_b
-    cn = _pad32(cs.cout)
-    gu16, _ = _from_nchw(gc, cn)
-    gwp = torch.empty((kk, cp, cn), dtype=torch.float32, device=dev)
-    _lib.check(L.cae_t_wgrad_s1(a16.data_ptr(), n, h, w, cp, gu16.data_ptr(), cn, cs.ks, 1, gwp.data_ptr(), _st()))
-    g_w = _weight_grad(gwp, (cs.cout, cs.cin), cs.ks)
-    wp_d = _pack(wt, 0, cs.ks)
-    gext = torch.empty((n, h + 2 * P, w + 2 * P, cp), dtype=torch.float32, device=dev)
-    _lib.check(L.cae_t_corr_s1(gu16.data_ptr(), n, h, w, cn, wp_d.data_ptr(), cs.ks, 1, gext.data_ptr(), None, cp, None, 0,
-                               _st()))
-    _lib.check(L.cae_t_fold_acc(gext.data_ptr(), n, h, w, P, cp, acc32.data_ptr(), _st()))
+    gu16, _ = _from_nchw(gc, _pad32(cs.cout))
+    g_w, _, gext, _ = _conv_s1_backward(gu16, a16, wt, False, False)
+    _fold_acc(gext, cs.ks // 2, acc32)
     return g_w, g_b
-
-
-def _split_colour(colour, tensors):
-    """flat colour tensors -> per level (w, b | None)"""
-    out, k = [], 0
-    for cs in colour:
-        out.append((tensors[k], tensors[k + 1] if cs.has_bias else None))
-        k += cs.n_tensors
-    return out
 
 
 class AnalysisFn(torch.autograd.Function):
@@ -329,135 +586,52 @@ class AnalysisFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, specs, *tensors):
-        L = _L()
         layers = _split_params(specs, tensors)
-        n, _, h, w = x.shape
-        dev = x.device
         edge = _edge_ok(specs[0], specs[0].cin)
         a16 = None if edge else _from_nchw(x, specs[0].cin_p)[0]
-        saved, dims = [], []
-        z32 = None
+        saved = []
         for i, (s, (wt, b, beta, gamma, pw, pb)) in enumerate(zip(specs, layers)):
             last = i == len(specs) - 1
-            oh, ow = (h + 1) // 2, (w + 1) // 2
             if i == 0 and edge:
                 # first layer: K = (tap, channel) = 27 of 32 as ONE contraction chunk of a 1 x 1 GEMM on the im2col of the image
-                cols = torch.empty((n, oh, ow, 32), dtype=torch.bfloat16, device=dev)
-                xc = x.detach().float().contiguous()
-                _lib.check(L.cae_t_im2col_s2(xc.data_ptr(), n, s.cin, h, w, oh, ow, s.ks, 1, cols.data_ptr(), _st()))
-                w1 = torch.zeros((s.cout, 32, 1, 1), dtype=torch.float32, device=dev)
-                w1[:, :s.ks * s.ks * s.cin, 0, 0] = wt.detach().float().permute(0, 2, 3, 1).reshape(s.cout, -1)
-                wp = _pack(w1, 1, 1)
-                bias_p = _bias_p(b, s.cout_p, dev)
-                need32 = s.has_gdn or last
-                z32 = torch.empty((n, oh, ow, s.cout_p), dtype=torch.float32, device=dev) if need32 else None
-                z16 = None if need32 else torch.empty((n, oh, ow, s.cout_p), dtype=torch.bfloat16, device=dev)
-                _lib.check(L.cae_t_pointwise(cols.data_ptr(), n, oh, ow, 32, wp.data_ptr(), _ptr(z32), _ptr(z16), s.cout_p,
-                                             _ptr(bias_p), 0 if need32 else s.act, _st()))
-                f_saved = None
-                if s.has_gdn:
-                    a16, f_saved = _gdn_forward(z32, beta, gamma, False)
-                elif not last:
-                    a16 = z16
-                saved.append(dict(a_in=cols, p=None, z=z32 if s.has_gdn else None, f=f_saved,
-                                  out=a16 if (s.act and not need32) else None, edge=True))
-                dims.append((h, w, oh, ow))
-                h, w = oh, ow
-                continue
-            a16_in, p16 = a16, None
-            if s.has_pre:  # stride-1 reflect convolution cin -> cin + activation
-                p16 = torch.empty((n, h, w, s.cin_p), dtype=torch.bfloat16, device=dev)
-                wpp, bpp = _pack(pw, 1, s.ks), _bias_p(pb, s.cin_p, dev)
-                _lib.check(L.cae_t_corr_s1(a16.data_ptr(), n, h, w, s.cin_p, wpp.data_ptr(), s.ks, 0, None, p16.data_ptr(),
-                                           s.cin_p, _ptr(bpp), s.act, _st()))
-            wp = _pack(wt, 1, s.ks)
-            bias_p = _bias_p(b, s.cout_p, dev)
-            need32 = s.has_gdn or last
-            z32 = torch.empty((n, oh, ow, s.cout_p), dtype=torch.float32, device=dev) if need32 else None
-            z16 = None if need32 else torch.empty((n, oh, ow, s.cout_p), dtype=torch.bfloat16, device=dev)
-            main_in = p16 if p16 is not None else a16
-            _lib.check(L.cae_t_conv_forward_act(main_in.data_ptr(), n, h, w, s.cin_p, wp.data_ptr(), s.ks, _ptr(z32), _ptr(z16),
-                                                s.cout_p, _ptr(bias_p), 0 if need32 else s.act, _st()))
-            f_saved = None
-            if s.has_gdn:
-                a16, f_saved = _gdn_forward(z32, beta, gamma, False)
-            elif not last:
-                a16 = z16  # (post-activation output of a LeakyReLU / ReLU unit)
-            saved.append(dict(a_in=a16_in, p=p16, z=z32 if s.has_gdn else None, f=f_saved,
-                              out=a16 if (s.act and not need32) else None))
-            dims.append((h, w, oh, ow))
-            h, w = oh, ow
-        y = _to_nchw(z32, specs[-1].cout)
-        ctx.specs, ctx.saved, ctx.dims, ctx.layers = specs, saved, dims, [tuple(t.detach() if t is not None else None
-                                                                                 for t in l) for l in layers]
-        return y
+                cols = _im2col_s2(x.detach().float().contiguous(), s.ks, 1)
+                a16, z32, sv = _layer_forward(_pointwise, cols, _first_layer_1x1(wt, s), _bias_p(b, s.cout_p, x.device), s,
+                                              beta, gamma, last, False, cols, None, edge=True)
+            else:
+                p16 = _conv_s1_forward(a16, pw, pb, s.ks, s.act, False, False, True)[1] if s.has_pre else None
+                a16, z32, sv = _layer_forward(_conv_fwd, a16 if p16 is None else p16, *_pack_bias(wt, b, 1, s.ks), s,
+                                              beta, gamma, last, False, a16, p16)
+            saved.append(sv)
+        ctx.specs, ctx.saved, ctx.layers = specs, saved, _detached(layers)
+        return _to_nchw(z32, specs[-1].cout)
 
     @staticmethod
     def backward(ctx, gy):
-        L = _L()
-        specs, saved, dims, layers = ctx.specs, ctx.saved, ctx.dims, ctx.layers
-        n = gy.shape[0]
-        dev = gy.device
+        specs, saved, layers = ctx.specs, ctx.saved, ctx.layers
         g16, _ = _from_nchw(gy, specs[-1].cout_p)  # gradient with respect to the last convolution's output
         per_layer = [[None] * 6 for _ in specs]
-        masked = False  # g16 already went through this unit's activation (applied on the fp32 gradient: one rounding)
         for i in reversed(range(len(specs))):
-            s = specs[i]
+            s, sv = specs[i], saved[i]
             wt, b, _, _, pw, pb = layers[i]
-            sv = saved[i]
-            h, w, oh, ow = dims[i]
-            kk = s.ks * s.ks
             P = s.ks // 2
-            if sv['out'] is not None and not masked:  # through the unit's activation
-                g16 = _act_backward(g16, None, 0, sv['out'], s.act)
-            masked = False
-            if sv.get('edge'):  # first layer as a pointwise GEMM: its weight gradient over the im2col, back in (cout, cin, k, k)
-                gw1 = torch.empty((1, 32, s.cout_p), dtype=torch.float32, device=dev)
-                _lib.check(L.cae_t_wgrad_pointwise(sv['a_in'].data_ptr(), g16.data_ptr(), n, oh, ow, 32, s.cout_p,
-                                                   gw1.data_ptr(), _st()))
-                per_layer[i][0] = (gw1[0, :kk * s.cin, :s.cout].t().reshape(s.cout, s.ks, s.ks, s.cin)
+            if sv.edge:  # first layer as a pointwise GEMM: its weight gradient over the im2col, back in (cout, cin, k, k)
+                gw1 = _wgrad_pointwise(sv.a_in, g16)
+                per_layer[i][0] = (gw1[0, :s.ks * s.ks * s.cin, :s.cout].t().reshape(s.cout, s.ks, s.ks, s.cin)
                                    .permute(0, 3, 1, 2).contiguous())
                 if b is not None:
                     per_layer[i][1] = _colsum(g16, s.cout)
                 break  # (the image itself needs no gradient)
-            main_in = sv['p'] if s.has_pre else sv['a_in']
-            gw = torch.empty((kk, s.cin_p, s.cout_p), dtype=torch.float32, device=dev)
-            _lib.check(L.cae_t_wgrad(main_in.data_ptr(), n, h, w, s.cin_p, g16.data_ptr(), oh, ow, s.cout_p, s.ks, 1,
-                                     gw.data_ptr(), _st()))
-            per_layer[i][0] = _weight_grad(gw, (s.cout, s.cin), s.ks)
-            if b is not None:
-                per_layer[i][1] = _colsum(g16, s.cout)
-            if i == 0 and not s.has_pre:
-                break  # (the image itself needs no gradient)
-            wp_d = _pack(wt, 0, s.ks)
-            gext = torch.empty((n, h + 2 * P, w + 2 * P, s.cin_p), dtype=torch.float32, device=dev)
-            _lib.check(L.cae_t_conv_dgrad_ext(g16.data_ptr(), n, oh, ow, s.cout_p, wp_d.data_ptr(), s.ks, h, w,
-                                              gext.data_ptr(), s.cin_p, _st()))
+            per_layer[i][0], per_layer[i][1], gext = _conv_s2_backward(g16, sv.a_in if sv.p is None else sv.p, wt,
+                                                                        b is not None, dgrad=i > 0 or s.has_pre)
             if s.has_pre:
-                gu16 = _act_backward(None, gext, P, sv['p'], s.act)  # fold + activation mask: gradient at the pre-convolution's output
-                gwp = torch.empty((kk, s.cin_p, s.cin_p), dtype=torch.float32, device=dev)
-                _lib.check(L.cae_t_wgrad_s1(sv['a_in'].data_ptr(), n, h, w, s.cin_p, gu16.data_ptr(), s.cin_p, s.ks, 1,
-                                            gwp.data_ptr(), _st()))
-                per_layer[i][4] = _weight_grad(gwp, (s.cin, s.cin), s.ks)
-                if pb is not None:
-                    per_layer[i][5] = _colsum(gu16, s.cin)
-                if i == 0:
-                    break
-                wpp_d = _pack(pw, 0, s.ks)
-                gext = torch.empty((n, h + 2 * P, w + 2 * P, s.cin_p), dtype=torch.float32, device=dev)
-                _lib.check(L.cae_t_corr_s1(gu16.data_ptr(), n, h, w, s.cin_p, wpp_d.data_ptr(), s.ks, 1, gext.data_ptr(), None,
-                                           s.cin_p, None, 0, _st()))
-            if specs[i - 1].has_gdn:
-                z_prev, f_prev = saved[i - 1]['z'], saved[i - 1]['f']
-                _, _, beta_p, gamma_p, _, _ = layers[i - 1]
-                g16, g_beta, g_gamma = _gdn_backward(z_prev, gext, P, beta_p, gamma_p, False, f_prev)
-                per_layer[i - 1][2], per_layer[i - 1][3] = g_beta, g_gamma
-            elif saved[i - 1]['out'] is not None:  # reflect fold + the previous unit's activation on the fp32 gradient
-                g16 = _act_backward(None, gext, P, saved[i - 1]['out'], specs[i - 1].act)
-                masked = True
-            else:
-                g16 = torch.empty((n, h, w, s.cin_p), dtype=torch.bfloat16, device=dev)
-                _lib.check(L.cae_t_fold_to_bf16(gext.data_ptr(), n, h, w, P, s.cin_p, g16.data_ptr(), _st()))
+                gu16 = _act_backward(None, gext, P, sv.p, s.act)  # fold + activation mask: gradient at the pre-convolution's output
+                per_layer[i][4], per_layer[i][5], gext, _ = _conv_s1_backward(gu16, sv.a_in, pw, pb is not None, False,
+                                                                               dgrad=i > 0)
+            if i == 0:
+                break  # (the image itself needs no gradient)
+            _, _, beta_p, gamma_p, _, _ = layers[i - 1]
+            g16, per_layer[i - 1][2], per_layer[i - 1][3], _ = _hand_down(gext, None, P, specs[i - 1], saved[i - 1],
+                                                                          beta_p, gamma_p, False)
         return (None, None, *_flat_grads(specs, per_layer))
 
 
@@ -470,197 +644,90 @@ class SynthesisFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, yq, specs, colour, *tensors):
-        L = _L()
         nt = sum(s.n_tensors for s in specs)
         layers = _split_params(specs, tensors[:nt])
         col_layers = _split_colour(colour, tensors[nt:]) if colour else []
-        colours = []
-        n, _, h, w = yq.shape
-        dev = yq.device
+        colours, saved = [], []
         a16, _ = _from_nchw(yq, specs[0].cin_p)
-        saved, dims = [], []
-        z32 = None
-        ctx.colour, ctx.col_layers, ctx.dev = colour or None, [(cw.detach(), cb) for cw, cb in col_layers], dev
         if colour:
             ctx.set_materialize_grads(False)  # (colour outputs the loss does not read hand back None)
         for i, (s, (wt, b, beta, gamma, pw, pb)) in enumerate(zip(specs, layers)):
             last = i == len(specs) - 1
             if colour and i > 0:  # colour layer of the previous level, on the activation this unit reads
                 colours.append(_colour_forward(a16, colour[i - 1], *col_layers[i - 1]))
-            a16_in, p16 = a16, None
-            if s.has_pre:  # ConvTranspose2d(cin, cin, k, stride 1, padding k//2) + activation
-                p16 = torch.empty((n, h, w, s.cin_p), dtype=torch.bfloat16, device=dev)
-                wpp, bpp = _pack(pw, 0, s.ks), _bias_p(pb, s.cin_p, dev)
-                _lib.check(L.cae_t_corr_s1(a16.data_ptr(), n, h, w, s.cin_p, wpp.data_ptr(), s.ks, 2, None, p16.data_ptr(),
-                                           s.cin_p, _ptr(bpp), s.act, _st()))
+            # ConvTranspose2d(cin, cin, k, stride 1, padding k//2) + activation in front of LeakyReLU / ReLU units
+            p16 = _conv_s1_forward(a16, pw, pb, s.ks, s.act, True, False, True)[1] if s.has_pre else None
+            main_in = a16 if p16 is None else p16
             if last and _edge_ok(s, s.cout):
                 # last layer: per INPUT position the k*k*cout <= 32 products with the weights (a 1 x 1 GEMM), then col2im
-                K = s.ks * s.ks * s.cout
-                w1 = torch.zeros((32, s.cin, 1, 1), dtype=torch.float32, device=dev)  # (j = tap * cout + co, ci)
-                w1[:K, :, 0, 0] = wt.detach().float().permute(2, 3, 1, 0).reshape(K, s.cin)
-                wp = _pack(w1, 1, 1)
-                main_in = p16 if p16 is not None else a16
-                u32 = torch.empty((n, h, w, 32), dtype=torch.float32, device=dev)
-                _lib.check(L.cae_t_pointwise(main_in.data_ptr(), n, h, w, s.cin_p, wp.data_ptr(), u32.data_ptr(), None, 32,
-                                             None, 0, _st()))
-                x_r = torch.empty((n, s.cout, 2 * h, 2 * w), dtype=torch.float32, device=dev)
-                bias_c = None if b is None else b.detach().float().contiguous()
-                _lib.check(L.cae_t_col2im_s2(u32.data_ptr(), _ptr(bias_c), n, s.cout, h, w, s.ks, x_r.data_ptr(), _st()))
-                saved.append(dict(a_in=a16_in, p=p16, z=None, f=None, out=None, edge=True))
-                dims.append((h, w))
-                ctx.specs, ctx.saved, ctx.dims = specs, saved, dims
-                ctx.layers = [tuple(t.detach() if t is not None else None for t in l) for l in layers]
-                ctx.need_input_grad = yq.requires_grad
-                ctx.out_shape = tuple(x_r.shape)
-                return (x_r, *colours) if colour else x_r
-            wp = _pack(wt, 0, s.ks)
-            bias_p = _bias_p(b, s.cout_p, dev)
-            need32 = s.has_gdn or last
-            z32 = torch.empty((n, 2 * h, 2 * w, s.cout_p), dtype=torch.float32, device=dev) if need32 else None
-            z16 = None if need32 else torch.empty((n, 2 * h, 2 * w, s.cout_p), dtype=torch.bfloat16, device=dev)
-            main_in = p16 if p16 is not None else a16
-            _lib.check(L.cae_t_deconv_forward_act(main_in.data_ptr(), n, h, w, s.cin_p, wp.data_ptr(), s.ks, _ptr(z32),
-                                                  _ptr(z16), s.cout_p, _ptr(bias_p), 0 if need32 else s.act, _st()))
-            f_saved = None
-            if s.has_gdn:
-                a16, f_saved = _gdn_forward(z32, beta, gamma, True)
-            elif not last:
-                a16 = z16
-            saved.append(dict(a_in=a16_in, p=p16, z=z32 if s.has_gdn else None, f=f_saved,
-                              out=a16 if (s.act and not need32) else None))
-            dims.append((h, w))
-            h, w = 2 * h, 2 * w
-        x_r = _to_nchw(z32, specs[-1].cout)
-        ctx.specs, ctx.saved, ctx.dims = specs, saved, dims
-        ctx.layers = [tuple(t.detach() if t is not None else None for t in l) for l in layers]
-        ctx.need_input_grad = yq.requires_grad
-        ctx.out_shape = tuple(x_r.shape)
+                u32, _ = _pointwise(main_in, _last_layer_1x1(wt, s, False), None, 0, True)
+                x_r = _col2im_s2(u32, None if b is None else b.detach().float().contiguous(), s.cout, s.ks)
+                saved.append(_Saved(a16, p16, None, None, None, edge=True))
+            else:
+                a16, z32, sv = _layer_forward(_deconv_fwd, main_in, *_pack_bias(wt, b, 0, s.ks), s, beta, gamma, last, True,
+                                              a16, p16)
+                saved.append(sv)
+                if last:
+                    x_r = _to_nchw(z32, s.cout)
+        ctx.specs, ctx.saved, ctx.layers = specs, saved, _detached(layers)
+        ctx.colour, ctx.col_layers = colour or None, [(cw.detach(), cb) for cw, cb in col_layers]
+        ctx.need_input_grad, ctx.out_shape, ctx.dev = yq.requires_grad, tuple(x_r.shape), yq.device
         return (x_r, *colours) if colour else x_r
 
     @staticmethod
     def backward(ctx, gx, *gcols):
-        L = _L()
-        specs, saved, dims, layers = ctx.specs, ctx.saved, ctx.dims, ctx.layers
+        specs, saved, layers = ctx.specs, ctx.saved, ctx.layers
         colour, col_layers = ctx.colour, ctx.col_layers
-        dev = ctx.dev
         if gx is None:
-            gx = torch.zeros(ctx.out_shape, dtype=torch.float32, device=dev)
-        n = gx.shape[0]
+            gx = torch.zeros(ctx.out_shape, dtype=F32, device=ctx.dev)
         col_grads = [(None, None)] * (len(colour) if colour else 0)
-
-        def add_colour(i, gx32):
-            """the colour layer of level i - 1 (input of unit i): its data gradient onto gx32, its parameter gradients"""
-            cw, cb = col_layers[i - 1]
-            col_grads[i - 1] = _colour_backward(gcols[i - 1], saved[i]['a_in'], colour[i - 1], cw, cb is not None, gx32)
-
-        edge = bool(saved[-1].get('edge'))
-        g16 = None if edge else _from_nchw(gx, specs[-1].cout_p)[0]  # gradient with respect to the last layer's output
+        g16 = None if saved[-1].edge else _from_nchw(gx, specs[-1].cout_p)[0]  # gradient with respect to the last layer's output
         per_layer = [[None] * 6 for _ in specs]
         g_in = None
-        masked = False  # g16 already went through this unit's activation (applied on the fp32 gradient: one rounding)
         for i in reversed(range(len(specs))):
-            s = specs[i]
+            s, sv = specs[i], saved[i]
             wt, b, _, _, pw, pb = layers[i]
-            sv = saved[i]
-            h, w = dims[i]
-            kk = s.ks * s.ks
-            if sv.get('edge'):
+            main_in = sv.a_in if sv.p is None else sv.p
+            stop = i == 0 and not ctx.need_input_grad
+            has_col = i > 0 and colour is not None and gcols[i - 1] is not None
+            # fp32 wherever something still reads the level's gradient before it is rounded (one rounding)
+            want32 = i == 0 or has_col or specs[i - 1].has_gdn or saved[i - 1].out is not None
+            if sv.edge:
                 # last layer as a pointwise GEMM: gu[pos][(tap, co)] = g_x[2 pos - P + tap][co] (im2col of the output
                 # gradient, zeros outside); weight gradient and data gradient are 1 x 1 contractions with it
-                K = kk * s.cout
                 gxc = gx.detach().float().contiguous()
-                gu16 = torch.empty((n, h, w, 32), dtype=torch.bfloat16, device=dev)
-                _lib.check(L.cae_t_im2col_s2(gxc.data_ptr(), n, s.cout, 2 * h, 2 * w, h, w, s.ks, 0, gu16.data_ptr(), _st()))
-                main_in = sv['p'] if s.has_pre else sv['a_in']
-                gw1 = torch.empty((1, s.cin_p, 32), dtype=torch.float32, device=dev)
-                _lib.check(L.cae_t_wgrad_pointwise(main_in.data_ptr(), gu16.data_ptr(), n, h, w, s.cin_p, 32, gw1.data_ptr(),
-                                                   _st()))
-                per_layer[i][0] = (gw1[0, :s.cin, :K].reshape(s.cin, s.ks, s.ks, s.cout).permute(0, 3, 1, 2).contiguous())
+                gu16 = _im2col_s2(gxc, s.ks, 0)
+                gw1 = _wgrad_pointwise(main_in, gu16)
+                per_layer[i][0] = (gw1[0, :s.cin, :s.ks * s.ks * s.cout].reshape(s.cin, s.ks, s.ks, s.cout)
+                                   .permute(0, 3, 1, 2).contiguous())
                 if b is not None:
                     per_layer[i][1] = gxc.bfloat16().float().sum(dim=(0, 2, 3))
-                if i == 0 and not ctx.need_input_grad:
+                if stop:
                     break
-                w1d = torch.zeros((s.cin, 32, 1, 1), dtype=torch.float32, device=dev)  # (ci, j)
-                w1d[:, :K, 0, 0] = wt.detach().float().permute(0, 2, 3, 1).reshape(s.cin, K)
-                wp_d = _pack(w1d, 1, 1)
-                prev_gdn = i > 0 and specs[i - 1].has_gdn
-                prev_act = i > 0 and saved[i - 1]['out'] is not None
-                has_col = i > 0 and colour is not None and gcols[i - 1] is not None
-                want32 = prev_gdn or prev_act or i == 0 or has_col
-                gx32 = torch.empty((n, h, w, s.cin_p), dtype=torch.float32, device=dev) if want32 else None
-                gx16 = None if want32 else torch.empty((n, h, w, s.cin_p), dtype=torch.bfloat16, device=dev)
-                _lib.check(L.cae_t_pointwise(gu16.data_ptr(), n, h, w, 32, wp_d.data_ptr(), _ptr(gx32), _ptr(gx16), s.cin_p,
-                                             None, 0, _st()))
-                if has_col:
-                    add_colour(i, gx32)
-                    if not (prev_gdn or prev_act):
-                        gx16 = _to_bf16(gx32)
-                if i == 0:
-                    g_in = _to_nchw(gx32, s.cin)
-                elif prev_gdn:
-                    z_prev, f_prev = saved[i - 1]['z'], saved[i - 1]['f']
-                    _, _, beta_p, gamma_p, _, _ = layers[i - 1]
-                    g16, g_beta, g_gamma = _gdn_backward(z_prev, gx32, 0, beta_p, gamma_p, True, f_prev)
-                    per_layer[i - 1][2], per_layer[i - 1][3] = g_beta, g_gamma
-                elif prev_act:
-                    g16 = _act_backward(None, gx32, 0, saved[i - 1]['out'], specs[i - 1].act)
-                    masked = True
-                else:
-                    g16 = gx16
-                continue
-            if sv['out'] is not None and not masked:  # through the unit's activation
-                g16 = _act_backward(g16, None, 0, sv['out'], s.act)
-            masked = False
-            main_in = sv['p'] if s.has_pre else sv['a_in']
-            gw = torch.empty((kk, s.cout_p, s.cin_p), dtype=torch.float32, device=dev)
-            _lib.check(L.cae_t_wgrad(g16.data_ptr(), n, 2 * h, 2 * w, s.cout_p, main_in.data_ptr(), h, w, s.cin_p, s.ks, 0,
-                                     gw.data_ptr(), _st()))
-            per_layer[i][0] = _weight_grad(gw, (s.cin, s.cout), s.ks)
-            if b is not None:
-                per_layer[i][1] = _colsum(g16, s.cout)
-            if i == 0 and not ctx.need_input_grad and not s.has_pre:
-                break
-            wp_d = _pack(wt, 1, s.ks)
-            prev_gdn = i > 0 and specs[i - 1].has_gdn
-            prev_act = i > 0 and saved[i - 1]['out'] is not None
-            has_col = i > 0 and colour is not None and gcols[i - 1] is not None
-            want32 = prev_gdn or prev_act or i == 0 or s.has_pre or has_col  # (fp32 into an activation's backward: one rounding)
-            gx32 = torch.empty((n, h, w, s.cin_p), dtype=torch.float32, device=dev) if want32 else None
-            gx16 = None if want32 else torch.empty((n, h, w, s.cin_p), dtype=torch.bfloat16, device=dev)
-            _lib.check(L.cae_t_deconv_dgrad(g16.data_ptr(), n, h, w, s.cout_p, wp_d.data_ptr(), s.ks, _ptr(gx32), _ptr(gx16),
-                                            s.cin_p, _st()))
-            if s.has_pre:
-                gu16 = _act_backward(None, gx32, 0, sv['p'], s.act)  # gradient at the pre-convolution's output
-                gwp = torch.empty((kk, s.cin_p, s.cin_p), dtype=torch.float32, device=dev)
-                _lib.check(L.cae_t_wgrad_s1(gu16.data_ptr(), n, h, w, s.cin_p, sv['a_in'].data_ptr(), s.cin_p, s.ks, 0,
-                                            gwp.data_ptr(), _st()))
-                per_layer[i][4] = _weight_grad(gwp, (s.cin, s.cin), s.ks)
-                if pb is not None:
-                    per_layer[i][5] = _colsum(gu16, s.cin)
-                if i == 0 and not ctx.need_input_grad:
+                gx32, gx16 = _pointwise(gu16, _last_layer_1x1(wt, s, True), None, 0, want32)
+            else:
+                per_layer[i][0] = _weight_grad(_wgrad(g16, main_in, s.ks, 0), (s.cin, s.cout), s.ks)
+                if b is not None:
+                    per_layer[i][1] = _colsum(g16, s.cout)
+                if stop and not s.has_pre:
                     break
-                wpp_d = _pack(pw, 1, s.ks)
-                want32 = prev_gdn or prev_act or i == 0 or has_col
-                gx32 = torch.empty((n, h, w, s.cin_p), dtype=torch.float32, device=dev) if want32 else None
-                gx16 = None if want32 else torch.empty((n, h, w, s.cin_p), dtype=torch.bfloat16, device=dev)
-                _lib.check(L.cae_t_corr_s1(gu16.data_ptr(), n, h, w, s.cin_p, wpp_d.data_ptr(), s.ks, 3, _ptr(gx32), _ptr(gx16),
-                                           s.cin_p, None, 0, _st()))
-            if has_col:
-                add_colour(i, gx32)
-                if not (prev_gdn or prev_act):
-                    gx16 = _to_bf16(gx32)
+                gx32, gx16 = _deconv_dgrad(g16, _pack(wt, 1, s.ks), want32 or s.has_pre)
+                if s.has_pre:
+                    gu16 = _act_backward(None, gx32, 0, sv.p, s.act)  # gradient at the pre-convolution's output
+                    per_layer[i][4], per_layer[i][5], gx32, gx16 = _conv_s1_backward(gu16, sv.a_in, pw, pb is not None, True,
+                                                                                     dgrad=not stop, want32=want32)
+                    if stop:
+                        break
             if i == 0:
                 g_in = _to_nchw(gx32, s.cin)
-            elif prev_gdn:
-                z_prev, f_prev = saved[i - 1]['z'], saved[i - 1]['f']
-                _, _, beta_p, gamma_p, _, _ = layers[i - 1]
-                g16, g_beta, g_gamma = _gdn_backward(z_prev, gx32, 0, beta_p, gamma_p, True, f_prev)
-                per_layer[i - 1][2], per_layer[i - 1][3] = g_beta, g_gamma
-            elif prev_act:  # the previous unit's activation on the fp32 gradient
-                g16 = _act_backward(None, gx32, 0, saved[i - 1]['out'], specs[i - 1].act)
-                masked = True
-            else:
-                g16 = gx16
+                break
+            _, _, beta_p, gamma_p, _, _ = layers[i - 1]
+            cw, cb = col_layers[i - 1] if has_col else (None, None)
+            g16, per_layer[i - 1][2], per_layer[i - 1][3], col = _hand_down(
+                gx32, gx16, 0, specs[i - 1], saved[i - 1], beta_p, gamma_p, True,
+                (gcols[i - 1], sv.a_in, colour[i - 1], cw, cb is not None) if has_col else None)
+            if has_col:
+                col_grads[i - 1] = col
         flat_col = [g for cs, (g_w, g_b) in zip(colour or (), col_grads) for g in ((g_w, g_b) if cs.has_bias else (g_w,))]
         return (g_in, None, None, *_flat_grads(specs, per_layer), *flat_col)
 
@@ -673,60 +740,29 @@ class SynthesisFn(torch.autograd.Function):
 
 class _ConvS1Fn(torch.autograd.Function):
     """Stride-1 convolution cin -> cin of a residual unit's res_model, (+ bias) (+ LeakyReLU / ReLU): analysis = Conv2d with
-    reflect padding, synthesis = ConvTranspose2d(stride 1, padding k//2) (cae_t_corr_s1 modes 0 / 2; backward: cae_t_wgrad_s1
-    and the data gradients of modes 1 / 3)."""
+    reflect padding, synthesis = ConvTranspose2d(stride 1, padding k//2) (_conv_s1_forward / _conv_s1_backward)."""
 
     @staticmethod
     def forward(ctx, x, synthesis, ks, act, w, b):
-        L = _L()
-        n, c, h, wd = x.shape
-        cp, dev = _pad32(c), x.device
-        a16, _ = _from_nchw(x, cp)
-        wp = _pack(w, 0 if synthesis else 1, ks)
-        bp = _bias_p(b, cp, dev)
-        out32 = torch.empty((n, h, wd, cp), dtype=torch.float32, device=dev)
-        out16 = torch.empty((n, h, wd, cp), dtype=torch.bfloat16, device=dev) if act else None
-        _lib.check(L.cae_t_corr_s1(a16.data_ptr(), n, h, wd, cp, wp.data_ptr(), ks, 2 if synthesis else 0, out32.data_ptr(),
-                                   _ptr(out16), cp, _ptr(bp), act, _st()))
+        c = x.shape[1]
+        a16, _ = _from_nchw(x, _pad32(c))
+        out32, out16 = _conv_s1_forward(a16, w, b, ks, act, synthesis, True, bool(act))
         ctx.a16, ctx.out16, ctx.w = a16, out16, w.detach()
         ctx.cfg = (bool(synthesis), int(ks), int(act), b is not None, c)
         return _to_nchw(out32, c)
 
     @staticmethod
     def backward(ctx, g):
-        L = _L()
         synthesis, ks, act, has_bias, c = ctx.cfg
-        a16 = ctx.a16
-        n, h, wd, cp = a16.shape
-        dev = g.device
-        P = ks // 2
+        cp = ctx.a16.shape[3]
         if act:  # through the activation on the fp32 gradient (one rounding)
-            g32 = _from_nchw(g, cp, want16=False, want32=True)[1]
-            gu16 = _act_backward(None, g32, 0, ctx.out16, act)
+            gu16 = _act_backward(None, _from_nchw(g, cp, want16=False, want32=True)[1], 0, ctx.out16, act)
         else:
             gu16 = _from_nchw(g, cp)[0]
-        gwp = torch.empty((ks * ks, cp, cp), dtype=torch.float32, device=dev)
-        if synthesis:
-            _lib.check(L.cae_t_wgrad_s1(gu16.data_ptr(), n, h, wd, cp, a16.data_ptr(), cp, ks, 0, gwp.data_ptr(), _st()))
-        else:
-            _lib.check(L.cae_t_wgrad_s1(a16.data_ptr(), n, h, wd, cp, gu16.data_ptr(), cp, ks, 1, gwp.data_ptr(), _st()))
-        g_w = _weight_grad(gwp, (c, c), ks)
-        g_b = _colsum(gu16, c) if has_bias else None
-        if synthesis:
-            wd_p = _pack(ctx.w, 1, ks)
-            gx32 = torch.empty((n, h, wd, cp), dtype=torch.float32, device=dev)
-            _lib.check(L.cae_t_corr_s1(gu16.data_ptr(), n, h, wd, cp, wd_p.data_ptr(), ks, 3, gx32.data_ptr(), None, cp, None, 0,
-                                       _st()))
-            gx = _to_nchw(gx32, c)
-        else:  # extended domain, then the reflect fold
-            wd_p = _pack(ctx.w, 0, ks)
-            gext = torch.empty((n, h + 2 * P, wd + 2 * P, cp), dtype=torch.float32, device=dev)
-            _lib.check(L.cae_t_corr_s1(gu16.data_ptr(), n, h, wd, cp, wd_p.data_ptr(), ks, 1, gext.data_ptr(), None, cp, None, 0,
-                                       _st()))
-            gx16 = torch.empty((n, h, wd, cp), dtype=torch.bfloat16, device=dev)
-            _lib.check(L.cae_t_fold_to_bf16(gext.data_ptr(), n, h, wd, P, cp, gx16.data_ptr(), _st()))
-            gx = _to_nchw(gx16.float(), c)
-        return gx, None, None, None, g_w, g_b
+        g_w, g_b, gx32, _ = _conv_s1_backward(gu16, ctx.a16, ctx.w, has_bias, synthesis)
+        if not synthesis:  # extended domain: the reflect fold
+            gx32 = _fold_to_bf16(gx32, ks // 2).float()
+        return _to_nchw(gx32, c), None, None, None, g_w, g_b
 
 
 class _ConvS2Fn(torch.autograd.Function):
@@ -735,40 +771,17 @@ class _ConvS2Fn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, ks, w, b):
-        L = _L()
-        n, c, h, wd = x.shape
-        cout = w.shape[0]
-        cin_p, cout_p, dev = _pad32(c), _pad32(cout), x.device
-        oh, ow = (h + 1) // 2, (wd + 1) // 2
-        a16, _ = _from_nchw(x, cin_p)
-        wp = _pack(w, 1, ks)
-        bp = _bias_p(b, cout_p, dev)
-        z32 = torch.empty((n, oh, ow, cout_p), dtype=torch.float32, device=dev)
-        _lib.check(L.cae_t_conv_forward_act(a16.data_ptr(), n, h, wd, cin_p, wp.data_ptr(), ks, z32.data_ptr(), None, cout_p,
-                                            _ptr(bp), 0, _st()))
-        ctx.a16, ctx.w = a16, w.detach()
-        ctx.cfg = (int(ks), b is not None, c, cout, oh, ow)
-        return _to_nchw(z32, cout)
+        a16, _ = _from_nchw(x, _pad32(x.shape[1]))
+        z32, _ = _conv_fwd(a16, *_pack_bias(w, b, 1, ks), 0, True)
+        ctx.a16, ctx.w, ctx.cfg = a16, w.detach(), (int(ks), b is not None)
+        return _to_nchw(z32, w.shape[0])
 
     @staticmethod
     def backward(ctx, g):
-        L = _L()
-        ks, has_bias, c, cout, oh, ow = ctx.cfg
-        a16 = ctx.a16
-        n, h, wd, cin_p = a16.shape
-        cout_p, dev, P, kk = _pad32(cout), g.device, ks // 2, ks * ks
-        g16 = _from_nchw(g, cout_p)[0]
-        gw = torch.empty((kk, cin_p, cout_p), dtype=torch.float32, device=dev)
-        _lib.check(L.cae_t_wgrad(a16.data_ptr(), n, h, wd, cin_p, g16.data_ptr(), oh, ow, cout_p, ks, 1, gw.data_ptr(), _st()))
-        g_w = _weight_grad(gw, (cout, c), ks)
-        g_b = _colsum(g16, cout) if has_bias else None
-        wp_d = _pack(ctx.w, 0, ks)
-        gext = torch.empty((n, h + 2 * P, wd + 2 * P, cin_p), dtype=torch.float32, device=dev)
-        _lib.check(L.cae_t_conv_dgrad_ext(g16.data_ptr(), n, oh, ow, cout_p, wp_d.data_ptr(), ks, h, wd, gext.data_ptr(), cin_p,
-                                          _st()))
-        gx16 = torch.empty((n, h, wd, cin_p), dtype=torch.bfloat16, device=dev)
-        _lib.check(L.cae_t_fold_to_bf16(gext.data_ptr(), n, h, wd, P, cin_p, gx16.data_ptr(), _st()))
-        return _to_nchw(gx16.float(), c), None, g_w, g_b
+        ks, has_bias = ctx.cfg
+        cout, c = ctx.w.shape[0], ctx.w.shape[1]
+        g_w, g_b, gext = _conv_s2_backward(_from_nchw(g, _pad32(cout))[0], ctx.a16, ctx.w, has_bias)
+        return _to_nchw(_fold_to_bf16(gext, ks // 2).float(), c), None, g_w, g_b
 
 
 class _GdnFn(torch.autograd.Function):
@@ -800,10 +813,6 @@ def _gdn_params(g, c: int):
     return beta_p, gamma_p
 
 
-def _torch_act(t: torch.Tensor, act: int) -> torch.Tensor:
-    return t if not act else (torch.nn.functional.leaky_relu(t, 0.01) if act == 1 else torch.relu(t))
-
-
 class _BatchNormFn(torch.autograd.Function):
     """nn.BatchNorm2d in training mode on an NCHW fp32 tensor: batch statistics (biased variance for the normalisation, as
     torch) by cae_t_bn_moments, y = x w rstd + (b - mean w rstd) by cae_t_bn_affine; the backward is the same pair of kernels
@@ -811,46 +820,32 @@ class _BatchNormFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, bias, eps):
-        L = _L()
         x = x.detach().float().contiguous()
         n, c, h, w = x.shape
-        dev = x.device
-        s1 = torch.empty(c, dtype=torch.float64, device=dev)
-        s2 = torch.empty(c, dtype=torch.float64, device=dev)
-        _lib.check(L.cae_t_bn_moments(x.data_ptr(), x.data_ptr(), n, c, h * w, s1.data_ptr(), s2.data_ptr(), _st()))
+        s1, s2 = _bn_moments(x, x)
         m = float(n * h * w)
         mean = s1 / m
         var = (s2 / m - mean * mean).clamp_min(0.0)
         rstd = torch.rsqrt(var + eps)
-        wt = weight.detach().double() if weight is not None else torch.ones(c, dtype=torch.float64, device=dev)
-        bs = bias.detach().double() if bias is not None else torch.zeros(c, dtype=torch.float64, device=dev)
-        A = (wt * rstd).float().contiguous()
-        C = (bs - mean * wt * rstd).float().contiguous()
-        y = torch.empty_like(x)
-        _lib.check(L.cae_t_bn_affine(x.data_ptr(), None, n, c, h * w, A.data_ptr(), None, C.data_ptr(), y.data_ptr(), _st()))
+        wt = weight.detach().double() if weight is not None else torch.ones(c, dtype=F64, device=x.device)
+        bs = bias.detach().double() if bias is not None else torch.zeros(c, dtype=F64, device=x.device)
+        y = _bn_affine(x, None, (wt * rstd).float().contiguous(), None, (bs - mean * wt * rstd).float().contiguous())
         ctx.x, ctx.stats, ctx.has = x, (mean, rstd, wt, m), (weight is not None, bias is not None)
         ctx.mark_non_differentiable(mean, var)
         return y, mean, var
 
     @staticmethod
     def backward(ctx, dy, _gm, _gv):
-        L = _L()
         x = ctx.x
         mean, rstd, wt, m = ctx.stats
-        n, c, h, w = x.shape
-        dev = x.device
         dy = dy.detach().float().contiguous()
-        s1 = torch.empty(c, dtype=torch.float64, device=dev)
-        s2 = torch.empty(c, dtype=torch.float64, device=dev)
-        _lib.check(L.cae_t_bn_moments(dy.data_ptr(), x.data_ptr(), n, c, h * w, s1.data_ptr(), s2.data_ptr(), _st()))
+        s1, s2 = _bn_moments(dy, x)
         sdyx = (s2 - mean * s1) * rstd  # sum dy xhat
         # dx = w rstd (dy - sum(dy) / m - xhat sum(dy xhat) / m),  xhat = (x - mean) rstd
         A = (wt * rstd).float().contiguous()
         B = (-wt * rstd * rstd * sdyx / m).float().contiguous()
         C = (wt * rstd * (-s1 / m + mean * rstd * sdyx / m)).float().contiguous()
-        dx = torch.empty_like(x)
-        _lib.check(L.cae_t_bn_affine(dy.data_ptr(), x.data_ptr(), n, c, h * w, A.data_ptr(), B.data_ptr(), C.data_ptr(),
-                                     dx.data_ptr(), _st()))
+        dx = _bn_affine(dy, x, A, B, C)
         has_w, has_b = ctx.has
         return dx, (sdyx.float() if has_w else None), (s1.float() if has_b else None), None
 
@@ -969,8 +964,7 @@ def _track_inputs(track, units, synthesis: bool):
                 or any(isinstance(m, nn.Dropout2d) and m.p > 0 for m in u.model)):
             return None, None  # composed per operation: _composed_track
         conv = u.main
-        has_gdn = u.gdn is not None
-        specs.append(LayerSpec(conv.in_channels, conv.out_channels, conv.kernel_size, conv.bias is not None, has_gdn,
+        specs.append(LayerSpec(conv.in_channels, conv.out_channels, conv.kernel_size, conv.bias is not None, u.gdn is not None,
                                act=u.act_code, has_pre=u.pre is not None))
         if u.pre is not None:  # LeakyReLU / ReLU units: the stride-1 convolution in front (same bias setting as the layer)
             tensors.append(u.pre.weight)
@@ -979,14 +973,8 @@ def _track_inputs(track, units, synthesis: bool):
         tensors.append(conv.weight)
         if conv.bias is not None:
             tensors.append(conv.bias)
-        if has_gdn:
-            g = u.gdn
-            c, cp = conv.out_channels, _pad32(conv.out_channels)
-            beta = g.beta_reparam(g.beta)      # LowerBound gradient rule inside (entropy._LowerBoundFn)
-            gamma = g.gamma_reparam(g.gamma)
-            beta_p = torch.cat([beta, beta.new_ones(cp - c)]) if cp > c else beta
-            gamma_p = torch.nn.functional.pad(gamma, (0, cp - c, 0, cp - c)) if cp > c else gamma
-            tensors.extend([beta_p, gamma_p])
+        if u.gdn is not None:
+            tensors.extend(_gdn_params(u.gdn, conv.out_channels))
     return tuple(specs), tensors
 
 
