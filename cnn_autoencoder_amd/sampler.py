@@ -1,0 +1,257 @@
+"""Training input on the device: sample and augment patches out of a pool of uint8 tiles in HBM.
+
+Stands where the reference's ``train_data`` / ``get_zarr_transform`` (utils/datasets/_augs.py:197-264, label_density == 0)
+stand: ToTensor, AddGaussianNoise(0, 0.001), RandomCrop(pad_if_needed) or CenterCrop, Normalize(0.5, 0.5) and a bilinear
+RandomRotation(30), but for a whole batch in one HIP kernel (``cae_t_sample_patches``, contract in include/cae_hip.h)
+that writes the fp32 NCHW batch ``train.train_step`` takes.  The random draws (tile, offsets, angle) are host code with
+torchvision's policies; the per-pixel work, the Gaussian noise included (a counter-based Philox4x32-10 stream), is the
+kernel's.
+
+Under several ranks every rank builds its own sampler and passes ``draw`` / ``sample`` a generator seeded per rank (and
+a per-rank ``seed`` for the noise): the sampler itself shares nothing between ranks.
+"""
+from __future__ import annotations
+
+import math
+from typing import Optional, Sequence
+
+import numpy as np
+import torch
+import torch.nn.functional as F
+
+from . import _lib
+
+_M64 = (1 << 64) - 1
+
+
+def _splitmix64(x: int) -> int:
+    x = (x + 0x9E3779B97F4A7C15) & _M64
+    x = ((x ^ (x >> 30)) * 0xBF58476D1CE4E5B9) & _M64
+    x = ((x ^ (x >> 27)) * 0x94D049BB133111EB) & _M64
+    return x ^ (x >> 31)
+
+
+def philox_normals(seed: int, sample: np.ndarray, pixel: np.ndarray) -> np.ndarray:
+    """The four standard normals of the contract for every (sample index, patch pixel index) pair: Philox4x32-10 in
+    exact integer arithmetic, Box-Muller in float64.  Returns float64 [..., 4].  (Host code: the values force_torch
+    uploads.)"""
+    c = [np.asarray(sample, dtype=np.uint64) & np.uint64(0xFFFFFFFF), np.asarray(pixel, dtype=np.uint64) & np.uint64(0xFFFFFFFF)]
+    c[0], c[1] = np.broadcast_arrays(c[0], c[1])
+    c += [np.zeros_like(c[0]), np.zeros_like(c[0])]
+    k0, k1 = seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF
+    m32 = np.uint64(0xFFFFFFFF)
+    for _ in range(10):
+        p0, p1 = np.uint64(0xD2511F53) * c[0], np.uint64(0xCD9E8D57) * c[2]  # 32 x 32 -> 64 bits, exact in uint64
+        c = [(p1 >> np.uint64(32)) ^ c[1] ^ np.uint64(k0), p1 & m32, (p0 >> np.uint64(32)) ^ c[3] ^ np.uint64(k1), p0 & m32]
+        k0, k1 = (k0 + 0x9E3779B9) & 0xFFFFFFFF, (k1 + 0xBB67AE85) & 0xFFFFFFFF
+    u = [(w.astype(np.float64) + 0.5) * 2.0 ** -32 for w in c]
+    out = np.empty(c[0].shape + (4,), dtype=np.float64)
+    for pair in (0, 1):
+        r = np.sqrt(-2.0 * np.log(u[2 * pair]))
+        out[..., 2 * pair] = r * np.cos(2.0 * np.pi * u[2 * pair + 1])
+        out[..., 2 * pair + 1] = r * np.sin(2.0 * np.pi * u[2 * pair + 1])
+    return out
+
+
+class PatchSampler:
+    """Patches of ``patch_size`` from ``pool``, uint8 ``[T, H, W, C]`` (``[T, H, W]``: one channel), 1 <= C <= 4.
+
+    The argument names and defaults follow ``get_zarr_transform``: ``data_mode`` 'train' (random crop, padded where a tile
+    is smaller than the patch) or 'test' (centre crop, tiles in order); ``add_noise`` adds N(0, noise_std^2) and clips to
+    [0, 1]; ``normalize`` maps to [-1, 1]; ``rotation`` turns every patch by an angle uniform in [-degrees, degrees].
+    ``tile_hw`` (``[T, 2]``) gives the valid rows and columns of each tile where the pool pads ragged tiles; padding is
+    never sampled as image.  ``seed`` keys the noise.  ``force_torch=True`` computes the same contract with torch ops on
+    the pool's device (the comparison of tools/bench_sampler.py; it is not a fallback: nothing selects it but this flag).
+
+    Iterating yields ``steps_per_epoch`` batches ``(x, x)`` of ``batch_size`` patches.
+    """
+
+    def __init__(self, pool, patch_size: int, data_mode: str = 'train', add_noise: bool = False, noise_std: float = 0.001,
+                 normalize: bool = False, rotation: bool = False, degrees: float = 30.0, seed: int = 0,
+                 force_torch: bool = False, tile_hw=None, batch_size: int = 16, steps_per_epoch: Optional[int] = None):
+        pool = torch.as_tensor(pool)
+        if pool.dim() == 3:
+            pool = pool[..., None]
+        if pool.dim() != 4 or pool.dtype != torch.uint8:
+            raise ValueError(f'the pool is uint8 [T, H, W, C], got {pool.dtype} {tuple(pool.shape)}')
+        if not 1 <= pool.shape[3] <= 4 or min(pool.shape[:3]) < 1:
+            raise ValueError(f'the pool needs at least one tile and 1 to 4 channels, got {tuple(pool.shape)}')
+        if 'train' in data_mode:
+            self.data_mode = 'train'
+        elif 'test' in data_mode:
+            self.data_mode = 'test'
+        else:
+            raise ValueError(f"data_mode is 'train' or 'test', got {data_mode!r}")
+        if int(patch_size) < 1:
+            raise ValueError(f'patch_size {patch_size}')
+        if not (noise_std >= 0.0 and math.isfinite(noise_std)):
+            raise ValueError(f'noise_std {noise_std}')
+        self.pool = pool.contiguous()
+        self.T, self.H, self.W, self.C = (int(v) for v in self.pool.shape)
+        self.patch_size = int(patch_size)
+        self.add_noise, self.noise_std = bool(add_noise), float(noise_std)
+        self.normalize, self.rotation, self.degrees = bool(normalize), bool(rotation), float(degrees)
+        self.seed = int(seed) & _M64
+        self.force_torch = bool(force_torch)
+        if tile_hw is None:
+            self.tile_hw = torch.tensor([[self.H, self.W]], dtype=torch.int32).repeat(self.T, 1)
+            self._ragged = False
+        else:
+            self.tile_hw = torch.as_tensor(tile_hw).to(torch.int32).cpu().reshape(self.T, 2).contiguous()
+            if bool((self.tile_hw < 1).any()) or bool((self.tile_hw > torch.tensor([self.H, self.W])).any()):
+                raise ValueError('tile_hw entries lie in [1, H] x [1, W]')
+            self._ragged = True
+        self.batch_size = int(batch_size)
+        self.steps_per_epoch = int(steps_per_epoch) if steps_per_epoch is not None else -(-self.T // self.batch_size)
+        self._batch = 0      # batches sampled so far: varies the noise seed
+        self._next_tile = 0  # 'test': the next tile in order
+        self._dev = None     # (pool, tile_hw) on the device, made on first use
+
+    # ---- construction from slides ------------------------------------------------------------------------------------
+    @classmethod
+    def from_zarr(cls, stores: Sequence[str], data_group: str = '0/0', patch_size: int = 128, **kwargs) -> 'PatchSampler':
+        """A sampler over every chunk of the ``data_group`` array (Y, X, C uint8; or Y, X) of each store, read through
+        ``ZarrArray.__getitem__``.  One tile per chunk: all stores share one chunk shape; the chunks on the lower and
+        right edges of an image are padded to it (``ZarrArray.pad_chunk``) and keep their valid size."""
+        from .zarrio import ZarrArray
+        tiles, hw, shape = [], [], None
+        for store in ([stores] if isinstance(stores, str) else stores):
+            arr = ZarrArray.open(store, data_group)
+            if len(arr.shape) not in (2, 3) or arr.dtype != np.uint8:
+                raise ValueError(f'{store}: expected a uint8 (Y, X, C) or (Y, X) array, got {arr.dtype} {arr.shape}')
+            if len(arr.shape) == 3 and arr.chunks[2] != arr.shape[2]:
+                raise ValueError(f'{store}: chunks must hold all channels of a pixel')
+            if shape is None:
+                shape = arr.chunks
+            elif arr.chunks != shape:
+                raise ValueError(f'{store}: chunk shape {arr.chunks} differs from {shape}; tiles must be of equal shape')
+            for idx in arr.chunk_indices():
+                data = arr[arr.chunk_slices(idx)]
+                hw.append(data.shape[:2])
+                tiles.append(arr.pad_chunk(data))
+        if not tiles:
+            raise ValueError('no store given')
+        return cls(np.stack(tiles), patch_size, tile_hw=np.asarray(hw, dtype=np.int32), **kwargs)
+
+    # ---- host: the random draws --------------------------------------------------------------------------------------
+    def draw(self, n: int, generator: Optional[torch.Generator] = None):
+        """``(tile, y0, x0, angle)`` of ``n`` patches with torchvision's policies; host code, no GPU needed.
+        'train': the tile is uniform; per axis, the offset is uniform in [0, dim - ps] where the tile's valid dim >= ps and
+        in [-(ps - dim), 0] where it is smaller (``RandomCrop(pad_if_needed)`` pads both sides by ps - dim).  'test': tiles in
+        order (continuing where the last draw stopped) and the ``CenterCrop`` offset, int(round((dim - ps) / 2)) for
+        dim >= ps, else -((ps - dim) // 2).  ``angle`` (degrees, float64) is uniform in [-degrees, degrees] with
+        ``rotation``, else None.  The same generator state gives the same draw."""
+        n, ps = int(n), self.patch_size
+        if self.data_mode == 'train':
+            r = torch.randint(0, 1 << 62, (3, n), generator=generator, dtype=torch.int64)
+            tile = r[0] % self.T
+            dims = self.tile_hw.to(torch.int64)[tile]  # [n, 2]
+            span = (dims - ps).abs() + 1
+            off = r[1:].t() % span + torch.clamp(dims - ps, max=0)
+        else:
+            tile = (self._next_tile + torch.arange(n, dtype=torch.int64)) % self.T
+            self._next_tile = int((self._next_tile + n) % self.T)
+            dims = self.tile_hw.to(torch.int64)[tile]
+            # torchvision's center_crop: int(round((dim - ps) / 2.0)) (Python's round: half to even), padding (ps - dim) // 2
+            off = torch.tensor([[int(round((d - ps) / 2.0)) if d >= ps else -((ps - d) // 2) for d in row]
+                                for row in dims.tolist()], dtype=torch.int64).reshape(n, 2)
+        angle = None
+        if self.rotation:
+            angle = (torch.rand(n, generator=generator, dtype=torch.float64) * 2.0 - 1.0) * self.degrees
+        return tile.to(torch.int32), off[:, 0].to(torch.int32).contiguous(), off[:, 1].to(torch.int32).contiguous(), angle
+
+    # ---- device: the batch -------------------------------------------------------------------------------------------
+    def _device_pool(self):
+        if self._dev is None:
+            dev = self.pool.device if self.pool.is_cuda else _lib.require_gpu()
+            self._dev = (self.pool.to(dev), self.tile_hw.to(dev) if self._ragged else None)
+        return self._dev
+
+    def gather(self, tile, y0, x0, angle=None, noise_seed: Optional[int] = None, sample_base: int = 0) -> torch.Tensor:
+        """The ``[n, C, ps, ps]`` fp32 batch of the given draw on the device.  ``angle`` in degrees (None: no rotation).
+        ``noise_seed`` keys the noise of this batch (None: the sampler's ``seed``); it is used with ``add_noise`` only.
+        ``sample_base`` is the index of the batch's first sample in the noise stream, so a batch can be gathered in
+        parts.  A tile index outside the pool raises ValueError before anything is launched."""
+        tile, y0, x0 = (torch.as_tensor(v).to(torch.int32).cpu().reshape(-1).contiguous() for v in (tile, y0, x0))
+        n = tile.numel()
+        if y0.numel() != n or x0.numel() != n:
+            raise ValueError('tile, y0 and x0 name one value per sample')
+        cs = None
+        if angle is not None:
+            a = torch.deg2rad(torch.as_tensor(angle, dtype=torch.float64).cpu().reshape(-1))
+            if a.numel() != n:
+                raise ValueError('one angle per sample')
+            cs = torch.stack([torch.cos(a), torch.sin(a)]).to(torch.float32)  # float64 on the host, rounded once
+        seed = self.seed if noise_seed is None else int(noise_seed) & _M64
+        std = self.noise_std if self.add_noise else 0.0
+        if self.force_torch:
+            g = self.torch_normals(n, seed, int(sample_base)) if std != 0.0 else None
+            return self._gather_torch(tile, y0, x0, cs, std, g)
+        pool, tile_hw = self._device_pool()
+        idx = torch.stack([tile, y0, x0]).to(pool.device)
+        cs_dev = cs.to(pool.device) if cs is not None else None
+        out = torch.empty((n, self.C, self.patch_size, self.patch_size), dtype=torch.float32, device=pool.device)
+        with torch.cuda.device(pool.device):
+            _lib.check(_lib.lib().cae_t_sample_patches(
+                pool.data_ptr(), self.T, self.H, self.W, self.C, tile_hw.data_ptr() if tile_hw is not None else None,
+                idx[0].data_ptr(), idx[1].data_ptr(), idx[2].data_ptr(), tile.data_ptr(),
+                cs_dev[0].data_ptr() if cs is not None else None, cs_dev[1].data_ptr() if cs is not None else None,
+                seed, int(sample_base) & 0xFFFFFFFF, std, int(self.normalize), n, self.patch_size, out.data_ptr(),
+                _lib.stream_ptr()))
+        return out
+
+    def torch_normals(self, n: int, seed: int, sample_base: int = 0) -> torch.Tensor:
+        """force_torch: the normals of a batch, ``[n, ps, ps, C]`` float32 on the pool's device, generated on the host."""
+        ps = self.patch_size
+        g = philox_normals(seed, (sample_base + np.arange(n, dtype=np.uint64))[:, None], np.arange(ps * ps, dtype=np.uint64))
+        return torch.from_numpy(g[..., :self.C].astype(np.float32)).to(self.pool.device).reshape(n, ps, ps, self.C)
+
+    def _gather_torch(self, tile, y0, x0, cs, std, g) -> torch.Tensor:
+        """The contract as torch ops on the pool's device; the Philox normals ``g`` come from the host."""
+        n, ps, dev = tile.numel(), self.patch_size, self.pool.device
+        if n and (int(tile.min()) < 0 or int(tile.max()) >= self.T):
+            raise ValueError(f'tile index outside the pool of {self.T} tiles')
+        t = tile.to(dev).long()
+        r = torch.arange(ps, device=dev)
+        iy, ix = y0.to(dev).long()[:, None] + r, x0.to(dev).long()[:, None] + r  # [n, ps]
+        hw = self.tile_hw.to(dev).long()[t]
+        vy, vx = (iy >= 0) & (iy < hw[:, :1]), (ix >= 0) & (ix < hw[:, 1:])
+        valid = (vy[:, :, None] & vx[:, None, :])[..., None]  # [n, ps, ps, 1]
+        u8 = self.pool[t[:, None, None], iy.clamp(0, self.H - 1)[:, :, None], ix.clamp(0, self.W - 1)[:, None, :]]
+        # the correctly rounded quotients as a table from the host (a device division by a scalar may multiply by 1 / 255)
+        v = torch.arange(256, dtype=torch.float32).div(255).to(dev)[u8.long()]
+        if std != 0.0:
+            v = (v + std * g).clamp_(0, 1)
+        v = torch.where(valid, v, torch.zeros((), dtype=v.dtype, device=dev))
+        if self.normalize:
+            v = (v - 0.5) / 0.5
+        p = v.permute(0, 3, 1, 2).contiguous()
+        if cs is None:
+            return p
+        c, s = cs[0].to(dev), cs[1].to(dev)
+        z = torch.zeros_like(c)
+        theta = torch.stack([torch.stack([c, -s, z], 1), torch.stack([s, c, z], 1)], 1)  # [n, 2, 3]
+        grid = F.affine_grid(theta, list(p.shape), align_corners=False)
+        return F.grid_sample(p, grid, mode='bilinear', padding_mode='zeros', align_corners=False)
+
+    def batch_seed(self, batch: int) -> int:
+        """The noise seed of the ``batch``-th sampled batch, derived from ``seed``."""
+        return _splitmix64(_splitmix64(self.seed) ^ (int(batch) & _M64))
+
+    def sample(self, n: int, generator: Optional[torch.Generator] = None) -> torch.Tensor:
+        """``draw`` then ``gather``; every call takes the next per-batch noise seed."""
+        tile, y0, x0, angle = self.draw(n, generator)
+        x = self.gather(tile, y0, x0, angle, noise_seed=self.batch_seed(self._batch))
+        self._batch += 1
+        return x
+
+    # ---- an epoch of batches, as the reference's data loader yields them -----------------------------------------------
+    def __len__(self) -> int:
+        return self.steps_per_epoch
+
+    def __iter__(self):
+        if self.data_mode == 'test':
+            self._next_tile = 0
+        for _ in range(self.steps_per_epoch):
+            x = self.sample(self.batch_size)
+            yield x, x

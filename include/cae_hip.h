@@ -427,6 +427,51 @@ int cae_t_density_forward(const float *y, const float *noise, const float *raw_p
                           float bound, float *out, float *lik, void *stream);
 int cae_t_density_backward(const float *out, const float *g_lik, const float *g_out, const float *raw_params, int n,
                            int channels, int hw, int plain, float bound, float *g_y, float *g_raw_params, void *stream);
+/* ---- training input: sample and augment patches on the device (csrc/cae_sampler.hip) ---------------------------------
+ * Replaces the per-patch CPU transform of utils/datasets/_augs.py:197-264 (get_zarr_transform, label_density == 0:
+ * ToTensor, AddGaussianNoise(0, 0.001), RandomCrop(pad_if_needed) / CenterCrop, Normalize(0.5, 0.5), bilinear
+ * RandomRotation(30)).  The random draws stay with the caller; one launch writes the batch train_step takes.
+ *
+ * pool_dev: uint8 [tiles][h][w][c] on the device, 1 <= c <= 4.  tile_hw_dev: int32 [tiles][2], the valid rows and
+ * columns of each tile (the rest is storage padding and counts as outside the image), or NULL: every tile is h x w.
+ * Per sample, on the device: int32 tile_dev, y0_dev, x0_dev; optionally float32 cos_dev, sin_dev of the angle (the host
+ * computes them in float64 and rounds once; both NULL = no rotation).  out_dev: float [n][c][ps][ps].
+ *
+ * Patch value.  For patch pixel (py, px) and channel ch, the image pixel is (y0+py, x0+px) of tile `tile`.
+ *   - Inside the image, v = clamp(u8 / 255 + noise_std * g, 0, 1).
+ *   - Outside the image, v = 0.  This is pad_if_needed's constant fill.  The reference adds noise before the crop, so
+ *     padding carries no noise.
+ *   - u8 / 255 is the correctly rounded float32 quotient, as torch's .div(255) gives (IEEE division, no reciprocal
+ *     multiply).
+ *   - Then p = normalize ? (v - 0.5) / 0.5 : v.
+ * Noise.  g is a standard normal from a counter-based generator, Philox4x32-10.
+ *   - The key is the two halves of `seed` (low word first).
+ *   - The counter is (sample_base + sample index, py * ps + px, 0, 0).
+ *   - The four output words map through u = (word + 0.5) * 2^-32 and two Box-Muller pairs to four normals: with
+ *     r = sqrt(-2 ln u_0), normals 0 and 1 are r cos(2 pi u_1) and r sin(2 pi u_1); words 2 and 3 give normals 2 and 3
+ *     likewise.  Channel ch takes normal ch.
+ *   - The accurate logf / log1pf / sincospif are used, not the fast intrinsics.  noise_std == 0 means no noise.
+ * The value at a patch pixel therefore does not depend on which output pixel reads it, so rotation interpolates one
+ * consistent noisy patch, as in the reference.  Results are bitwise repeatable and independent of the launch shape;
+ * sample_base lets a batch be produced in several calls.
+ * Rotation.  The reference rotates the cropped, normalised patch with zero fill.  With cx = cy = (ps - 1) / 2, output
+ * (i, j) reads the patch at
+ *     sx = cx + cos a * (j - cx) - sin a * (i - cy)
+ *     sy = cy + sin a * (j - cx) + cos a * (i - cy)
+ * and takes the four bilinear taps of p.  A tap outside [0, ps) contributes 0, which is 0 after normalisation, i.e.
+ * mid-grey.  A positive angle turns the picture counter-clockwise as displayed.  With the rotation pointers NULL, the
+ * output is p itself, bit for bit.
+ *
+ * CAE_ERR_ARG before any launch: c outside 1..4, ps outside 1..16384, n < 0, tiles / h / w < 1 (h, w at most 2^24), a NULL
+ * pool / tile / y0 / x0 / out pointer, only one of cos_dev / sin_dev, a negative or non-finite noise_std, more than
+ * 2^31 - 1 blocks of 256 work items, and -- when tile_host, a HOST copy of tile_dev, is given -- a tile index outside
+ * [0, tiles).  The kernels fault on no device-side value either: a tile index outside [0, tiles) reads as an empty image
+ * (all padding), offsets are clamped to where they select only padding, tile_hw entries to [0, h] x [0, w]. */
+int cae_t_sample_patches(const uint8_t *pool_dev, int tiles, int h, int w, int c, const int32_t *tile_hw_dev,
+                         const int32_t *tile_dev, const int32_t *y0_dev, const int32_t *x0_dev, const int32_t *tile_host,
+                         const float *cos_dev, const float *sin_dev, uint64_t seed, uint32_t sample_base, float noise_std,
+                         int normalize, int n, int ps, float *out_dev, void *stream);
+
 /* compressai NonNegativeParametrizer (GDN beta / gamma; layers/gdn.py via _autoencoders.py GDN units) under autograd:
  * out = max(x, bound)^2 - pedestal;  g_x = g 2 max(x, bound) where x >= bound or that value is negative (LowerBound rule). */
 int cae_t_reparam_forward(const float *x, long n, float bound, float pedestal, float *out, void *stream);
