@@ -801,6 +801,9 @@ __global__ void __launch_bounds__(512, 1) conv_first_f16_kernel(const LayerArgs 
         }
     };
     char *whalo = hbuf + wave * G::WAVE_HALO_BYTES;
+    // float tiles enter the split format here, without a layout conversion in front: the range guard of
+    // nchw_to_c8s_kernel (|v| > F16_MAX or NaN; the maxima of the split stores drop a NaN) applies to them as read
+    bool bad = false;
     auto commit = [&]() {  // exact x/255 through the table
 #pragma unroll
         for (int k = 0; k < G::NPOS; ++k) {
@@ -811,6 +814,7 @@ __global__ void __launch_bounds__(512, 1) conv_first_f16_kernel(const LayerArgs 
                 for (int c = 0; c < 4; ++c) {
                     float val;
                     if constexpr (U8) val = lut[raw[k][c]]; else val = raw[k][c];
+                    if constexpr (!U8) bad |= !(__builtin_fabsf(val) <= F16_MAX);  // (absent channels repeat the last one)
                     v[c] = c <= c_last ? val : 0.0f;
                 }
                 *(f32x4 *)(whalo + i * 16) = v;
@@ -880,6 +884,8 @@ __global__ void __launch_bounds__(512, 1) conv_first_f16_kernel(const LayerArgs 
         const int oy = ty * TY + 2 * wave + (m >> 4), ox = tx * TX + (m & 15);
         store_tiles_f16<CT, false, !GDN>(acc, p, n, oy, ox, h, oy < p.OH && ox < p.OW);
     }
+    if constexpr (!U8)
+        if (bad) *p.flag = 1;
 }
 
 // ---- last-layer product map ("pmap") ------------------------------------------------------------------------
