@@ -1,4 +1,6 @@
 // C ABI of the training path (include/cae_hip.h, "training"): stateless launches on caller-owned device buffers.
+// The launch decisions of the MFMA kernels -- taps, halo, LDS, kernel, grid -- are each made once, in the helpers of the
+// anonymous namespace; tests/native/train_launches.cpp records what every entry point launches, without a GPU.
 #include "cae_hip.h"
 #include "cae_internal.hpp"
 #include "cae_launch.hpp"
@@ -9,6 +11,7 @@
 #include <atomic>
 #include <map>
 #include <mutex>
+#include <type_traits>
 
 using namespace cae;
 using namespace cae::tr;
@@ -38,126 +41,201 @@ const void *zero_page() {
 
 unsigned ew_grid(size_t total) {
     const size_t b = (total + 255) / 256;
-    return (unsigned)std::min<size_t>(std::max<size_t>(b, 1), 256 * 8 * 4);
+    return (unsigned)std::min<size_t>(std::max<size_t>(b, 1), TRAIN_CUS * 8 * 4);
 }
 
-bool bad_channels(int c) { return c < 32 || c % 32 != 0 || c > 192; }
+// raises the kernel's dynamic LDS limit where it asks for LDS, launches it, -> CAE_*
+template <class... P, class... A>
+int launch(void (*kern)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t st, A... args) {
+    if (lds > 0) CAE_TRY(ensure_lds((const void *)kern, (int)lds));
+    hipLaunchKernelGGL(kern, grid, block, lds, st, args...);
+    HIP_TRY(hipGetLastError());
+    return CAE_OK;
+}
+
+// an element-wise kernel: blocks of 256 threads striding over `total` elements
+template <class... P, class... A>
+int launch_ew(void (*kern)(P...), size_t total, void *stream, A... args) {
+    return launch(kern, dim3(ew_grid(total)), dim3(256), 0, (hipStream_t)stream, args...);
+}
+
+bool bad_channels(int c) { return c < 32 || c % 32 != 0 || c > 32 * MAX_CT; }
+
+int ceil_div(int a, int b) { return (a + b - 1) / b; }
+
+// ceil(2^32 / d): __umulhi(x, .) is the exact quotient x / d of the piece indices the kernels divide
+unsigned recip32(int d) { return (unsigned)(((1ull << 32) + (unsigned)d - 1) / (unsigned)d); }
+
+// f(std::integral_constant<int, CT>) for the run-time tile count ct = 1 .. N (N for anything above)
+template <int N, class F>
+int for_tiles(int ct, F f) {
+    if constexpr (N > 1)
+        if (ct < N) return for_tiles<N - 1>(ct, f);
+    return f(std::integral_constant<int, N>());
+}
+
+// ---- taps ----
+struct TapList {
+    int n = 0;
+    short dy[MAX_TAPS] = {}, dx[MAX_TAPS] = {}, wt[MAX_TAPS] = {};  // input offset and weight index (ky * k + kx) per tap
+};
+
+// Appends the taps (ky, kx) of a k x k window whose offsets (oy + s ky, ox + s kx) are multiples of `step`, with
+// offset / step.  step 1: the whole window -- o = -P, s = 1: d = k - P;  o = 0, s = -1: d = -k;  o = P, s = -1: d = P - k.
+// step 2, s = -1, o = parity + shift: the taps of one output parity of the stride-2 transpose, d = (parity + shift - k) / 2.
+void add_taps(TapList &t, int ks, int oy, int ox, int s, int step) {
+    for (int ky = 0; ky < ks; ++ky) {
+        if ((oy + s * ky) % step != 0) continue;
+        for (int kx = 0; kx < ks; ++kx) {
+            if ((ox + s * kx) % step != 0) continue;
+            t.dy[t.n] = (short)((oy + s * ky) / step);
+            t.dx[t.n] = (short)((ox + s * kx) / step);
+            t.wt[t.n] = (short)(ky * ks + kx);
+            ++t.n;
+        }
+    }
+}
+
+void set_taps(GGArgs &a, const TapList &t) {
+    a.ntaps = t.n;
+    std::copy(t.dy, t.dy + MAX_TAPS, a.dy);
+    std::copy(t.dx, t.dx + MAX_TAPS, a.dx);
+    std::copy(t.wt, t.wt + MAX_TAPS, a.wt);
+}
+
+// ---- halo ----
+// logical positions per tile: 16 x 16 in gather_gemm / gg8 / gg8t (i0 = ty * 16, j0 = tx * 16 there), 8 x 16 in wgrad / wgrad8
+constexpr int GG_TILE = 16, WG_TILE_ROWS = 8, WG_TILE_COLS = 16;
+
+// Bounding box of the input pixels a tile of rows x cols positions (stride S apart) reads through the taps, into the
+// dymin / dxmin / HR / HC / m_hc of a GGArgs or WGArgs.
+template <class Args>
+void set_halo(Args &a, const TapList &t, int S, int rows, int cols) {
+    int dymin = t.dy[0], dymax = t.dy[0], dxmin = t.dx[0], dxmax = t.dx[0];
+    for (int i = 1; i < t.n; ++i) {
+        dymin = std::min<int>(dymin, t.dy[i]);
+        dymax = std::max<int>(dymax, t.dy[i]);
+        dxmin = std::min<int>(dxmin, t.dx[i]);
+        dxmax = std::max<int>(dxmax, t.dx[i]);
+    }
+    a.dymin = dymin;
+    a.dxmin = dxmin;
+    a.HR = S * (rows - 1) + (dymax - dymin) + 1;
+    a.HC = S * (cols - 1) + (dxmax - dxmin) + 1;
+    a.m_hc = recip32(a.HC);
+}
+
+// ---- LDS ----
+// LDS-DMA instructions (1 KiB each) of a halo of nq 8-channel quarters
+int halo_instr(int nq, int HR, int HC) { return (nq * HR * HC + 63) / 64; }
+
+// bytes of one staged slice: the halo of nq quarters + the weights of every tap, NT n-tiles, nq / 2 k-steps (1 KiB each)
+size_t slice_bytes(int nq, int HR, int HC, int ntaps, int NT) {
+    return ((size_t)halo_instr(nq, HR, HC) + (size_t)ntaps * NT * (nq / 2)) * 1024;
+}
+
+// quarters per slice of the pipelined form (a slice twice in the LDS): 4 = a 32-channel chunk, 2 = half, 0 = does not fit
+int pick_nq(int HR, int HC, int ntaps, int NT, int max_halo_instr) {
+    for (int nq : {4, 2})
+        if (2 * slice_bytes(nq, HR, HC, ntaps, NT) <= LDS_BUDGET && halo_instr(nq, HR, HC) <= max_halo_instr) return nq;
+    return 0;
+}
+
+// samples a block of the 8-wave kernels walks: enough blocks for two rounds over the CUs, the rest of the batch amortises
+// a block's prologue
+int samples_per_block(int n, size_t blocks_per_sample) {
+    return (int)std::min<size_t>(std::max<size_t>((size_t)n * blocks_per_sample / (2 * TRAIN_CUS), 1), (size_t)n);
+}
+
+// ---- gather-GEMM launches ----
+// the tile grid over the logical positions, and the zero page
+int set_tiles(GGArgs &a) {
+    a.tiles_x = ceil_div(a.LW, GG_TILE);
+    a.tiles_y = ceil_div(a.LH, GG_TILE);
+    a.zero = zero_page();
+    return a.zero ? CAE_OK : fail(CAE_ERR_NOMEM, "zero page");
+}
 
 template <int NT, bool PIPE>
 int launch_gg_tp(const GGArgs &a, size_t lds, hipStream_t st) {
-    auto kern = gather_gemm_kernel<NT, PIPE>;
-    CAE_TRY(ensure_lds((const void *)kern, (int)lds));
     const unsigned grid = (unsigned)((size_t)a.N * a.tiles_x * a.tiles_y);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, a);
-    HIP_TRY(hipGetLastError());
-    return CAE_OK;
+    return launch(gather_gemm_kernel<NT, PIPE>, dim3(grid), dim3(256), lds, st, a);
 }
 
 // gg8_kernel (two waves per SIMD, compile-time taps, blocks walking several samples): the shapes of the canonical model
 template <int NT, int NQ, int NTAPS>
-int launch_gg8(GGArgs &a, hipStream_t st) {
-    auto kern = gg8_kernel<NT, NQ, NTAPS>;
-    const size_t h_instr = (size_t)(NQ * a.HR * a.HC + 63) / 64;
-    const size_t lds = 2 * (h_instr + (size_t)NTAPS * NT * (NQ / 2)) * 1024;
-    CAE_TRY(ensure_lds((const void *)kern, (int)lds));
-    // samples per block: enough blocks for two rounds over the 256 CUs, the rest of the batch amortises a block's prologue
+int launch_gg8(GGArgs a, hipStream_t st) {
     const size_t tiles = (size_t)a.tiles_x * a.tiles_y;
     const int forced = g_samples_per_block.load(std::memory_order_relaxed);
-    a.npb = forced > 0 ? std::min(forced, a.N) : (int)std::min<size_t>(std::max<size_t>((size_t)a.N * tiles / 512, 1), (size_t)a.N);
-    const unsigned grid = (unsigned)(tiles * (size_t)((a.N + a.npb - 1) / a.npb));
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, st, a);
-    HIP_TRY(hipGetLastError());
-    return CAE_OK;
+    a.npb = forced > 0 ? std::min(forced, a.N) : samples_per_block(a.N, tiles);
+    const unsigned grid = (unsigned)(tiles * (size_t)ceil_div(a.N, a.npb));
+    return launch(gg8_kernel<NT, NQ, NTAPS>, dim3(grid), dim3(512), 2 * slice_bytes(NQ, a.HR, a.HC, NTAPS, NT), st, a);
 }
 
-// -> true when a gg8 instantiation covers the launch (rc holds its result)
-bool try_gg8(GGArgs &a, int NT, hipStream_t st, int &rc) {
-    if (NT == 6 && (a.ntaps == 9 || a.ntaps == 4 || a.ntaps == 2 || a.ntaps == 1)) {
-        // 192 output channels: two launches of three n-tiles (six do not leave room for two slice buffers in the LDS)
-        int nq = 0;
-        for (int q : {4, 2}) {
-            const size_t slice = (size_t)((q * a.HR * a.HC + 63) / 64) * 1024 + (size_t)a.ntaps * 3 * (q / 2) * 1024;
-            if (2 * slice <= 160 * 1024 && (q * a.HR * a.HC + 63) / 64 <= 80) {
-                nq = q;
-                break;
-            }
-        }
-        if ((a.ntaps == 9 && nq != 2) || (a.ntaps != 9 && nq != 4)) return false;
-        for (int part = 0; part < 2; ++part) {
-            GGArgs b = a;
-            b.nq = nq;
-            b.nt0 = 3 * part;
-            b.nt_all = 6;
-            rc = a.ntaps == 9 ? launch_gg8<3, 2, 9>(b, st)
-                 : a.ntaps == 4 ? launch_gg8<3, 4, 4>(b, st)
-                 : a.ntaps == 2 ? launch_gg8<3, 4, 2>(b, st) : launch_gg8<3, 4, 1>(b, st);
-            if (rc) return true;
-        }
-        return true;
-    }
-    if (a.nq == 0 || (a.nq * a.HR * a.HC + 63) / 64 > 80) return false;
-    if (NT == 4 && a.nq == 2 && a.ntaps == 9) { rc = launch_gg8<4, 2, 9>(a, st); return true; }
-    if (NT == 4 && a.nq == 4 && a.ntaps == 4) { rc = launch_gg8<4, 4, 4>(a, st); return true; }
-    if (NT == 4 && a.nq == 4 && a.ntaps == 2) { rc = launch_gg8<4, 4, 2>(a, st); return true; }
-    if (NT == 4 && a.nq == 4 && a.ntaps == 1) { rc = launch_gg8<4, 4, 1>(a, st); return true; }
-    if (NT == 1 && a.nq == 4 && a.ntaps == 1) { rc = launch_gg8<1, 4, 1>(a, st); return true; }
-    return false;
+// all four output parities of the k = 3 transpose in one launch (gg8t_kernel): 64 output channels per block
+template <bool EXT>
+int launch_gg8t(GGArgs a, hipStream_t st) {
+    const size_t tiles = (size_t)a.tiles_x * a.tiles_y, halves = (size_t)a.Cn / 64;
+    a.npb = samples_per_block(a.N, tiles * halves);
+    const unsigned grid = (unsigned)(tiles * (size_t)ceil_div(a.N, a.npb));
+    return launch(gg8t_kernel<EXT>, dim3(grid, (unsigned)halves), dim3(512), 2 * slice_bytes(4, a.HR, a.HC, 9, 2), st, a);
 }
 
-template <int NT>
-int launch_gg_t(const GGArgs &a, size_t lds, hipStream_t st) {
-    return a.nq ? launch_gg_tp<NT, true>(a, lds, st) : launch_gg_tp<NT, false>(a, lds, st);
+// The gg8_kernel instantiations that are built: n-tiles per launch, quarters per slice, taps, and the launches the
+// output's n-tiles are split over (192 output channels go as two launches of three n-tiles: six do not leave room for
+// two slice buffers in the LDS).
+struct GG8Form {
+    int nt, nq, ntaps, parts;
+    int (*launch)(GGArgs, hipStream_t);
+};
+#define GG8_FORM(NT, NQ, NTAPS, PARTS) {NT, NQ, NTAPS, PARTS, launch_gg8<NT, NQ, NTAPS>}
+const GG8Form GG8_FORMS[] = {GG8_FORM(3, 2, 9, 2), GG8_FORM(3, 4, 4, 2), GG8_FORM(3, 4, 2, 2), GG8_FORM(3, 4, 1, 2),
+                             GG8_FORM(4, 2, 9, 1), GG8_FORM(4, 4, 4, 1), GG8_FORM(4, 4, 2, 1), GG8_FORM(4, 4, 1, 1),
+                             GG8_FORM(1, 4, 1, 1)};
+#undef GG8_FORM
+
+// the gg8 form that covers a launch whose halo is filled in, or null: gather_gemm_kernel<Cn / 32, nq != 0> runs
+const GG8Form *choose_gg8(const GGArgs &a) {
+    const int parts = a.Cn / 32 == MAX_CT ? 2 : 1, nt = a.Cn / 32 / parts;
+    const int nq = parts == 1 ? a.nq : pick_nq(a.HR, a.HC, a.ntaps, nt, GG8_HALO_INSTR);
+    if (nq == 0 || halo_instr(nq, a.HR, a.HC) > GG8_HALO_INSTR) return nullptr;
+    for (const GG8Form &f : GG8_FORMS)
+        if (f.nt == nt && f.nq == nq && f.ntaps == a.ntaps && f.parts == parts) return &f;
+    return nullptr;
 }
 
-// fills the halo / staging geometry of `a` from its tap list and launches
-int launch_gg(GGArgs &a, hipStream_t st) {
+// fills the taps and the halo / staging geometry of `a`, picks the kernel and launches
+int launch_gg(GGArgs &a, const TapList &t, hipStream_t st) {
     if (bad_channels(a.Ck) || bad_channels(a.Cn)) return fail(CAE_ERR_ARG, "channel counts must be multiples of 32, at most 192");
-    if (a.ntaps < 1 || a.ntaps > MAX_TAPS) return fail(CAE_ERR_ARG, "bad tap count");
-    int dymin = a.dy[0], dymax = a.dy[0], dxmin = a.dx[0], dxmax = a.dx[0];
-    for (int t = 1; t < a.ntaps; ++t) {
-        dymin = std::min<int>(dymin, a.dy[t]);
-        dymax = std::max<int>(dymax, a.dy[t]);
-        dxmin = std::min<int>(dxmin, a.dx[t]);
-        dxmax = std::max<int>(dxmax, a.dx[t]);
-    }
-    a.dymin = dymin;
-    a.dxmin = dxmin;
-    a.HR = a.S * 15 + (dymax - dymin) + 1;
-    a.HC = a.S * 15 + (dxmax - dxmin) + 1;
+    if (t.n < 1 || t.n > MAX_TAPS) return fail(CAE_ERR_ARG, "bad tap count");
+    set_taps(a, t);
+    set_halo(a, t, a.S, GG_TILE, GG_TILE);
     const int NT = a.Cn / 32;
-    const int pieces = 4 * a.HR * a.HC;
-    if ((pieces + 63) / 64 > 80) return fail(CAE_ERR_UNSUPPORTED, "halo too large");
-    const size_t halo = (size_t)((pieces + 63) / 64) * 1024;
-    const size_t budget = 160 * 1024 - halo;
-    a.taps_per_stage = std::min<int>(a.ntaps, (int)(budget / ((size_t)NT * 2048)));
+    if (halo_instr(4, a.HR, a.HC) > GG_HALO_INSTR) return fail(CAE_ERR_UNSUPPORTED, "halo too large");
+    // unpipelined form: the halo of a 32-channel chunk + the weights (2 KiB per tap and n-tile) of as many taps as fit
+    const size_t halo = (size_t)halo_instr(4, a.HR, a.HC) * 1024;
+    a.taps_per_stage = std::min<int>(a.ntaps, (int)((LDS_BUDGET - halo) / ((size_t)NT * 2048)));
     if (a.taps_per_stage < 1) return fail(CAE_ERR_UNSUPPORTED, "weights of one tap do not fit the LDS");
-    size_t lds = halo + (size_t)a.taps_per_stage * NT * 2048;
-    // pipelined form: a slice (32 or 16 channels: halo + the weights of all taps) twice in the LDS
-    a.nq = 0;
-    for (int nq : {4, 2}) {
-        const size_t slice = (size_t)((nq * a.HR * a.HC + 63) / 64) * 1024 + (size_t)a.ntaps * NT * (nq / 2) * 1024;
-        if (2 * slice <= 160 * 1024) {
-            a.nq = nq;
-            lds = 2 * slice;
-            break;
+    a.nq = pick_nq(a.HR, a.HC, a.ntaps, NT, GG_HALO_INSTR);
+    const size_t lds = a.nq ? 2 * slice_bytes(a.nq, a.HR, a.HC, a.ntaps, NT) : halo + (size_t)a.taps_per_stage * NT * 2048;
+    a.m_plane = recip32(a.HR * a.HC);
+    CAE_TRY(set_tiles(a));
+    if (const GG8Form *f = choose_gg8(a)) {
+        for (int part = 0; part < f->parts; ++part) {
+            GGArgs b = a;
+            if (f->parts > 1) {
+                b.nq = f->nq;
+                b.nt0 = f->nt * part;
+                b.nt_all = NT;
+            }
+            CAE_TRY(f->launch(b, st));
         }
+        return CAE_OK;
     }
-    a.m_plane = (unsigned)(((1ull << 32) + (unsigned)(a.HR * a.HC) - 1) / (unsigned)(a.HR * a.HC));
-    a.m_hc = (unsigned)(((1ull << 32) + (unsigned)a.HC - 1) / (unsigned)a.HC);
-    a.tiles_x = (a.LW + 15) / 16;
-    a.tiles_y = (a.LH + 15) / 16;
-    a.zero = zero_page();
-    if (!a.zero) return fail(CAE_ERR_NOMEM, "zero page");
-    int rc8 = CAE_OK;
-    if (try_gg8(a, NT, st, rc8)) return rc8;
-    switch (NT) {
-        case 1: return launch_gg_t<1>(a, lds, st);
-        case 2: return launch_gg_t<2>(a, lds, st);
-        case 3: return launch_gg_t<3>(a, lds, st);
-        case 4: return launch_gg_t<4>(a, lds, st);
-        case 5: return launch_gg_t<5>(a, lds, st);
-        default: return launch_gg_t<6>(a, lds, st);
-    }
+    return for_tiles<MAX_CT>(NT, [&](auto ct) {
+        constexpr int CT = decltype(ct)::value;
+        return a.nq ? launch_gg_tp<CT, true>(a, lds, st) : launch_gg_tp<CT, false>(a, lds, st);
+    });
 }
 
 // operands, shapes, strides and activation of a gather-GEMM launch; the rest of the fields zero
@@ -182,117 +260,65 @@ GGArgs gg_args(const void *in16, int n, int ih, int iw, int ck, const void *pack
     return a;
 }
 
-// strided correlation: position (i, j) <- input (2i + ky - P, 2j + kx - P), every tap
-int strided_corr(const void *in16, int n, int ih, int iw, int ck, const void *packed, int ks, int reflect, float *out32,
-                 void *out16, int cn, int oh, int ow, const float *bias, hipStream_t st, int act = 0) {
-    if (ks != 3 && ks != 5) return fail(CAE_ERR_UNSUPPORTED, "kernel_size %d not supported (3 or 5)", ks);
-    GGArgs a = gg_args(in16, n, ih, iw, ck, packed, out32, out16, cn, oh, ow, bias, 2, 1, act);
-    a.LH = oh;
-    a.LW = ow;
-    a.reflect = reflect;
+bool bad_kernel_size(int ks) { return ks != 3 && ks != 5; }
+int kernel_size_error(int ks) { return fail(CAE_ERR_UNSUPPORTED, "kernel_size %d not supported (3 or 5)", ks); }
+
+// Correlation over the whole k x k window, one output pixel per position: position (i, j) <- input (S i + d_ky, S j + d_kx)
+// with d_k = o + s k (add_taps).  k = 1: the pointwise product.
+int window_corr(GGArgs a, int ks, int o, int s, hipStream_t st) {
+    a.LH = a.OH;
+    a.LW = a.OW;
     a.ktaps = ks * ks;
-    a.ntaps = ks * ks;
-    const int P = ks / 2;
-    for (int ky = 0; ky < ks; ++ky)
-        for (int kx = 0; kx < ks; ++kx) {
-            const int t = ky * ks + kx;
-            a.dy[t] = (short)(ky - P);
-            a.dx[t] = (short)(kx - P);
-            a.wt[t] = (short)t;
-        }
-    return launch_gg(a, st);
+    TapList t;
+    add_taps(t, ks, o, o, s, 1);
+    return launch_gg(a, t, st);
 }
 
-// transpose of the strided correlation, one launch per output parity.
+// strided correlation: position (i, j) <- input (2i + ky - P, 2j + kx - P), every tap
+int strided_corr(const void *in16, int n, int ih, int iw, int ck, const void *packed, int ks, int reflect, float *out32,
+                 void *out16, int cn, int oh, int ow, const float *bias, int act, hipStream_t st) {
+    if (bad_kernel_size(ks)) return kernel_size_error(ks);
+    GGArgs a = gg_args(in16, n, ih, iw, ck, packed, out32, out16, cn, oh, ow, bias, 2, 1, act);
+    a.reflect = reflect;
+    return window_corr(a, ks, -(ks / 2), 1, st);
+}
+
+// transpose of the strided correlation.
 //   shift = P : cropped domain   out[Y] = sum in[(Y + P - ky) / 2]  (ConvTranspose2d(k, 2, k//2, output_padding 1))
 //   shift = 0 : extended domain  out[Y] = sum in[(Y - ky) / 2],  Y in [0, 2 ih + k - 2]   (data gradient of a valid
 //               convolution on the reflect-padded input; Y = y + P)
-// all four output parities of the k = 3 transpose in one launch (gg8t_kernel); -> false when the shape is not covered
-template <bool EXT>
-int launch_gg8t(GGArgs &a, hipStream_t st) {
-    auto kern = gg8t_kernel<EXT>;
-    const size_t h_instr = (size_t)(4 * a.HR * a.HC + 63) / 64;
-    const size_t lds = 2 * (h_instr + 9 * 2 * 2) * 1024;
-    CAE_TRY(ensure_lds((const void *)kern, (int)lds));
-    const size_t tiles = (size_t)a.tiles_x * a.tiles_y, halves = (size_t)a.Cn / 64;
-    a.npb = (int)std::min<size_t>(std::max<size_t>((size_t)a.N * tiles * halves / 512, 1), (size_t)a.N);
-    const unsigned grid = (unsigned)(tiles * (size_t)((a.N + a.npb - 1) / a.npb));
-    hipLaunchKernelGGL(kern, dim3(grid, (unsigned)halves), dim3(512), lds, st, a);
-    HIP_TRY(hipGetLastError());
-    return CAE_OK;
-}
-
-bool try_gg8t(const void *in16, int n, int ih, int iw, int ck, const void *packed, int shift, float *out32, void *out16, int cn,
-              int oh, int ow, const float *bias, hipStream_t st, int act, int &rc) {
-    if (cn % 64 || bad_channels(ck) || bad_channels(cn)) return false;
-    GGArgs a = gg_args(in16, n, ih, iw, ck, packed, out32, out16, cn, oh, ow, bias, 1, 2, act);
-    a.LH = (oh + 1) / 2;
-    a.LW = (ow + 1) / 2;
-    a.ktaps = 9;
-    a.ntaps = 9;
-    int nt = 0, dymin = 1 << 20, dymax = -(1 << 20), dxmin = 1 << 20, dxmax = -(1 << 20);
-    for (int py = 0; py < 2; ++py)
-        for (int px = 0; px < 2; ++px)  // parity-major: (0,0), (0,1), (1,0), (1,1) = gg8t_parity's order
-            for (int ky = 0; ky < 3; ++ky) {
-                if (((py + shift - ky) & 1) != 0) continue;
-                for (int kx = 0; kx < 3; ++kx) {
-                    if (((px + shift - kx) & 1) != 0) continue;
-                    a.dy[nt] = (short)((py + shift - ky) / 2);
-                    a.dx[nt] = (short)((px + shift - kx) / 2);
-                    a.wt[nt] = (short)(ky * 3 + kx);
-                    dymin = std::min<int>(dymin, a.dy[nt]);
-                    dymax = std::max<int>(dymax, a.dy[nt]);
-                    dxmin = std::min<int>(dxmin, a.dx[nt]);
-                    dxmax = std::max<int>(dxmax, a.dx[nt]);
-                    ++nt;
-                }
-            }
-    if (nt != 9) return false;
-    a.dymin = dymin;
-    a.dxmin = dxmin;
-    a.HR = 15 + (dymax - dymin) + 1;
-    a.HC = 15 + (dxmax - dxmin) + 1;
-    if ((4 * a.HR * a.HC + 63) / 64 > 32) return false;
-    a.m_hc = (unsigned)(((1ull << 32) + (unsigned)a.HC - 1) / (unsigned)a.HC);
-    a.tiles_x = (a.LW + 15) / 16;
-    a.tiles_y = (a.LH + 15) / 16;
-    a.zero = zero_page();
-    if (!a.zero) return false;
-    rc = shift == 0 ? launch_gg8t<true>(a, st) : launch_gg8t<false>(a, st);
-    return true;
-}
-
+// k = 3 and a multiple of 64 output channels: all four output parities in one gg8t launch, their tap lists one after the
+// other in gg8t_parity's order (0,0), (0,1), (1,0), (1,1); else one launch per output parity.
 int strided_corr_t(const void *in16, int n, int ih, int iw, int ck, const void *packed, int ks, int shift, float *out32,
-                   void *out16, int cn, int oh, int ow, const float *bias, hipStream_t st, int act = 0) {
-    if (ks != 3 && ks != 5) return fail(CAE_ERR_UNSUPPORTED, "kernel_size %d not supported (3 or 5)", ks);
-    int rc8t = CAE_OK;
-    if (ks == 3 && (shift == 0 || shift == 1) &&
-        try_gg8t(in16, n, ih, iw, ck, packed, shift, out32, out16, cn, oh, ow, bias, st, act, rc8t))
-        return rc8t;
+                   void *out16, int cn, int oh, int ow, const float *bias, int act, hipStream_t st) {
+    if (bad_kernel_size(ks)) return kernel_size_error(ks);
+    GGArgs base = gg_args(in16, n, ih, iw, ck, packed, out32, out16, cn, oh, ow, bias, 1, 2, act);
+    base.ktaps = ks * ks;
+    if (ks == 3 && (shift == 0 || shift == 1) && cn % 64 == 0 && !bad_channels(ck) && !bad_channels(cn)) {
+        GGArgs a = base;
+        TapList t;
+        for (int py = 0; py < 2; ++py)
+            for (int px = 0; px < 2; ++px) add_taps(t, ks, py + shift, px + shift, -1, 2);
+        set_taps(a, t);
+        set_halo(a, t, 1, GG_TILE, GG_TILE);
+        if (halo_instr(4, a.HR, a.HC) <= GG8T_HALO_INSTR) {
+            a.LH = (oh + 1) / 2;
+            a.LW = (ow + 1) / 2;
+            CAE_TRY(set_tiles(a));
+            return shift == 0 ? launch_gg8t<true>(a, st) : launch_gg8t<false>(a, st);
+        }
+    }
     for (int py = 0; py < 2; ++py)
         for (int px = 0; px < 2; ++px) {
-            GGArgs a = gg_args(in16, n, ih, iw, ck, packed, out32, out16, cn, oh, ow, bias, 1, 2, act);
+            GGArgs a = base;
             a.LH = (oh - py + 1) / 2;
             a.LW = (ow - px + 1) / 2;
-            if (a.LH < 1 || a.LW < 1) continue;
             a.oy0 = py;
             a.ox0 = px;
-            a.ktaps = ks * ks;
-            int nt = 0;
-            for (int ky = 0; ky < ks; ++ky) {
-                if (((py + shift - ky) & 1) != 0) continue;
-                for (int kx = 0; kx < ks; ++kx) {
-                    if (((px + shift - kx) & 1) != 0) continue;
-                    a.dy[nt] = (short)((py + shift - ky) / 2);  // exact: the numerator is even
-                    a.dx[nt] = (short)((px + shift - kx) / 2);
-                    a.wt[nt] = (short)(ky * ks + kx);
-                    ++nt;
-                }
-            }
-            a.ntaps = nt;
-            if (nt == 0) continue;
-            int rc = launch_gg(a, st);
-            if (rc) return rc;
+            TapList t;
+            add_taps(t, ks, py + shift, px + shift, -1, 2);
+            if (a.LH < 1 || a.LW < 1 || t.n == 0) continue;
+            CAE_TRY(launch_gg(a, t, st));
         }
     return CAE_OK;
 }
@@ -304,101 +330,149 @@ int strided_corr_t(const void *in16, int n, int ih, int iw, int ck, const void *
 //   mode 3  its data gradient                     d = k - P, zeros
 int stride1_corr(const void *in16, int n, int ih, int iw, int ck, const void *packed, int ks, int mode, float *out32,
                  void *out16, int cn, const float *bias, int act, hipStream_t st) {
-    if (ks != 3 && ks != 5) return fail(CAE_ERR_UNSUPPORTED, "kernel_size %d not supported (3 or 5)", ks);
+    if (bad_kernel_size(ks)) return kernel_size_error(ks);
     if (mode < 0 || mode > 3) return fail(CAE_ERR_ARG, "bad mode %d", mode);
-    const int P = ks / 2;
-    const int oh = mode == 1 ? ih + 2 * P : ih, ow = mode == 1 ? iw + 2 * P : iw;
-    GGArgs a = gg_args(in16, n, ih, iw, ck, packed, out32, out16, cn, oh, ow, bias, 1, 1, act);
-    a.LH = oh;
-    a.LW = ow;
+    const int P = ks / 2, grow = mode == 1 ? 2 * P : 0;
+    GGArgs a = gg_args(in16, n, ih, iw, ck, packed, out32, out16, cn, ih + grow, iw + grow, bias, 1, 1, act);
     a.reflect = mode == 0;
-    a.ktaps = ks * ks;
-    a.ntaps = ks * ks;
-    for (int ky = 0; ky < ks; ++ky)
-        for (int kx = 0; kx < ks; ++kx) {
-            const int t = ky * ks + kx;
-            a.dy[t] = (short)(mode == 1 ? -ky : (mode == 2 ? P - ky : ky - P));
-            a.dx[t] = (short)(mode == 1 ? -kx : (mode == 2 ? P - kx : kx - P));
-            a.wt[t] = (short)t;
-        }
-    return launch_gg(a, st);
+    return mode == 1 ? window_corr(a, ks, 0, -1, st) : mode == 2 ? window_corr(a, ks, P, -1, st) : window_corr(a, ks, -P, 1, st);
 }
 
-template <int NB>
-int launch_wg_t(const WGArgs &a, size_t lds, int ksplit, int at, int tg, hipStream_t st) {
-    auto kern = wgrad_kernel<NB>;
-    CAE_TRY(ensure_lds((const void *)kern, (int)lds));
-    hipLaunchKernelGGL(kern, dim3(ksplit, at, tg), dim3(256), lds, st, a);
-    HIP_TRY(hipGetLastError());
-    return CAE_OK;
+int pointwise_impl(const void *x16, int n, int h, int w, int ck, const void *packed, float *out32, void *out16, int cn,
+                   const float *bias, int act, int acc, hipStream_t st) {
+    GGArgs a = gg_args(x16, n, h, w, ck, packed, out32, out16, cn, h, w, bias, 1, 1, act);
+    a.acc = acc;
+    return window_corr(a, 1, 0, 1, st);
 }
 
-template <int CT, int MODE>
-int launch_gdn_a_t(const GdnArgs &a, hipStream_t st) {
-    auto kern = gdn_gemm_a_kernel<CT, MODE>;
-    constexpr int LDS = CT * 32 * (CT * 32 + 4) * 4 + (CT <= 4 ? 2 * 32768 : 0);  // M (+ the A double buffer)
-    CAE_TRY(ensure_lds((const void *)kern, LDS));
-    const long tiles = (a.pixels + 255) / 256;
-    const unsigned grid = (unsigned)std::min<long>(tiles, 512);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), LDS, st, a);
-    HIP_TRY(hipGetLastError());
-    return CAE_OK;
-}
-
+// ---- GDN ----
 template <int MODE>
 int launch_gdn_a(const GdnArgs &a, hipStream_t st) {
-    switch (a.C / 32) {
-        case 1: return launch_gdn_a_t<1, MODE>(a, st);
-        case 2: return launch_gdn_a_t<2, MODE>(a, st);
-        case 3: return launch_gdn_a_t<3, MODE>(a, st);
-        case 4: return launch_gdn_a_t<4, MODE>(a, st);
-        case 5: return launch_gdn_a_t<5, MODE>(a, st);
-        default: return launch_gdn_a_t<6, MODE>(a, st);
-    }
+    return for_tiles<MAX_CT>(a.C / 32, [&](auto ct) {
+        constexpr int CT = decltype(ct)::value;
+        constexpr int LDS = CT * 32 * (CT * 32 + 4) * 4 + (CT <= 4 ? 2 * 32768 : 0);  // M (+ the A double buffer)
+        const long tiles = (a.pixels + 255) / 256;
+        const unsigned grid = (unsigned)std::min<long>(tiles, 2 * TRAIN_CUS);
+        return launch(gdn_gemm_a_kernel<CT, MODE>, dim3(grid), dim3(256), LDS, st, a);
+    });
 }
 
 template <int CT>
 int launch_gdn_b_t(const float *gn, const float *z, long pixels, float *gg, float *gb, hipStream_t st) {
-    const unsigned grid = (unsigned)std::min<long>(std::max<long>(pixels / 256, 1), 256);
-    hipLaunchKernelGGL(gdn_gemm_b_kernel<CT>, dim3(grid), dim3(CT * 64), 0, st, gn, z, pixels, gg, gb);
-    HIP_TRY(hipGetLastError());
-    return CAE_OK;
+    const unsigned grid = (unsigned)std::min<long>(std::max<long>(pixels / 256, 1), TRAIN_CUS);
+    return launch(gdn_gemm_b_kernel<CT>, dim3(grid), dim3(CT * 64), 0, st, gn, z, pixels, gg, gb);
 }
 
-template <int CT>
-int launch_gdn_fused_t(const GdnFusedArgs &a, bool backward, hipStream_t st) {
-    constexpr int C = CT * 32;
-    constexpr int LDS_F = 2 * 32 * C * 4 + 32 * (C * 2 + 16);  // (Gamma in registers)
-    constexpr int LDS_B = C * (C + 4) * 4 + 4 * 32 * C * 4 + 32 * (C * 2 + 16);
-    auto kf = gdn_fwd_fused_kernel<CT>;
-    auto kb = gdn_bwd_fused_kernel<CT>;
-    CAE_TRY(ensure_lds((const void *)kf, LDS_F));
-    CAE_TRY(ensure_lds((const void *)kb, LDS_B));
-    const long tiles = (a.pixels + 31) / 32;
-    // persistent blocks walk the tiles: one per CU (backward: Gamma + two tile sets fill the LDS), two per CU (forward)
-    const unsigned grid = (unsigned)std::min<long>(tiles, backward ? 256 : 512);
-    if (backward)
-        hipLaunchKernelGGL(kb, dim3(grid), dim3(CT * 64), LDS_B, st, a);
-    else
-        hipLaunchKernelGGL(kf, dim3(grid), dim3(CT * 64), LDS_F, st, a);
-    HIP_TRY(hipGetLastError());
-    return CAE_OK;
+constexpr int FUSED_GDN_MAX_CT = 4;  // gdn_fwd_fused_kernel / gdn_bwd_fused_kernel: Gamma and the tile sets fill the LDS above
+int fused_gdn_too_wide(int cp) {
+    return fail(CAE_ERR_UNSUPPORTED, "fused GDN kernels are built for at most 128 channels, got %d", cp);
 }
 
 int launch_gdn_fused(const GdnFusedArgs &a, int cp, bool backward, hipStream_t st) {
-    switch (cp / 32) {
-        case 1: return launch_gdn_fused_t<1>(a, backward, st);
-        case 2: return launch_gdn_fused_t<2>(a, backward, st);
-        case 3: return launch_gdn_fused_t<3>(a, backward, st);
-        case 4: return launch_gdn_fused_t<4>(a, backward, st);
-        default: return fail(CAE_ERR_UNSUPPORTED, "fused GDN kernels are built for at most 128 channels, got %d", cp);
+    if (cp < 32 || cp > 32 * FUSED_GDN_MAX_CT) return fused_gdn_too_wide(cp);
+    return for_tiles<FUSED_GDN_MAX_CT>(cp / 32, [&](auto ct) {
+        constexpr int CT = decltype(ct)::value, C = CT * 32;
+        constexpr int LDS_F = 2 * 32 * C * 4 + 32 * (C * 2 + 16);  // (Gamma in registers)
+        constexpr int LDS_B = C * (C + 4) * 4 + 4 * 32 * C * 4 + 32 * (C * 2 + 16);
+        const long tiles = (a.pixels + 31) / 32;
+        // persistent blocks walk the tiles: one per CU (backward: Gamma + two tile sets fill the LDS), two per CU (forward)
+        const unsigned grid = (unsigned)std::min<long>(tiles, backward ? TRAIN_CUS : 2 * TRAIN_CUS);
+        if (!backward) return launch(gdn_fwd_fused_kernel<CT>, dim3(grid), dim3(CT * 64), LDS_F, st, a);
+        return launch(gdn_bwd_fused_kernel<CT>, dim3(grid), dim3(CT * 64), LDS_B, st, a);
+    });
+}
+
+// reflect fold of an extended-domain gradient in place (touches the border pixels only); nothing to do without padding
+int fold_in_place(float *gext32, int n, int h, int w, int pad, int cp, hipStream_t st) {
+    if (pad <= 0) return CAE_OK;
+    return launch(fold_inplace_kernel, dim3((unsigned)(n * (2 * pad + 1))), dim3(256), 0, st, gext32, h, w, pad, cp);
+}
+
+// the GDN parameter gradients are accumulated by atomics
+int zero_gdn_grads(float *ggamma, float *gbeta, int cp, hipStream_t st) {
+    HIP_TRY(hipMemsetAsync(ggamma, 0, (size_t)cp * cp * sizeof(float), st));
+    HIP_TRY(hipMemsetAsync(gbeta, 0, (size_t)cp * sizeof(float), st));
+    return CAE_OK;
+}
+
+// ---- weight gradient ----
+// gW[tap] of the k x k window d = k - P over positions S apart (tiles of 8 x 16 positions); k = 1: the pointwise product
+int wgrad_impl(const void *xbig16, int n, int h, int w, int ca, const void *ysmall16, int oh, int ow, int cb, int ks,
+               int reflect, int S, float *gw32, void *stream) {
+    if (!xbig16 || !ysmall16 || !gw32) return fail(CAE_ERR_ARG, "NULL argument");
+    if (ks != 1 && bad_kernel_size(ks)) return fail(CAE_ERR_UNSUPPORTED, "kernel_size %d not supported (1, 3 or 5)", ks);
+    if (bad_channels(ca) || bad_channels(cb)) return fail(CAE_ERR_ARG, "channel counts must be multiples of 32, at most 192");
+    hipStream_t st = (hipStream_t)stream;
+    WGArgs a{};
+    a.S = S;
+    a.x = xbig16;
+    a.y = ysmall16;
+    a.gw = gw32;
+    a.zero = zero_page();
+    if (!a.zero) return fail(CAE_ERR_NOMEM, "zero page");
+    a.N = n;
+    a.H = h;
+    a.W = w;
+    a.Ca = ca;
+    a.OH = oh;
+    a.OW = ow;
+    a.Cb = cb;
+    a.reflect = reflect;
+    a.kk = ks * ks;
+    TapList t;
+    add_taps(t, ks, -(ks / 2), -(ks / 2), 1, 1);
+    std::copy(t.dy, t.dy + MAX_TAPS, a.dy);
+    std::copy(t.dx, t.dx + MAX_TAPS, a.dx);
+    set_halo(a, t, S, WG_TILE_ROWS, WG_TILE_COLS);
+    a.m_ypp = recip32(cb / 8);
+    a.tiles_x = ceil_div(ow, WG_TILE_COLS);
+    a.tiles_y = ceil_div(oh, WG_TILE_ROWS);
+    a.total_tiles = n * a.tiles_x * a.tiles_y;
+    HIP_TRY(hipMemsetAsync(gw32, 0, (size_t)a.kk * ca * cb * sizeof(float), st));
+    // staging buffer: the X halo of a 32-channel a-tile + a tile's positions of Y, 16-byte pieces, 64 per instruction
+    const int x_instr = halo_instr(4, a.HR, a.HC), y_instr = (WG_TILE_ROWS * WG_TILE_COLS * (cb / 8) + 63) / 64;
+    const size_t lds = (size_t)(x_instr + y_instr) * 1024;
+    const int a_tiles = ca / 32, tap_groups = (a.kk + 8) / 9;
+    // wgrad8_kernel: 8 waves, double-buffered samples; needs two staging buffers in the LDS and Cb <= 128
+    // (the 192-channel layers as two launches of 96 b channels measured slower than wgrad_kernel<2>: r03_experiments.md)
+    // (at least the 80 KiB in which the position groups merge their partial sums at the end)
+    const size_t lds8 = std::max<size_t>(2 * lds, 4 * 5 * 16 * 64 * sizeof(float));
+    if (cb <= WG8_MAX_CB && x_instr <= WG8_X_INSTR && lds8 <= LDS_BUDGET) {
+        const int tpi = a.tiles_x * a.tiles_y;
+        // sample lanes: about ONE block per CU, and at least four samples per block -- every block ends with an atomic flush
+        // of its 9 x 32 x Cb partial sums, and that flush, not the contraction, set the time with more blocks
+        // (128 -> 128, 128^2 / 64^2 inputs; batch 128: 512 blocks 0.50 / 0.18 ms, 256 blocks 0.46 / 0.14 ms;
+        //  batch 16: 512 blocks 0.15 / 0.13 ms, 256 / 128 blocks 0.105 / 0.053 ms)
+        const int base = std::max(1, tpi * a_tiles * tap_groups);
+        const int step = std::max(1, std::min(std::max(1, n / 4), TRAIN_CUS / base));
+        a.Cbs = cb;  // (cb0 = 0: all b channels in one launch)
+        return launch(wgrad8_kernel, dim3(tpi * step, a_tiles, tap_groups), dim3(512), lds8, st, a, tpi, step);
     }
+    // (about one block per CU here too: 256 blocks 13.06 - 13.11 ms per 128 x 256^2 step, 512: 13.18, 128: 13.15 - 13.18, 64: 13.45 - 13.5)
+    const int ksplit = std::max(1, std::min(a.total_tiles, TRAIN_CUS / (a_tiles * tap_groups)));
+    const dim3 grid(ksplit, a_tiles, tap_groups);  // (wgrad_kernel<NB>: NB b-tiles per wave)
+    return cb / 32 <= 4 ? launch(wgrad_kernel<1>, grid, dim3(256), lds, st, a)
+                        : launch(wgrad_kernel<2>, grid, dim3(256), lds, st, a);
+}
+
+// the strided layers' forwards; `bad` is the entry point's text for a bad shape
+int conv_forward(const void *x16, int n, int h, int w, int cin_p, const void *packed, int ks, float *z32, void *z16, int cout_p,
+                 const float *bias, int act, const char *bad, void *stream) {
+    if (!x16 || !packed || (!z32 && !z16)) return fail(CAE_ERR_ARG, "NULL argument");
+    if (n < 1 || h < 2 || w < 2 || act < 0 || act > 2) return fail(CAE_ERR_ARG, "%s", bad);
+    return strided_corr(x16, n, h, w, cin_p, packed, ks, 1, z32, z16, cout_p, (h + 1) / 2, (w + 1) / 2, bias, act,
+                        (hipStream_t)stream);
+}
+
+int deconv_forward(const void *x16, int n, int h, int w, int cin_p, const void *packed, int ks, float *z32, void *z16,
+                   int cout_p, const float *bias, int act, const char *bad, void *stream) {
+    if (!x16 || !packed || (!z32 && !z16)) return fail(CAE_ERR_ARG, "NULL argument");
+    if (n < 1 || h < 1 || w < 1 || act < 0 || act > 2) return fail(CAE_ERR_ARG, "%s", bad);
+    return strided_corr_t(x16, n, h, w, cin_p, packed, ks, ks / 2, z32, z16, cout_p, 2 * h, 2 * w, bias, act,
+                          (hipStream_t)stream);
 }
 
 }  // namespace
-
-static int wgrad_impl(const void *xbig16, int n, int h, int w, int ca, const void *ysmall16, int oh, int ow, int cb, int ks,
-                      int reflect, int S, float *gw32, void *stream);
 
 extern "C" {
 
@@ -422,52 +496,39 @@ int cae_t_pack_weights(const float *w, int dim0, int dim1, int ks, int contract_
     const long sk = contract_dim == 0 ? s0 : s1, sn = contract_dim == 0 ? s1 : s0;
     const int kchunks = (Kc + 31) / 32, NT = (Nc + 31) / 32;
     const size_t total = (size_t)kchunks * kk * NT * 1024;
-    hipLaunchKernelGGL(pack_weights_kernel, dim3(ew_grid(total)), dim3(256), 0, (hipStream_t)stream, w, (__bf16 *)packed, Kc,
-                       Nc, kk, sk, sn, kchunks, NT);
-    HIP_TRY(hipGetLastError());
-    return CAE_OK;
+    return launch_ew(pack_weights_kernel, total, stream, w, (__bf16 *)packed, Kc, Nc, kk, sk, sn, kchunks, NT);
 }
 
 int cae_t_from_nchw(const float *x, int n, int c, int h, int w, int cp, void *out16, float *out32, void *stream) {
     if (!x || (!out16 && !out32)) return fail(CAE_ERR_ARG, "NULL argument");
     if (n < 1 || c < 1 || h < 1 || w < 1 || cp < c || cp % 32) return fail(CAE_ERR_ARG, "bad shape");
-    hipLaunchKernelGGL(nchw_to_t_kernel, dim3(ew_grid((size_t)n * h * w * cp)), dim3(256), 0, (hipStream_t)stream, x,
-                       (__bf16 *)out16, out32, n, c, h, w, cp);
-    HIP_TRY(hipGetLastError());
-    return CAE_OK;
+    return launch_ew(nchw_to_t_kernel, (size_t)n * h * w * cp, stream, x, (__bf16 *)out16, out32, n, c, h, w, cp);
 }
 
 int cae_t_to_nchw(const float *t32, int n, int c, int h, int w, int cp, float *out, void *stream) {
     if (!t32 || !out) return fail(CAE_ERR_ARG, "NULL argument");
     if (n < 1 || c < 1 || h < 1 || w < 1 || cp < c || cp % 32) return fail(CAE_ERR_ARG, "bad shape");
-    hipLaunchKernelGGL(t_to_nchw_kernel, dim3(ew_grid((size_t)n * c * h * w)), dim3(256), 0, (hipStream_t)stream, t32, out, n,
-                       c, h, w, cp);
-    HIP_TRY(hipGetLastError());
-    return CAE_OK;
+    return launch_ew(t_to_nchw_kernel, (size_t)n * c * h * w, stream, t32, out, n, c, h, w, cp);
 }
 
 int cae_t_conv_forward(const void *x16, int n, int h, int w, int cin_p, const void *packed, int ks, float *z32, void *z16,
                        int cout_p, const float *bias, void *stream) {
-    if (!x16 || !packed || (!z32 && !z16)) return fail(CAE_ERR_ARG, "NULL argument");
-    if (n < 1 || h < 2 || w < 2) return fail(CAE_ERR_ARG, "bad shape");
-    return strided_corr(x16, n, h, w, cin_p, packed, ks, 1, z32, z16, cout_p, (h + 1) / 2, (w + 1) / 2, bias,
-                        (hipStream_t)stream);
+    return conv_forward(x16, n, h, w, cin_p, packed, ks, z32, z16, cout_p, bias, 0, "bad shape", stream);
 }
 
 int cae_t_conv_forward_act(const void *x16, int n, int h, int w, int cin_p, const void *packed, int ks, float *z32, void *z16,
                            int cout_p, const float *bias, int act, void *stream) {
-    if (!x16 || !packed || (!z32 && !z16)) return fail(CAE_ERR_ARG, "NULL argument");
-    if (n < 1 || h < 2 || w < 2 || act < 0 || act > 2) return fail(CAE_ERR_ARG, "bad shape or activation");
-    return strided_corr(x16, n, h, w, cin_p, packed, ks, 1, z32, z16, cout_p, (h + 1) / 2, (w + 1) / 2, bias,
-                        (hipStream_t)stream, act);
+    return conv_forward(x16, n, h, w, cin_p, packed, ks, z32, z16, cout_p, bias, act, "bad shape or activation", stream);
+}
+
+int cae_t_deconv_forward(const void *x16, int n, int h, int w, int cin_p, const void *packed, int ks, float *z32, void *z16,
+                         int cout_p, const float *bias, void *stream) {
+    return deconv_forward(x16, n, h, w, cin_p, packed, ks, z32, z16, cout_p, bias, 0, "bad shape", stream);
 }
 
 int cae_t_deconv_forward_act(const void *x16, int n, int h, int w, int cin_p, const void *packed, int ks, float *z32, void *z16,
                              int cout_p, const float *bias, int act, void *stream) {
-    if (!x16 || !packed || (!z32 && !z16)) return fail(CAE_ERR_ARG, "NULL argument");
-    if (n < 1 || h < 1 || w < 1 || act < 0 || act > 2) return fail(CAE_ERR_ARG, "bad shape or activation");
-    return strided_corr_t(x16, n, h, w, cin_p, packed, ks, ks / 2, z32, z16, cout_p, 2 * h, 2 * w, bias, (hipStream_t)stream,
-                          act);
+    return deconv_forward(x16, n, h, w, cin_p, packed, ks, z32, z16, cout_p, bias, act, "bad shape or activation", stream);
 }
 
 int cae_t_corr_s1(const void *x16, int n, int h, int w, int ck, const void *packed, int ks, int mode, float *out32, void *out16,
@@ -476,9 +537,6 @@ int cae_t_corr_s1(const void *x16, int n, int h, int w, int ck, const void *pack
     if (n < 1 || h < 1 || w < 1 || act < 0 || act > 2) return fail(CAE_ERR_ARG, "bad shape or activation");
     return stride1_corr(x16, n, h, w, ck, packed, ks, mode, out32, out16, cn, bias, act, (hipStream_t)stream);
 }
-
-static int pointwise_impl(const void *x16, int n, int h, int w, int ck, const void *packed, float *out32, void *out16, int cn,
-                          const float *bias, int act, int acc, hipStream_t st);
 
 int cae_t_pointwise(const void *x16, int n, int h, int w, int ck, const void *packed, float *out32, void *out16, int cn,
                     const float *bias, int act, void *stream) {
@@ -493,84 +551,50 @@ int cae_t_pointwise_acc(const void *x16, int n, int h, int w, int ck, const void
     return pointwise_impl(x16, n, h, w, ck, packed, out32, nullptr, cn, nullptr, 0, 1, (hipStream_t)stream);
 }
 
-static int pointwise_impl(const void *x16, int n, int h, int w, int ck, const void *packed, float *out32, void *out16, int cn,
-                          const float *bias, int act, int acc, hipStream_t st) {
-    GGArgs a = gg_args(x16, n, h, w, ck, packed, out32, out16, cn, h, w, bias, 1, 1, act);
-    a.LH = h;
-    a.LW = w;
-    a.acc = acc;
-    a.ktaps = 1;
-    a.ntaps = 1;
-    a.dy[0] = a.dx[0] = a.wt[0] = 0;
-    return launch_gg(a, st);
-}
-
 int cae_t_col2im_s1r(const float *u32, const float *bias, int n, int c, int h, int w, int ks, int kp, float *out_nchw,
                      void *stream) {
     if (!u32 || !out_nchw) return fail(CAE_ERR_ARG, "NULL argument");
-    if (n < 1 || c < 1 || c > 3 || (ks != 3 && ks != 5) || kp % 32 || kp < ks * ks * c || kp > 96)
+    if (n < 1 || c < 1 || c > 3 || bad_kernel_size(ks) || kp % 32 || kp < ks * ks * c || kp > 96)
         return fail(CAE_ERR_ARG, "bad shape (1 to 3 channels, kernel_size 3 or 5, kp = pad32(k * k * c) <= 96)");
     if (h <= ks / 2 || w <= ks / 2) return fail(CAE_ERR_ARG, "image %d x %d too small for reflect padding %d", h, w, ks / 2);
-    hipLaunchKernelGGL(col2im_s1r_kernel, dim3(ew_grid((size_t)n * h * w)), dim3(256), 0, (hipStream_t)stream, u32, bias,
-                       out_nchw, n, c, h, w, ks, kp);
-    HIP_TRY(hipGetLastError());
-    return CAE_OK;
+    return launch_ew(col2im_s1r_kernel, (size_t)n * h * w, stream, u32, bias, out_nchw, n, c, h, w, ks, kp);
 }
 
 int cae_t_im2col_s1r(const float *g_nchw, int n, int c, int h, int w, int ks, int kp, void *out16, void *stream) {
     if (!g_nchw || !out16) return fail(CAE_ERR_ARG, "NULL argument");
-    if (n < 1 || c < 1 || c > 3 || (ks != 3 && ks != 5) || kp % 32 || kp < ks * ks * c || kp > 96)
+    if (n < 1 || c < 1 || c > 3 || bad_kernel_size(ks) || kp % 32 || kp < ks * ks * c || kp > 96)
         return fail(CAE_ERR_ARG, "bad shape (1 to 3 channels, kernel_size 3 or 5, kp = pad32(k * k * c) <= 96)");
     if (h <= ks / 2 || w <= ks / 2) return fail(CAE_ERR_ARG, "image %d x %d too small for reflect padding %d", h, w, ks / 2);
-    hipLaunchKernelGGL(im2col_s1r_kernel, dim3(ew_grid((size_t)n * h * w * (kp / 8))), dim3(256), 0, (hipStream_t)stream,
-                       g_nchw, (__bf16 *)out16, n, c, h, w, ks, kp);
-    HIP_TRY(hipGetLastError());
-    return CAE_OK;
+    return launch_ew(im2col_s1r_kernel, (size_t)n * h * w * (kp / 8), stream, g_nchw, (__bf16 *)out16, n, c, h, w, ks, kp);
 }
 
 int cae_t_fold_acc(const float *gext32, int n, int h, int w, int pad, int cp, float *out32, void *stream) {
     if (!gext32 || !out32) return fail(CAE_ERR_ARG, "NULL argument");
     if (n < 1 || h <= pad || w <= pad || pad < 0 || cp % 32) return fail(CAE_ERR_ARG, "bad shape");
-    hipLaunchKernelGGL(fold_acc_kernel, dim3(ew_grid((size_t)n * h * w * cp)), dim3(256), 0, (hipStream_t)stream,
-                       FoldSrc{gext32, h, w, pad}, out32, n, cp);
-    HIP_TRY(hipGetLastError());
-    return CAE_OK;
+    return launch_ew(fold_acc_kernel, (size_t)n * h * w * cp, stream, FoldSrc{gext32, h, w, pad}, out32, n, cp);
 }
 
 int cae_t_pyramid_down(const float *x_nchw, int n, int c, int h, int w, float *out_nchw, void *stream) {
     if (!x_nchw || !out_nchw) return fail(CAE_ERR_ARG, "NULL argument");
     if (n < 1 || c < 1 || h < 2 || w < 2) return fail(CAE_ERR_ARG, "bad shape (the pyramid step needs h, w >= 2)");
     const int oh = h / 2, ow = w / 2;
-    hipLaunchKernelGGL(pyramid_down_kernel, dim3(ew_grid((size_t)n * c * oh * ow)), dim3(256), 0, (hipStream_t)stream, x_nchw,
-                       out_nchw, n * c, h, w, oh, ow);
-    HIP_TRY(hipGetLastError());
-    return CAE_OK;
-}
-
-int cae_t_wgrad_pointwise(const void *x16, const void *y16, int n, int h, int w, int ca, int cb, float *gw32, void *stream) {
-    if (n < 1 || h < 1 || w < 1) return fail(CAE_ERR_ARG, "bad shape");
-    return wgrad_impl(x16, n, h, w, ca, y16, h, w, cb, 1, 0, 1, gw32, stream);
+    return launch_ew(pyramid_down_kernel, (size_t)n * c * oh * ow, stream, x_nchw, out_nchw, n * c, h, w, oh, ow);
 }
 
 int cae_t_im2col_s2(const float *x_nchw, int n, int c, int h, int w, int oh, int ow, int ks, int reflect, void *out16,
                     void *stream) {
     if (!x_nchw || !out16) return fail(CAE_ERR_ARG, "NULL argument");
-    if (n < 1 || c < 1 || h < 1 || w < 1 || oh < 1 || ow < 1 || (ks != 3 && ks != 5) || ks * ks * c > 32)
+    if (n < 1 || c < 1 || h < 1 || w < 1 || oh < 1 || ow < 1 || bad_kernel_size(ks) || ks * ks * c > 32)
         return fail(CAE_ERR_ARG, "bad shape (kernel_size^2 * channels must fit 32)");
-    hipLaunchKernelGGL(im2col_s2_kernel, dim3(ew_grid((size_t)n * oh * ow * 4)), dim3(256), 0, (hipStream_t)stream, x_nchw,
-                       (__bf16 *)out16, n, c, h, w, oh, ow, ks, reflect);
-    HIP_TRY(hipGetLastError());
-    return CAE_OK;
+    return launch_ew(im2col_s2_kernel, (size_t)n * oh * ow * 4, stream, x_nchw, (__bf16 *)out16, n, c, h, w, oh, ow, ks,
+                     reflect);
 }
 
 int cae_t_col2im_s2(const float *u32, const float *bias, int n, int c, int h, int w, int ks, float *out_nchw, void *stream) {
     if (!u32 || !out_nchw) return fail(CAE_ERR_ARG, "NULL argument");
-    if (n < 1 || c < 1 || h < 1 || w < 1 || (ks != 3 && ks != 5) || ks * ks * c > 32)
+    if (n < 1 || c < 1 || h < 1 || w < 1 || bad_kernel_size(ks) || ks * ks * c > 32)
         return fail(CAE_ERR_ARG, "bad shape (kernel_size^2 * channels must fit 32)");
-    hipLaunchKernelGGL(col2im_s2_kernel, dim3(ew_grid((size_t)n * 4 * h * w)), dim3(256), 0, (hipStream_t)stream, u32, bias,
-                       out_nchw, n, c, h, w, ks);
-    HIP_TRY(hipGetLastError());
-    return CAE_OK;
+    return launch_ew(col2im_s2_kernel, (size_t)n * 4 * h * w, stream, u32, bias, out_nchw, n, c, h, w, ks);
 }
 
 int cae_t_act_backward(const void *g16, float *gext32, int pad, const void *y16, int n, int h, int w, int cp, int act,
@@ -578,15 +602,9 @@ int cae_t_act_backward(const void *g16, float *gext32, int pad, const void *y16,
     if ((!g16 && !gext32) || !y16 || !out16) return fail(CAE_ERR_ARG, "NULL argument");
     if (n < 1 || h < 1 || w < 1 || pad < 0 || cp % 32 || act < 1 || act > 2) return fail(CAE_ERR_ARG, "bad shape or activation");
     hipStream_t st = (hipStream_t)stream;
-    if (!g16 && pad > 0) {  // reflect fold of the extended-domain gradient, in place
-        hipLaunchKernelGGL(fold_inplace_kernel, dim3((unsigned)(n * (2 * pad + 1))), dim3(256), 0, st, gext32, h, w, pad, cp);
-        HIP_TRY(hipGetLastError());
-    }
-    hipLaunchKernelGGL(act_bwd_kernel, dim3(ew_grid((size_t)n * h * w * cp)), dim3(256), 0, st, (const __bf16 *)g16,
-                       FoldSrc{gext32, h, w, g16 ? 0 : pad}, (const __bf16 *)y16, act == 1 ? 0.01f : 0.0f, (__bf16 *)out16, n, h,
-                       w, cp);
-    HIP_TRY(hipGetLastError());
-    return CAE_OK;
+    if (!g16) CAE_TRY(fold_in_place(gext32, n, h, w, pad, cp, st));
+    return launch_ew(act_bwd_kernel, (size_t)n * h * w * cp, st, (const __bf16 *)g16, FoldSrc{gext32, h, w, g16 ? 0 : pad},
+                     (const __bf16 *)y16, act == 1 ? 0.01f : 0.0f, (__bf16 *)out16, n, h, w, cp);
 }
 
 int cae_t_conv_dgrad_ext(const void *gz16, int n, int oh, int ow, int cout_p, const void *packed, int ks, int h, int w,
@@ -594,24 +612,17 @@ int cae_t_conv_dgrad_ext(const void *gz16, int n, int oh, int ow, int cout_p, co
     if (!gz16 || !packed || !gext32) return fail(CAE_ERR_ARG, "NULL argument");
     if (oh != (h + 1) / 2 || ow != (w + 1) / 2) return fail(CAE_ERR_ARG, "gradient shape does not match the input shape");
     const int P = ks / 2, eh = h + 2 * P, ew = w + 2 * P;
-    // (every position of the extended domain belongs to exactly one of the four parity launches below and each of them has
-    //  at least one tap for k >= 2, so all of gext32 is written: positions beyond 2 oh + k - 2 (odd input sizes) read
+    // (every position of the extended domain belongs to exactly one of the four output parities and each of them has at
+    //  least one tap for k >= 2, so all of gext32 is written: positions beyond 2 oh + k - 2 (odd input sizes) read
     //  nothing but the zero page and come out as 0 -- no memset of the ~1 GB tensor)
-    return strided_corr_t(gz16, n, oh, ow, cout_p, packed, ks, 0, gext32, nullptr, cin_p, eh, ew, nullptr, (hipStream_t)stream);
-}
-
-int cae_t_deconv_forward(const void *x16, int n, int h, int w, int cin_p, const void *packed, int ks, float *z32, void *z16,
-                         int cout_p, const float *bias, void *stream) {
-    if (!x16 || !packed || (!z32 && !z16)) return fail(CAE_ERR_ARG, "NULL argument");
-    if (n < 1 || h < 1 || w < 1) return fail(CAE_ERR_ARG, "bad shape");
-    return strided_corr_t(x16, n, h, w, cin_p, packed, ks, ks / 2, z32, z16, cout_p, 2 * h, 2 * w, bias, (hipStream_t)stream);
+    return strided_corr_t(gz16, n, oh, ow, cout_p, packed, ks, 0, gext32, nullptr, cin_p, eh, ew, nullptr, 0, (hipStream_t)stream);
 }
 
 int cae_t_deconv_dgrad(const void *gz16, int n, int h, int w, int cout_p, const void *packed, int ks, float *gx32, void *gx16,
                        int cin_p, void *stream) {
     if (!gz16 || !packed || (!gx32 && !gx16)) return fail(CAE_ERR_ARG, "NULL argument");
     if (n < 1 || h < 1 || w < 1) return fail(CAE_ERR_ARG, "bad shape");
-    return strided_corr(gz16, n, 2 * h, 2 * w, cout_p, packed, ks, 0, gx32, gx16, cin_p, h, w, nullptr, (hipStream_t)stream);
+    return strided_corr(gz16, n, 2 * h, 2 * w, cout_p, packed, ks, 0, gx32, gx16, cin_p, h, w, nullptr, 0, (hipStream_t)stream);
 }
 
 int cae_t_wgrad(const void *xbig16, int n, int h, int w, int ca, const void *ysmall16, int oh, int ow, int cb, int ks,
@@ -626,69 +637,9 @@ int cae_t_wgrad_s1(const void *x16, int n, int h, int w, int ca, const void *y16
     return wgrad_impl(x16, n, h, w, ca, y16, h, w, cb, ks, reflect, 1, gw32, stream);
 }
 
-static int wgrad_impl(const void *xbig16, int n, int h, int w, int ca, const void *ysmall16, int oh, int ow, int cb, int ks,
-                      int reflect, int S, float *gw32, void *stream) {
-    if (!xbig16 || !ysmall16 || !gw32) return fail(CAE_ERR_ARG, "NULL argument");
-    if (ks != 1 && ks != 3 && ks != 5) return fail(CAE_ERR_UNSUPPORTED, "kernel_size %d not supported (1, 3 or 5)", ks);
-    if (bad_channels(ca) || bad_channels(cb)) return fail(CAE_ERR_ARG, "channel counts must be multiples of 32, at most 192");
-    hipStream_t st = (hipStream_t)stream;
-    WGArgs a{};
-    a.S = S;
-    a.x = xbig16;
-    a.y = ysmall16;
-    a.gw = gw32;
-    a.zero = zero_page();
-    if (!a.zero) return fail(CAE_ERR_NOMEM, "zero page");
-    a.N = n;
-    a.H = h;
-    a.W = w;
-    a.Ca = ca;
-    a.OH = oh;
-    a.OW = ow;
-    a.Cb = cb;
-    a.reflect = reflect;
-    a.kk = ks * ks;
-    const int P = ks / 2;
-    for (int ky = 0; ky < ks; ++ky)
-        for (int kx = 0; kx < ks; ++kx) {
-            a.dy[ky * ks + kx] = (short)(ky - P);
-            a.dx[ky * ks + kx] = (short)(kx - P);
-        }
-    a.dymin = -P;
-    a.dxmin = -P;
-    a.HR = S * 7 + ks;
-    a.HC = S * 15 + ks;
-    a.m_hc = (unsigned)(((1ull << 32) + (unsigned)a.HC - 1) / (unsigned)a.HC);
-    a.m_ypp = (unsigned)(((1ull << 32) + (unsigned)(cb / 8) - 1) / (unsigned)(cb / 8));
-    a.tiles_x = (ow + 15) / 16;
-    a.tiles_y = (oh + 7) / 8;
-    a.total_tiles = n * a.tiles_x * a.tiles_y;
-    HIP_TRY(hipMemsetAsync(gw32, 0, (size_t)a.kk * ca * cb * sizeof(float), st));
-    const size_t lds = (size_t)((a.HR * a.HC * 4 + 63) / 64) * 1024 + (size_t)((128 * (cb / 8) + 63) / 64) * 1024;
-    const int a_tiles = ca / 32, tap_groups = (a.kk + 8) / 9;
-    // wgrad8_kernel: 8 waves, double-buffered samples; needs two staging buffers in the LDS and Cb <= 128
-    // (the 192-channel layers as two launches of 96 b channels measured slower than wgrad_kernel<2>: r03_experiments.md)
-    const int x_instr = (a.HR * a.HC * 4 + 63) / 64, y_instr = (128 * (cb / 8) + 63) / 64;
-    // (two staging buffers; at least the 80 KiB in which the position groups merge their partial sums at the end)
-    const size_t lds8 = std::max<size_t>(2 * (size_t)(x_instr + y_instr) * 1024, 4 * 5 * 16 * 64 * sizeof(float));
-    if (cb <= 128 && x_instr <= 64 && lds8 <= 160 * 1024) {
-        CAE_TRY(ensure_lds((const void *)wgrad8_kernel, (int)lds8));
-        const int tpi = a.tiles_x * a.tiles_y;
-        // sample lanes: about ONE block per CU, and at least four samples per block -- every block ends with an atomic flush
-        // of its 9 x 32 x Cb partial sums, and that flush, not the contraction, set the time with more blocks
-        // (128 -> 128, 128^2 / 64^2 inputs; batch 128: 512 blocks 0.50 / 0.18 ms, 256 blocks 0.46 / 0.14 ms;
-        //  batch 16: 512 blocks 0.15 / 0.13 ms, 256 / 128 blocks 0.105 / 0.053 ms)
-        const int base = std::max(1, tpi * a_tiles * tap_groups);
-        const int step = std::max(1, std::min(std::max(1, n / 4), 256 / base));
-        a.Cbs = cb;  // (cb0 = 0: all b channels in one launch)
-        hipLaunchKernelGGL(wgrad8_kernel, dim3(tpi * step, a_tiles, tap_groups), dim3(512), lds8, st, a, tpi, step);
-        HIP_TRY(hipGetLastError());
-        return CAE_OK;
-    }
-    // (about one block per CU here too: 256 blocks 13.06 - 13.11 ms per 128 x 256^2 step, 512: 13.18, 128: 13.15 - 13.18, 64: 13.45 - 13.5)
-    const int ksplit = std::max(1, std::min(a.total_tiles, 256 / (a_tiles * tap_groups)));
-    if (cb / 32 <= 4) return launch_wg_t<1>(a, lds, ksplit, a_tiles, tap_groups, st);
-    return launch_wg_t<2>(a, lds, ksplit, a_tiles, tap_groups, st);
+int cae_t_wgrad_pointwise(const void *x16, const void *y16, int n, int h, int w, int ca, int cb, float *gw32, void *stream) {
+    if (n < 1 || h < 1 || w < 1) return fail(CAE_ERR_ARG, "bad shape");
+    return wgrad_impl(x16, n, h, w, ca, y16, h, w, cb, 1, 0, 1, gw32, stream);
 }
 
 int cae_t_gdn_forward(const float *z32, long pixels, int cp, const float *beta, const float *gamma, int inverse, float *y32,
@@ -730,8 +681,7 @@ int cae_t_gdn_backward(const float *z32, const float *gext32, int n, int h, int 
     a.pixels = pixels;
     a.C = cp;
     a.inverse = inverse;
-    int rc = launch_gdn_a<1>(a, st);
-    if (rc) return rc;
+    CAE_TRY(launch_gdn_a<1>(a, st));
     GdnArgs b{};
     b.a = gn_ws32;
     b.mat = gamma_t;
@@ -742,21 +692,15 @@ int cae_t_gdn_backward(const float *z32, const float *gext32, int n, int h, int 
     b.pixels = pixels;
     b.C = cp;
     b.inverse = inverse;
-    if ((rc = launch_gdn_a<2>(b, st))) return rc;
-    HIP_TRY(hipMemsetAsync(ggamma, 0, (size_t)cp * cp * sizeof(float), st));
-    HIP_TRY(hipMemsetAsync(gbeta, 0, (size_t)cp * sizeof(float), st));
-    switch (cp / 32) {
-        case 1: return launch_gdn_b_t<1>(gn_ws32, z32, pixels, ggamma, gbeta, st);
-        case 2: return launch_gdn_b_t<2>(gn_ws32, z32, pixels, ggamma, gbeta, st);
-        case 3: return launch_gdn_b_t<3>(gn_ws32, z32, pixels, ggamma, gbeta, st);
-        case 4: return launch_gdn_b_t<4>(gn_ws32, z32, pixels, ggamma, gbeta, st);
-        case 5: return launch_gdn_b_t<5>(gn_ws32, z32, pixels, ggamma, gbeta, st);
-        default: return launch_gdn_b_t<6>(gn_ws32, z32, pixels, ggamma, gbeta, st);
-    }
+    CAE_TRY(launch_gdn_a<2>(b, st));
+    CAE_TRY(zero_gdn_grads(ggamma, gbeta, cp, st));
+    return for_tiles<MAX_CT>(cp / 32, [&](auto ct) {
+        return launch_gdn_b_t<decltype(ct)::value>(gn_ws32, z32, pixels, ggamma, gbeta, st);
+    });
 }
 
 size_t cae_t_gdn_saved_elems(long pixels, int cp) {
-    if (pixels < 1 || cp < 32 || cp > 128 || cp % 32) return 0;
+    if (pixels < 1 || cp < 32 || cp > 32 * FUSED_GDN_MAX_CT || cp % 32) return 0;
     return (size_t)((pixels + 63) / 64) * 64 * (size_t)cp;
 }
 
@@ -781,14 +725,10 @@ int cae_t_gdn_backward_fused(const float *z32, const float *f_saved, float *gext
     if (n < 1 || h < 1 || w < 1 || pad < 0 || cp % 32) return fail(CAE_ERR_ARG, "bad shape");
     const long pixels = (long)n * h * w;
     if (pixels >= (1l << 31)) return fail(CAE_ERR_ARG, "more than 2^31 pixels per call");
-    if (cp > 128) return fail(CAE_ERR_UNSUPPORTED, "fused GDN kernels are built for at most 128 channels, got %d", cp);
+    if (cp > 32 * FUSED_GDN_MAX_CT) return fused_gdn_too_wide(cp);
     hipStream_t st = (hipStream_t)stream;
-    HIP_TRY(hipMemsetAsync(ggamma, 0, (size_t)cp * cp * sizeof(float), st));
-    HIP_TRY(hipMemsetAsync(gbeta, 0, (size_t)cp * sizeof(float), st));
-    if (pad > 0) {  // reflect fold of the extended-domain gradient, in place (touches the border pixels only)
-        hipLaunchKernelGGL(fold_inplace_kernel, dim3((unsigned)(n * (2 * pad + 1))), dim3(256), 0, st, gext32, h, w, pad, cp);
-        HIP_TRY(hipGetLastError());
-    }
+    CAE_TRY(zero_gdn_grads(ggamma, gbeta, cp, st));
+    CAE_TRY(fold_in_place(gext32, n, h, w, pad, cp, st));
     GdnFusedArgs a{};
     a.z = z32;
     a.gamma = gamma;
@@ -807,10 +747,7 @@ int cae_t_gdn_backward_fused(const float *z32, const float *f_saved, float *gext
 int cae_t_fold_to_bf16(const float *gext32, int n, int h, int w, int pad, int cp, void *out16, void *stream) {
     if (!gext32 || !out16) return fail(CAE_ERR_ARG, "NULL argument");
     if (n < 1 || h < 1 || w < 1 || pad < 0 || cp % 32) return fail(CAE_ERR_ARG, "bad shape");
-    hipLaunchKernelGGL(fold_to_bf16_kernel, dim3(ew_grid((size_t)n * h * w * cp)), dim3(256), 0, (hipStream_t)stream,
-                       FoldSrc{gext32, h, w, pad}, (__bf16 *)out16, n, cp);
-    HIP_TRY(hipGetLastError());
-    return CAE_OK;
+    return launch_ew(fold_to_bf16_kernel, (size_t)n * h * w * cp, stream, FoldSrc{gext32, h, w, pad}, (__bf16 *)out16, n, cp);
 }
 
 int cae_t_bn_moments(const float *a, const float *b, int n, int c, long hw, double *s1, double *s2, void *stream) {
@@ -821,9 +758,7 @@ int cae_t_bn_moments(const float *a, const float *b, int n, int c, long hw, doub
     HIP_TRY(hipMemsetAsync(s2, 0, (size_t)c * sizeof(double), st));
     const long total = (long)n * hw;
     const unsigned splits = (unsigned)std::min<long>(std::max<long>(total / 4096, 1), std::max<long>(2048 / c, 1));
-    hipLaunchKernelGGL(bn_moments_kernel, dim3((unsigned)c, splits), dim3(256), 0, st, a, b, n, c, hw, s1, s2);
-    HIP_TRY(hipGetLastError());
-    return CAE_OK;
+    return launch(bn_moments_kernel, dim3((unsigned)c, splits), dim3(256), 0, st, a, b, n, c, hw, s1, s2);
 }
 
 int cae_t_bn_affine(const float *a, const float *b, int n, int c, long hw, const float *A, const float *B, const float *C,
@@ -831,10 +766,7 @@ int cae_t_bn_affine(const float *a, const float *b, int n, int c, long hw, const
     if (!a || !A || !C || !out || (b && !B)) return fail(CAE_ERR_ARG, "NULL argument");
     if (n < 1 || c < 1 || hw < 1) return fail(CAE_ERR_ARG, "bad shape");
     const size_t total = (size_t)n * c * hw;
-    hipLaunchKernelGGL(bn_affine_kernel, dim3(ew_grid(total)), dim3(256), 0, (hipStream_t)stream, a, b, c, hw, total, A, B, C,
-                       out);
-    HIP_TRY(hipGetLastError());
-    return CAE_OK;
+    return launch_ew(bn_affine_kernel, total, stream, a, b, c, hw, total, A, B, C, out);
 }
 
 int cae_t_colsum(const void *g16, long pixels, int cp, float *out, void *stream) {
@@ -845,9 +777,7 @@ int cae_t_colsum(const void *g16, long pixels, int cp, float *out, void *stream)
     const int threads = (256 / cp) * cp;
     const long rows = 256 / cp;
     const unsigned grid = (unsigned)std::min<long>(std::max<long>((pixels + rows - 1) / rows, 1), 1024);
-    hipLaunchKernelGGL(colsum_bf16_kernel, dim3(grid), dim3(threads), 0, st, (const __bf16 *)g16, pixels, cp, out);
-    HIP_TRY(hipGetLastError());
-    return CAE_OK;
+    return launch(colsum_bf16_kernel, dim3(grid), dim3(threads), 0, st, (const __bf16 *)g16, pixels, cp, out);
 }
 
 }  // extern "C"

@@ -39,6 +39,12 @@ typedef short s16x4 __attribute__((ext_vector_type(4)));
 
 constexpr int MAX_TAPS = 25;
 
+// What the host launch layer (cae_train.hip) and the kernels below have to agree on.  The per-kernel limits stand in
+// front of their kernels, each next to the register-array size it mirrors.
+constexpr int LDS_BUDGET = 160 * 1024;  // dynamic LDS a block may ask for (bytes; gfx950)
+constexpr int TRAIN_CUS = 256;          // compute units the persistent grids are sized to
+constexpr int MAX_CT = 6;               // 32-channel tiles of a tensor (192 channels)
+
 // ---------------------------------------------------------------------------------------------------------------
 // weights -> MFMA B fragments, on the device (the weights change every optimiser step):
 //   packed[q][t][nt][s][lane][e] = W(k = 32q + 16s + 8(lane>>5) + e, n = 32nt + (lane&31), tap t)  as bf16,
@@ -91,6 +97,8 @@ struct GGArgs {
     short dy[MAX_TAPS], dx[MAX_TAPS], wt[MAX_TAPS];
 };
 
+constexpr int GG_HALO_INSTR = 80;  // most LDS-DMA instructions (1 KiB) of a halo: gather_gemm_kernel's 4 waves x MAXP
+
 template <int NT, bool PIPE>
 __global__ void __launch_bounds__(256, 1) gather_gemm_kernel(const GGArgs p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -111,7 +119,7 @@ __global__ void __launch_bounds__(256, 1) gather_gemm_kernel(const GGArgs p) {
     char *wbuf = smem + (size_t)halo_instr * 1024;
     const char *in_n = (const char *)p.in + (size_t)n * p.IH * p.IW * p.Ck * 2;
 
-    constexpr int MAXP = 20;  // ceil(4 * 35 * 35 / 64 / 4)
+    constexpr int MAXP = GG_HALO_INSTR / 4;  // 20 = ceil(4 * 35 * 35 / 64 / 4)
     // this thread's halo pieces (same for every chunk / slice): byte offset inside the sample, or ~0 = zeros
     const int npieces = PIPE ? p.nq * plane : pieces;
     unsigned hoff[MAXP];
@@ -305,6 +313,8 @@ __global__ void __launch_bounds__(256, 1) gather_gemm_kernel(const GGArgs p) {
 // groups; the LDS-DMA writes lane-linear slots, so the same involution picks the SOURCE piece of every slot when staging.
 __device__ __forceinline__ int gg8_swz(int piece) { return piece ^ ((piece >> 4) & 3); }
 
+constexpr int GG8_HALO_INSTR = 80;  // most LDS-DMA instructions of a slice's halo: gg8_kernel's 8 waves x MAXP
+
 template <int NT, int NQ, int NTAPS>
 __global__ void __launch_bounds__(512, 1) gg8_kernel(const GGArgs p) {
     constexpr int NW = 8, KSTEPS = NQ / 2;
@@ -327,7 +337,7 @@ __global__ void __launch_bounds__(512, 1) gg8_kernel(const GGArgs p) {
     const size_t sample_bytes = (size_t)p.IH * p.IW * p.Ck * 2;
 
     // this thread's halo pieces of a slice: byte offset inside the sample, or ~0 = zeros
-    constexpr int MAXP = 10;  // 80 LDS-DMA instructions (80 KiB of halo) over 8 waves
+    constexpr int MAXP = GG8_HALO_INSTR / NW;  // 10: 80 LDS-DMA instructions (80 KiB of halo) over 8 waves
     unsigned hoff[MAXP];
 #pragma unroll
     for (int i = 0; i < MAXP; ++i) {
@@ -463,6 +473,8 @@ __host__ __device__ constexpr int gg8t_parity(int t) {
     return EXT ? (t < 4 ? 0 : (t < 6 ? 1 : (t < 8 ? 2 : 3))) : (t < 1 ? 0 : (t < 3 ? 1 : (t < 5 ? 2 : 3)));
 }
 
+constexpr int GG8T_HALO_INSTR = 32;  // most LDS-DMA instructions of a slice's halo: gg8t_kernel's 8 waves x MAXP
+
 template <bool EXT>
 __global__ void __launch_bounds__(512, 1) gg8t_kernel(const GGArgs p) {
     constexpr int NW = 8, NT = 2, NQ = 4, KSTEPS = 2, NTAPS = 9;
@@ -485,7 +497,7 @@ __global__ void __launch_bounds__(512, 1) gg8t_kernel(const GGArgs p) {
     const size_t buf_bytes = (size_t)(h_instr + W_INSTR) * 1024;
     const size_t sample_bytes = (size_t)p.IH * p.IW * p.Ck * 2;
 
-    constexpr int MAXP = 4;  // 4 x 18 x 18 pieces / 64 / 8 waves
+    constexpr int MAXP = GG8T_HALO_INSTR / NW;  // 4: 4 x 18 x 18 pieces / 64 / 8 waves
     unsigned hoff[MAXP];
 #pragma unroll
     for (int i = 0; i < MAXP; ++i) {
@@ -748,6 +760,9 @@ __global__ void __launch_bounds__(256, 1) wgrad_kernel(const WGArgs p) {
 //   LDS-DMA while sample k multiplies; 8 waves = 2 position groups (tile rows 4 kg .. 4 kg + 3) x 4 b-tiles, every wave
 //   with its own partial sums (9 taps x 16 registers), flushed by atomics at the end as before.  Cb <= 128.
 // ---------------------------------------------------------------------------------------------------------------
+constexpr int WG8_X_INSTR = 64;  // most LDS-DMA instructions of the X halo: wgrad8_kernel's 8 waves x MAXX
+constexpr int WG8_MAX_CB = 128;  // most b channels: 128 positions x Cb / 8 pieces = 8 waves x MAXY instructions of Y
+
 __global__ void __launch_bounds__(512, 1) wgrad8_kernel(const WGArgs p, int tiles_per_image, int sample_step) {
     constexpr int NW = 8;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -771,7 +786,7 @@ __global__ void __launch_bounds__(512, 1) wgrad8_kernel(const WGArgs p, int tile
     const int i0 = ty * 8, j0 = tx * 16;
 
     // source offsets of this thread's staging pieces inside a sample (~0 = zeros), once per block
-    constexpr int MAXX = 8, MAXY = 4;  // <= 64 KiB of X halo, 32 KiB of Y (Cb <= 128)
+    constexpr int MAXX = WG8_X_INSTR / NW, MAXY = 128 * (WG8_MAX_CB / 8) / 64 / NW;  // 8, 4: <= 64 KiB of X halo, 32 KiB of Y
     unsigned xoff[MAXX], yoff[MAXY];
 #pragma unroll
     for (int i = 0; i < MAXX; ++i) {
