@@ -105,19 +105,23 @@ inline int bypass_digits(uint32_t raw) {
     return n;
 }
 
-// number of coder steps symbol (value - offset) costs beyond its own
-inline void classify(int32_t sym, int32_t offset, int32_t max_value, int32_t &value, uint32_t &raw, bool &esc) {
-    value = sym - offset;
+// table index of symbol `sym` and, for a symbol outside the support, its escape value.  64-bit arithmetic, as the device
+// count kernel: sym - offset, -2 * value and 2 * (value - max_value) overflow 32 bits for symbols near INT32_MIN /
+// INT32_MAX (a saturated latent), which count_steps has to see in order to refuse them.  raw: up to 2^33.
+inline void classify(int32_t sym, int32_t offset, int32_t max_value, int32_t &value, uint64_t &raw, bool &esc) {
+    const int64_t wide = (int64_t)sym - offset;
     raw = 0;
     esc = false;
-    if (value < 0) {
-        raw = (uint32_t)(-2 * value - 1);
+    if (wide < 0) {
+        raw = (uint64_t)(-2 * wide - 1);
         value = max_value;
         esc = true;
-    } else if (value >= max_value) {
-        raw = (uint32_t)(2 * (value - max_value));
+    } else if (wide >= max_value) {
+        raw = (uint64_t)(2 * (wide - max_value));
         value = max_value;
         esc = true;
+    } else {
+        value = (int32_t)wide;
     }
 }
 
@@ -133,19 +137,19 @@ static int count_steps(const EntropyTables &T, const int32_t *symbols, int hw, s
         const int32_t *s = symbols + (size_t)c * hw;
         size_t esc_steps = 0;
         unsigned nesc = 0;  // branch-free (vectorisable) scan; escapes are rare
-        for (int i = 0; i < hw; ++i) nesc += (unsigned)(s[i] - off) >= (unsigned)maxv;
+        for (int i = 0; i < hw; ++i) nesc += (uint64_t)((int64_t)s[i] - off) >= (uint64_t)maxv;
         for (int i = 0; nesc && i < hw; ++i) {
-            const int32_t value = s[i] - off;
+            const int64_t value = (int64_t)s[i] - off;
             if (value < 0 || value >= maxv) {
                 int32_t v;
-                uint32_t raw;
+                uint64_t raw;
                 bool esc;
                 classify(s[i], off, maxv, v, raw, esc);
                 // the escape code carries raw in 4-bit digits counted by a 32-bit shift loop upstream:
                 // values with raw >= 2^28 are not representable (upstream shifts by 32 there)
                 if (raw >= (1u << 28) || s[i] > (1 << 27) || s[i] < -(1 << 27))
                     return fail(CAE_ERR_ARG, "symbol %d (channel %d) is outside the codable range", s[i], c);
-                const int nb = bypass_digits(raw);
+                const int nb = bypass_digits((uint32_t)raw);
                 esc_steps += (size_t)(nb / (int)kMaxBypass) + 1 + nb;
             }
         }
@@ -189,10 +193,11 @@ int encode_streams(const EntropyTables &T, const int32_t *const *symbols, int hw
         auto step = [&](uint64_t &xs, uint32_t *&wp, int32_t sym) __attribute__((always_inline)) {
             int32_t v = sym - off;
             if (__builtin_expect((unsigned)v >= (unsigned)maxv, 0)) {
-                uint32_t raw;
+                uint64_t wide;
                 bool esc;
                 BackWriter bw{wp};
-                classify(sym, off, maxv, v, raw, esc);
+                classify(sym, off, maxv, v, wide, esc);
+                const uint32_t raw = (uint32_t)wide;  // < 2^28: count_steps has refused the rest
                 const int nb = bypass_digits(raw);
                 for (int j = nb - 1; j >= 0; --j) put_bits(xs, bw, (raw >> (j * kBypassBits)) & kMaxBypass);
                 put_bits(xs, bw, (uint32_t)(nb % (int)kMaxBypass));

@@ -36,6 +36,7 @@ constexpr int kStage = kLanes * (kChunk + 1);  // int32 words of the staging til
 constexpr int kScanThreads = 1024;
 constexpr int kCountThreads = 256;
 constexpr int kMaxStride = 4096;  // CDF row length the LDS-staged rows allow (24 B per EncSym)
+constexpr int kMaxStreams = 65535;  // one grid row per stream in the count and compact kernels
 constexpr int kStatusRange = CAE_ERR_ARG, kStatusSpace = CAE_ERR_NOMEM, kStatusCorrupt = CAE_ERR_CORRUPT;
 
 using EncSym = EntropyTables::EncSym;
@@ -474,6 +475,8 @@ using namespace cae;
 // argument checks shared by the device coder entry points (before anything touches the device)
 static int device_coder_args(Model *m, int n, int hw) {
     if (n <= 0 || hw <= 0) return fail(CAE_ERR_ARG, "bad shape (n=%d, hw=%d)", n, hw);
+    if (n > kMaxStreams)
+        return fail(CAE_ERR_ARG, "%d streams exceed the %d of one device coder call: split the batch", n, kMaxStreams);
     if (m->ent.channels == 0) return fail(CAE_ERR_ARG, "entropy model not set");
     if ((int64_t)m->ent.channels * hw >= INT_MAX)
         return fail(CAE_ERR_ARG, "stream of %d x %d symbols too long", m->ent.channels, hw);

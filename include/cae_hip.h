@@ -522,8 +522,9 @@ int cae_rans_decode_batch(cae_model_t *m, const uint8_t *const *bufs, const size
  * The same streams, byte for byte, coded by HIP kernels (csrc/cae_rans_device.hip): one stream per lane, the
  * handle's tables (cae_model_set_entropy) kept on the device and re-uploaded into a fresh buffer after every table
  * change.  Launches are asynchronous on `stream`; the per-stream results are valid once that stream's work is done.
- * Shapes: n_streams >= 1, hw >= 1, CDF rows of at most 4096 entries (else CAE_ERR_UNSUPPORTED).  Argument errors
- * return CAE_ERR_ARG before anything touches the device.
+ * Shapes: n_streams 1..65535 (one grid row per stream; CAE_ERR_ARG otherwise: split larger batches), hw >= 1, CDF rows
+ * of at most 4096 entries (else CAE_ERR_UNSUPPORTED).  Argument errors return CAE_ERR_ARG before anything touches the
+ * device.
  *
  * Encode: symbols_dev (n_streams, channels, hw) int32 -> the streams packed densely into out_dev (stream i =
  * out_dev[offsets_dev[i] .. offsets_dev[i+1]), offsets_dev int64 [n_streams + 1]); status_dev int32 [n_streams] per

@@ -245,7 +245,12 @@ def rans_symbolize(symbols, indexes, cdfs, cdf_lengths, offsets):
 
 
 def rans_encode_with_indexes(symbols, indexes, cdfs, cdf_lengths, offsets) -> bytes:
-    syms = rans_symbolize(symbols, indexes, cdfs, cdf_lengths, offsets)
+    return encode_stack(rans_symbolize(symbols, indexes, cdfs, cdf_lengths, offsets))
+
+
+def encode_stack(syms) -> bytes:
+    """The rANS64 stream of a (start, range, bypass) stack as rans_symbolize builds it.  (On its own it also codes stacks
+    that no encoder emits: tests craft escape codes with it.)"""
     x = RANS64_L
     words: List[int] = []  # emitted in reverse memory order
     for start, rng, bypass in reversed(syms):

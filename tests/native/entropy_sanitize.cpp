@@ -2,11 +2,14 @@
 // Links the product's own cae_entropy.cpp: random CDF tables from cae_pmf_to_quantized_cdf, random symbols including
 // values outside the support (bypass coding), every lockstep width (1, 2, 4 streams per thread through the batch entry
 // points, the single-chunk entry points of the codec front door), round trips, and damaged / truncated streams, which
-// must come back as CAE_ERR_CORRUPT without touching memory they do not own.
+// must come back as CAE_ERR_CORRUPT without touching memory they do not own.  Then the codable-range boundary (symbols up
+// to INT32_MIN / INT32_MAX, where 32-bit arithmetic on them overflows) and rows of 4096 entries.
 // Build + run: tests/test_sanitize.py.
 #include "cae_hip.h"
 #include "cae_internal.hpp"
 
+#include <algorithm>
+#include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -141,11 +144,110 @@ static int run(unsigned seed, int channels, int hw, int n_streams) {
     return 0;
 }
 
+// explicit frequency rows (each sums to 65536) as the handle's tables
+static void set_tables(EntropyTables &T, const std::vector<std::vector<uint32_t>> &freqs, const std::vector<int32_t> &offs) {
+    const int channels = (int)freqs.size();
+    int stride = 0;
+    for (auto &f : freqs) stride = std::max(stride, (int)f.size() + 1);
+    T.channels = channels;
+    T.stride = stride;
+    T.cdf.assign((size_t)channels * stride, 0);
+    T.len.assign(channels, 0);
+    T.off = offs;
+    T.medians.assign(channels, 0.0f);
+    for (int c = 0; c < channels; ++c) {
+        uint32_t run = 0;
+        for (size_t i = 0; i < freqs[c].size(); ++i) {
+            run += freqs[c][i];
+            T.cdf[(size_t)c * stride + i + 1] = (int32_t)run;
+        }
+        T.len[c] = (int)freqs[c].size() + 1;
+    }
+    T.build_tables();
+}
+
+// The codable-range boundary: one symbol at or beyond it in an otherwise ordinary stream, offsets 2 and -6 over an
+// 11-symbol support.  The refusal rule is restated here in 64-bit arithmetic; the coder must reach it without a signed
+// overflow on the way (INT32_MIN - 2, -2 * value, 2 * (value - max_value) do overflow in 32 bits).
+static int boundary() {
+    Model m;
+    EntropyTables &T = m.ent;
+    const std::vector<uint32_t> row = {5000, 5000, 5000, 5000, 5000, 5536, 5000, 5000, 5000, 5000, 5000, 10000};
+    set_tables(T, {row, row}, {2, -6});
+    cae_model_t *mm = reinterpret_cast<cae_model_t *>(&m);
+    const int hw = 9, n_streams = 4;
+    const size_t per = 2 * (size_t)hw;
+    const int64_t P27 = 1ll << 27, P30 = (1ll << 30) + 5;
+    std::vector<int64_t> values = {P27, -P27, P27 + 1, P27 - 1, -P27 + 1, -P27 - 1, INT32_MIN, INT32_MAX, P30, -P30};
+    for (int32_t off : {2, -6}) {
+        const int64_t maxv = (int64_t)row.size() - 1;
+        // raw = 2^28 - 1 | 2^28 + 1 below the support, raw = 2^28 - 2 | 2^28 above it
+        for (int64_t v : {-P27, -P27 - 1, maxv + P27 - 1, maxv + P27}) values.push_back(v + off);
+    }
+    for (int64_t big : values)
+        for (int c = 0; c < 2; ++c) {
+            const int64_t value = big - T.off[c], maxv = T.len[c] - 2;
+            bool refused = false;
+            if (value < 0 || value >= maxv) {
+                const int64_t raw = value < 0 ? -2 * value - 1 : 2 * (value - maxv);
+                refused = raw >= (1ll << 28) || big > P27 || big < -P27;
+            }
+            std::vector<int32_t> sym(n_streams * per);
+            for (size_t i = 0; i < sym.size(); ++i) sym[i] = T.off[i / hw % 2] + (int32_t)(i % 11);
+            for (int s = 0; s < n_streams; ++s) sym[s * per + c * hw + (size_t)(2 * s)] = (int32_t)big;
+            std::vector<uint8_t *> bufs(n_streams, nullptr);
+            std::vector<size_t> ls(n_streams, 0);
+            const int rc = cae_rans_encode_batch(mm, sym.data(), n_streams, hw, bufs.data(), ls.data(), 2);
+            REQUIRE(rc == (refused ? CAE_ERR_ARG : CAE_OK));
+            uint8_t *one = nullptr;
+            size_t len = 0;
+            REQUIRE(rans_encode_chunk(T, sym.data(), hw, 0, &one, &len) == rc);
+            if (rc != CAE_OK) continue;
+            REQUIRE(len == ls[0] && memcmp(one, bufs[0], len) == 0);
+            free(one);
+            std::vector<int32_t> back(sym.size(), 12345);
+            REQUIRE(cae_rans_decode_batch(mm, bufs.data(), ls.data(), n_streams, hw, back.data(), 2) == 0);
+            REQUIRE(back == sym);
+            for (auto *b : bufs) free(b);
+        }
+    return 0;
+}
+
+// rows of 4096 entries (the device coder's limit): an even row, and one dominant symbol followed by 4094 symbols of
+// frequency 1, which share LUT buckets so that the decoder's forward scan runs long
+static int long_rows() {
+    std::mt19937 rng(4096);
+    Model m;
+    EntropyTables &T = m.ent;
+    std::vector<uint32_t> even(4095, 16), skew(4095, 1);
+    even[7] += 16;
+    skew[0] = 65536 - 4094;
+    set_tables(T, {even, skew}, {-2000, 3});
+    REQUIRE(T.stride == 4096 && T.cdf[4095] == 65536 && T.cdf[4096 + 4095] == 65536);
+    cae_model_t *mm = reinterpret_cast<cae_model_t *>(&m);
+    const int hw = 300, n_streams = 4;
+    std::vector<int32_t> sym((size_t)n_streams * 2 * hw);
+    for (size_t i = 0; i < sym.size(); ++i) {
+        const int c = (int)(i / hw % 2);
+        sym[i] = T.off[c] + (int32_t)(rng() % 4200) - 50;  // the whole support, and beyond it on both sides
+    }
+    std::vector<uint8_t *> bufs(n_streams, nullptr);
+    std::vector<size_t> ls(n_streams, 0);
+    REQUIRE(cae_rans_encode_batch(mm, sym.data(), n_streams, hw, bufs.data(), ls.data(), 2) == 0);
+    std::vector<int32_t> back(sym.size(), 12345);
+    REQUIRE(cae_rans_decode_batch(mm, bufs.data(), ls.data(), n_streams, hw, back.data(), 2) == 0);
+    REQUIRE(back == sym);
+    for (auto *b : bufs) free(b);
+    return 0;
+}
+
 int main() {
     const int shapes[][3] = {{1, 1, 1}, {3, 17, 2}, {5, 64, 5}, {7, 33, 9}, {2, 4096, 4}};
     for (unsigned seed = 0; seed < 6; ++seed)
         for (auto &s : shapes)
             if (int rc = run(1000 * seed + (unsigned)s[1], s[0], s[1], s[2])) return rc;
+    if (int rc = boundary()) return rc;
+    if (int rc = long_rows()) return rc;
     printf("entropy_sanitize: ok (lockstep %d)\n", cae_coder_lockstep());
     return 0;
 }

@@ -90,6 +90,10 @@ def test_device_abi_rejects_bad_arguments_without_a_device(cae):
     for args in ((None, 4, 16), (t.h.ptr, 0, 16), (t.h.ptr, 4, 0), (fresh.ptr, 4, 16)):
         assert L.cae_rans_encode_workspace(args[0], args[1], args[2], ctypes.byref(size)) == -1
     assert L.cae_rans_encode_workspace(t.h.ptr, 4, 16, None) == -1
+    # one grid row per stream: 65535 streams at the most
+    assert L.cae_rans_encode_workspace(t.h.ptr, 65535, 16, ctypes.byref(size)) == 0
+    assert L.cae_rans_encode_workspace(t.h.ptr, 65536, 16, ctypes.byref(size)) == -1
+    assert b'65535' in L.cae_last_error()
 
     def enc(h=t.h.ptr, sym=fake, n=4, hw=16, out=fake, offs=fake, status=fake, ws=fake, ws_bytes=1 << 20):
         return L.cae_rans_encode_device(h, sym, n, hw, out, 1 << 20, offs, status, ws, ws_bytes, None)
