@@ -148,6 +148,16 @@ SYMBOLS = {
     'cae_door_decode': (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_size_t]),
     'cae_door_stats': (c_int, [c_void_p, c_void_p, c_int, c_int]),
     'cae_door_hold': (c_int, [c_void_p, c_int]),
+    'cae_seg_weight_count': (c_int, [c_void_p]),
+    'cae_seg_create': (c_int, [c_void_p, c_void_p, c_int, ctypes.POINTER(c_void_p)]),
+    'cae_seg_destroy': (None, [c_void_p]),
+    'cae_seg_stage_count': (c_int, [c_void_p]),
+    'cae_seg_forward': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    'cae_seg_last_ticket': (ctypes.c_int64, []),
+    'cae_seg_range_check': (c_int, [c_void_p, ctypes.c_int64]),
+    'cae_seg_packed_halves': (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    'cae_seg_pack': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_size_t]),
+    'cae_seg_tile': (None, [ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
 }
 
 CAE_ANALYSIS, CAE_SYNTHESIS = 0, 1
@@ -189,6 +199,8 @@ def check(rc: int):
         msg = lib().cae_last_error().decode('utf-8', 'replace')
         if rc == -1:
             raise ValueError(msg)  # the reference / compressai raise ValueError on bad shapes
+        if rc == -6:
+            raise FloatingPointError(msg)  # the call left the valid range of its kernels
         raise CaeError(f'libcae_hip error {rc}: {msg}')
 
 

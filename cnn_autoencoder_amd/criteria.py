@@ -5,8 +5,9 @@
 
 Under ``torch.no_grad()`` the analysis / synthesis tracks and the eval-mode density run on the inference kernels; with
 autograd recording (``train.train_step``) the tracks switch to the training kernels with hand-written backward
-(``train.py``) and the entropy model adds its uniform noise (train mode).  Classifier / segmentation heads and penalty
-terms of the reference are outside the hot path and not built.  The multiscale objective
+(``train.py``) and the entropy model adds its uniform noise (train mode).  Classifier heads and penalty terms of the
+reference are outside the hot path and not built; the segmentation head (``segmenters.JNet``, key ``'seg_model'``)
+runs for inference only.  The multiscale objective
 (``RateMultiscaleMSE``, ``DistMSEPyramidLoss`` of ``_ratedist.py:10-43, 88-93``) scores the colour layers of a
 ``multiscale_analysis`` decoder against a blurred, downsampled pyramid of the input (``pyramid_down``).
 
@@ -31,7 +32,7 @@ def setup_forward_func(enabled_modules: Sequence[str] = ('encoder', 'fact_ent', 
     """decorate_trainable_modules / forward_func of the reference for the modules of the hot path; disabled modules
     are identities exactly as there (`_taskutils.py:40-80`)."""
     enabled = set(enabled_modules)
-    unknown = enabled - {'encoder', 'fact_ent', 'decoder'}
+    unknown = enabled - {'encoder', 'fact_ent', 'decoder', 'seg_model'}
     if unknown:
         raise NotImplementedError(f'modules outside the compression path are not built: {sorted(unknown)}')
 
@@ -39,8 +40,16 @@ def setup_forward_func(enabled_modules: Sequence[str] = ('encoder', 'fact_ent', 
         y = model['encoder'](x) if 'encoder' in enabled else x
         y_q, p_y = model['fact_ent'](y) if 'fact_ent' in enabled else (y, None)
         x_r, fx_brg = model['decoder'](y_q) if 'decoder' in enabled else (y_q, None)
-        return dict(x_r=x_r, fx_brg=fx_brg, y=y, y_q=y_q, p_y=p_y, t_pred=None, t_aux_pred=None, s_pred=None,
-                    s_aux_pred=None)
+        s_pred = s_aux_pred = None
+        if 'seg_model' in enabled:
+            # compressed-domain analysis beside the codec (`_taskutils.py:101-102`): inference only
+            if torch.is_grad_enabled() and (x.requires_grad or any(
+                    q.requires_grad for m in model.values() for q in m.parameters())):
+                raise NotImplementedError("'seg_model' with autograd recording: training the segmentation head is not "
+                                          'built; call forward_func under torch.no_grad()')
+            s_pred, s_aux_pred = model['seg_model'](y_q, fx_brg=fx_brg)
+        return dict(x_r=x_r, fx_brg=fx_brg, y=y, y_q=y_q, p_y=p_y, t_pred=None, t_aux_pred=None, s_pred=s_pred,
+                    s_aux_pred=s_aux_pred)
 
     return forward_func
 

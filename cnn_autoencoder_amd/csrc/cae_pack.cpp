@@ -209,4 +209,43 @@ std::vector<_Float16> pack_pmap_f16(const float *w, int cin, int cout, int njt) 
     });
 }
 
+// ---- segmentation head (cae_kernels_seg.hpp) --------------------------------------------------------------
+// channel tiles per block of seg_conv_f16_kernel<ks, ct> for m output rows, and the groups of such tiles over the grid
+int seg_ct(int m, int ks) {
+    if (m <= 32) return 1;
+    if (m <= 64 || ks == 3) return 2;
+    return 4;
+}
+int seg_groups(int m, int ks) { return (m + 32 * seg_ct(m, ks) - 1) / (32 * seg_ct(m, ks)); }
+int seg_rows(int cout, bool up) { return up ? 4 * ((cout + 7) / 8 * 8) : cout; }
+int seg_chunks(int cin_a, int cin_b) { return ((cin_a + 7) / 8 + (cin_b + 7) / 8 + 1) / 2; }
+
+// [group][q][ky][kx][ct][hl][lane][8]: W(row = 32 (group CT + ct) + (lane&31), k = 16q + 8(lane>>5) + j, ky, kx).
+// k runs over the concatenated PLANE grid of the two sources: the ceil(cin_a / 8) planes of source A, then source B's;
+// the padding channels of either source's last plane (and of an odd last plane pair) are zero rows.
+//   conv (up = false): w is (cout, cin_a + cin_b, ks, ks), row = cout index.
+//   2x2 stride-2 transposed conv (up = true, ks = 1): w is (cin_a, cout, 2, 2); row = (2 dy + dx) CP + co with
+//   CP = cout rounded up to whole planes: four pointwise matrices, one per output parity.
+std::vector<_Float16> pack_seg_f16(const float *w, int cin_a, int cin_b, int cout, int ks, bool up) {
+    const int m = seg_rows(cout, up), ct = seg_ct(m, ks), groups = seg_groups(m, ks);
+    const int pa = (cin_a + 7) / 8, cp = (cout + 7) / 8 * 8, cin = cin_a + cin_b;
+    return pack_split({groups, seg_chunks(cin_a, cin_b), ks, ks, ct}, [=](const int *r, int lane, int j) {
+        const int row = 32 * (r[0] * ct + r[4]) + (lane & 31), k = 16 * r[1] + 8 * (lane >> 5) + j;
+        int ci;
+        if (k < 8 * pa) {
+            if (k >= cin_a) return 0.0f;
+            ci = k;
+        } else {
+            if (k - 8 * pa >= cin_b) return 0.0f;
+            ci = cin_a + k - 8 * pa;
+        }
+        if (row >= m) return 0.0f;
+        if (up) {
+            const int par = row / cp, co = row % cp;
+            return co < cout ? w[((size_t)ci * cout + co) * 4 + par] : 0.0f;
+        }
+        return w[(((size_t)row * cin + ci) * ks + r[2]) * ks + r[3]];
+    });
+}
+
 }  // namespace cae

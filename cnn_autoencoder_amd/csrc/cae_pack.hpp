@@ -26,4 +26,11 @@ std::vector<_Float16> pack_first_f16(const float *w, int cin, int cout, int ks, 
 std::vector<_Float16> pack_last_f16(const float *w, int cin, int cout, int ks);
 std::vector<_Float16> pack_pmap_f16(const float *w, int cin, int cout, int njt);
 
+// segmentation head: launch shape of a layer with m output rows, and its packed f16x3 weights (cae_pack.cpp)
+int seg_ct(int m, int ks);
+int seg_groups(int m, int ks);
+int seg_rows(int cout, bool up);
+int seg_chunks(int cin_a, int cin_b);
+std::vector<_Float16> pack_seg_f16(const float *w, int cin_a, int cin_b, int cout, int ks, bool up);
+
 }  // namespace cae

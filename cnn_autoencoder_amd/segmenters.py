@@ -1,0 +1,363 @@
+"""Compressed-domain segmentation: the reference's ``JNet`` head (``models/tasks/_segmenters.py:307-328``) on the
+quantised latents ``y_q`` and the decoder's per-level features ``fx_brg``, as ``forward_func`` hands them over
+(``_taskutils.py:95-108``).  Eval-mode inference only; the hot path is ``cae_seg_forward`` (csrc/cae_seg.hip,
+csrc/cae_kernels_seg.hpp).  This is analysis beside the codec, not part of it.
+
+The module classes carry the reference's attribute names, so the ``state_dict`` keys and shapes are the reference's
+and its checkpoints load with ``strict=True``.  The parameter holders are ordinary torch layers; they are never called
+on the hot path.  ``force_torch=True`` runs the same head as torch ops on the device (the measurement's comparison and
+a second opinion in the tests).  Not built, and raising ``NotImplementedError``: ``UNet`` with its own analysis track
+(image domain, ``MaxPool``), training the head, calling it while autograd is recording.
+
+Unlike the reference (whose in-place ReLU overwrites the caller's bridges when ``batch_norm=False``) the head never
+writes its inputs.
+"""
+from __future__ import annotations
+
+import ctypes
+import struct
+from typing import Dict, List, Optional, Sequence
+
+import numpy as np
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+from . import _lib
+
+F16_MAX = 65504.0
+EPS = 1e-5
+
+
+def _norm(channels: int, batch_norm: bool) -> nn.Module:
+    return nn.GroupNorm(num_groups=channels, num_channels=channels) if batch_norm else nn.Identity()
+
+
+def _conv3(cin: int, cout: int) -> nn.Conv2d:
+    return nn.Conv2d(cin, cout, kernel_size=3, stride=1, padding=1, bias=False)
+
+
+def _up2(cin: int, cout: int) -> nn.ConvTranspose2d:
+    return nn.ConvTranspose2d(cin, cout, kernel_size=2, stride=2, padding=0, output_padding=0, bias=True)
+
+
+class _Holder(nn.Module):
+    """Parameter holder of one unit: the head's forward runs all units in one library call."""
+
+    def forward(self, *args, **kwargs):
+        raise NotImplementedError(f'{type(self).__name__} is not callable on its own: call the JNet that owns it')
+
+
+class ProjectionUnit(_Holder):
+    """GN, ReLU, 3x3 conv, GN, ReLU on a bridge."""
+
+    def __init__(self, channels_in, channels_out, kernel_size=3, batch_norm=True):
+        super().__init__()
+        if kernel_size != 3:
+            raise NotImplementedError('the segmentation head is built for kernel_size=3')
+        self._bn1 = _norm(channels_in, batch_norm)
+        self._c2 = _conv3(channels_in, channels_out)
+        self._bn2 = _norm(channels_out, batch_norm)
+        self._relu = nn.ReLU(inplace=False)
+
+
+class UpsamplingUnit(_Holder):
+    """3x3 conv, GN, ReLU, 3x3 conv, GN, ReLU, then the 2x2 stride-2 transposed conv (identity at the last level)."""
+
+    def __init__(self, channels_in, channels_unit, channels_out, kernel_size=3, batch_norm=True, upsample=True):
+        super().__init__()
+        if kernel_size != 3:
+            raise NotImplementedError('the segmentation head is built for kernel_size=3')
+        self._c1 = _conv3(channels_in, channels_unit)
+        self._bn1 = _norm(channels_unit, batch_norm)
+        self._c2 = _conv3(channels_unit, channels_unit)
+        self._bn2 = _norm(channels_unit, batch_norm)
+        self._relu = nn.ReLU(inplace=False)
+        self._up_sample = _up2(channels_unit, channels_out) if upsample else nn.Identity()
+
+
+class BottleneckUnit(_Holder):
+    """As JNet patches it: 1x1 conv on the raw latents (no pooling), GN, ReLU, 3x3 conv, GN, ReLU, transposed conv."""
+
+    def __init__(self, channels_latent, channels_in, channels_out, batch_norm=True):
+        super().__init__()
+        self._dwn_sample = nn.Identity()
+        self._c1 = nn.Conv2d(channels_latent, channels_out, kernel_size=1, stride=1, padding=0, bias=False)
+        self._bn1 = _norm(channels_out, batch_norm)
+        self._c2 = _conv3(channels_out, channels_out)
+        self._bn2 = _norm(channels_out, batch_norm)
+        self._relu = nn.ReLU(inplace=False)
+        self._up_sample = _up2(channels_out, channels_in)
+
+
+class UNet(nn.Module):
+    def __init__(self, *args, **kwargs):
+        raise NotImplementedError('UNet with its own analysis track (image domain, MaxPool) is not built: only JNet, the '
+                                  'synthesis track on latents and decoder bridges, is')
+
+
+class _SegConfig(ctypes.Structure):
+    _fields_ = [('channels_bn', ctypes.c_int), ('seg_channels_bn', ctypes.c_int), ('levels', ctypes.c_int),
+                ('num_classes', ctypes.c_int), ('concat_bridges', ctypes.c_int), ('batch_norm', ctypes.c_int),
+                ('bridge_channels', ctypes.c_int * 8), ('level_channels', ctypes.c_int * 8),
+                ('up_channels', ctypes.c_int * 8)]
+
+
+class _SegTaps(ctypes.Structure):
+    _fields_ = [('raw', ctypes.POINTER(ctypes.c_void_p)), ('ab', ctypes.POINTER(ctypes.c_void_p)),
+                ('bridge_ab', ctypes.POINTER(ctypes.c_void_p))]
+
+
+class _SegHandle:
+    """Owns one cae_seg_t."""
+
+    def __init__(self, cfg: _SegConfig, weights: Sequence[np.ndarray]):
+        self._h = ctypes.c_void_p()
+        ptrs = (ctypes.c_void_p * len(weights))(*[w.ctypes.data for w in weights])
+        _lib.check(_lib.lib().cae_seg_create(ctypes.byref(cfg), ptrs, len(weights), ctypes.byref(self._h)))
+
+    @property
+    def ptr(self):
+        return self._h
+
+    def close(self):
+        if self._h:
+            _lib.lib().cae_seg_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class JNet(nn.Module):
+    def __init__(self, seg_channels_net=64, channels_bn=320, seg_channels_bn=1024, seg_channels_expansion=2,
+                 compression_level=4, concat_bridges=False, channels_org=3, channels_net=64, channels_expansion=1,
+                 num_classes=1, batch_norm=True, force_torch=False, **kwargs):
+        # (unknown kwargs -- save_bridges, channels_prg, the codec's own keys -- are swallowed as in the reference)
+        super().__init__()
+        L = int(compression_level)
+        if not 1 <= L <= 8:
+            raise ValueError(f'compression_level {compression_level} outside 1..8')
+        self._concat_bridges = bool(concat_bridges)
+        self._batch_norm = bool(batch_norm)
+        self.force_torch = bool(force_torch)
+        self._channels_bn = int(channels_bn)
+        self._num_classes = int(num_classes)
+        self._bridge_channels = [int(channels_net * channels_expansion ** c) for c in range(L - 1)] + [int(channels_org)]
+        self._level_channels = [int(seg_channels_net * seg_channels_expansion ** c) for c in reversed(range(L))]
+        self._up_channels = [int(seg_channels_net * seg_channels_expansion ** (c - 1)) for c in reversed(range(L))]
+        self._seg_channels_bn = int(seg_channels_bn)
+        self.analysis_track: List = []
+
+        proj, track = [], []
+        for i in range(L):
+            ch = self._level_channels[i]
+            proj.append(ProjectionUnit(self._bridge_channels[i], ch, batch_norm=batch_norm) if concat_bridges
+                        else nn.Identity())
+            track.append(UpsamplingUnit(ch * 2 ** int(bool(concat_bridges)), ch, self._up_channels[i],
+                                        batch_norm=batch_norm, upsample=i + 1 < L))
+        self.bridges_projection = nn.ModuleList(proj)
+        self.synthesis_track = nn.ModuleList(track)
+        self.bottleneck = BottleneckUnit(self._channels_bn, self._level_channels[0], self._seg_channels_bn,
+                                         batch_norm=batch_norm)
+        self.fc = nn.Conv2d(int(seg_channels_net), self._num_classes, kernel_size=1, stride=1, padding=0, bias=True)
+        self._handle: Optional[_SegHandle] = None
+        self._uploaded = None
+
+    # ---- the head as a list of stages, in the library's launch order -----------------------------------------
+    def stage_plan(self) -> List[Dict]:
+        """One entry per convolution: name, ks, up (2x2 stride-2 transposed), weight, bias, norm (the GroupNorm behind
+        it, or None), and its sources in contraction order: ('latent',), ('bridge', i) (normalised by the projection's
+        _bn1, then ReLU), ('raw', s, True) (stage s's output through its (a, b) and ReLU) or ('raw', s, False)
+        (untransformed)."""
+        bn = self._batch_norm
+        plan: List[Dict] = []
+
+        def add(name, conv, srcs, norm=None, up=False):
+            plan.append(dict(name=name, ks=1 if up else conv.kernel_size[0], up=up, weight=conv.weight, bias=conv.bias,
+                             norm=norm if bn else None, has_ab=norm is not None, srcs=srcs))
+            return len(plan) - 1
+
+        b = self.bottleneck
+        s = add('bottleneck._c1', b._c1, [('latent',)], b._bn1)
+        s = add('bottleneck._c2', b._c2, [('raw', s, True)], b._bn2)
+        up = add('bottleneck._up_sample', b._up_sample, [('raw', s, True)], up=True)
+        for i, (p, u) in enumerate(zip(self.bridges_projection, self.synthesis_track)):
+            srcs = [('raw', up, False)]
+            if self._concat_bridges:
+                s = add(f'bridges_projection.{i}._c2', p._c2, [('bridge', i)], p._bn2)
+                srcs = [('raw', s, True)] + srcs
+            s = add(f'synthesis_track.{i}._c1', u._c1, srcs, u._bn1)
+            s = add(f'synthesis_track.{i}._c2', u._c2, [('raw', s, True)], u._bn2)
+            if i + 1 < len(self.synthesis_track):
+                up = add(f'synthesis_track.{i}._up_sample', u._up_sample, [('raw', s, True)], up=True)
+        add('fc', self.fc, [('raw', s, True)])
+        return plan
+
+    def _weight_list(self) -> List[torch.Tensor]:
+        out: List[torch.Tensor] = []
+        for i, st in enumerate(self.stage_plan()):
+            if st['srcs'][0][0] == 'bridge' and self._batch_norm:
+                bn1 = self.bridges_projection[st['srcs'][0][1]]._bn1
+                out += [bn1.weight, bn1.bias]
+            out.append(st['weight'])
+            if st['bias'] is not None:
+                out.append(st['bias'])
+            if st['norm'] is not None:
+                out += [st['norm'].weight, st['norm'].bias]
+        return out
+
+    def _config(self) -> _SegConfig:
+        cfg = _SegConfig()
+        cfg.channels_bn, cfg.seg_channels_bn = self._channels_bn, self._seg_channels_bn
+        cfg.levels, cfg.num_classes = len(self.synthesis_track), self._num_classes
+        cfg.concat_bridges, cfg.batch_norm = int(self._concat_bridges), int(self._batch_norm)
+        for i in range(cfg.levels):
+            cfg.bridge_channels[i] = self._bridge_channels[i]
+            cfg.level_channels[i] = self._level_channels[i]
+            cfg.up_channels[i] = self._up_channels[i]
+        return cfg
+
+    def _sync(self) -> _SegHandle:
+        ws = self._weight_list()
+        version = tuple((w.data_ptr(), w._version) for w in ws)
+        if self._handle is None or version != self._uploaded:
+            host = [np.ascontiguousarray(w.detach().cpu().float().numpy()) for w in ws]
+            handle = _SegHandle(self._config(), host)  # ValueError: a weight, gamma or beta outside the f16 range
+            if self._handle is not None:
+                self._handle.close()
+            self._handle, self._uploaded = handle, version
+        return self._handle
+
+    # ---- call surface --------------------------------------------------------------------------------------------
+    def _check(self, x, fx_brg):
+        if self.training:
+            raise NotImplementedError('training the segmentation head is not built: call .eval() (GroupNorm keeps no '
+                                      'running statistics, eval mode normalises by the data as train mode does)')
+        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
+            raise NotImplementedError('the segmentation head has no backward pass: call it under torch.no_grad()')
+        if x.dim() != 4 or x.size(1) != self._channels_bn:
+            raise ValueError(f'expected latents (B,{self._channels_bn},h,w), got {tuple(x.shape)}')
+        if not self._concat_bridges:
+            return None
+        L = len(self.synthesis_track)
+        if fx_brg is None or len(fx_brg) != L:
+            raise ValueError(f'concat_bridges=True needs {L} bridges (Synthesizer.forward returns them), got '
+                             f'{None if fx_brg is None else len(fx_brg)}')
+        n, _, lh, lw = x.shape
+        for i, b in enumerate(fx_brg):
+            want = (n, self._bridge_channels[i], lh * 2 ** (i + 1), lw * 2 ** (i + 1))
+            if b.dim() != 4 or tuple(b.shape) != want:
+                raise ValueError(f'bridge {i}: expected {want}, got {tuple(b.shape)}')
+        return list(fx_brg)
+
+    def forward(self, x: torch.Tensor, fx_brg=None, taps: bool = False):
+        """y_q (B,channels_bn,h,w), fx_brg: the decoder's bridges (coarsest first, the reconstruction last) ->
+        (logits (B,num_classes,h 2^L,w 2^L), None).  taps=True (tests): (logits, dict of every stage's raw output and
+        (a, b) pairs)."""
+        fx_brg = self._check(x, fx_brg)
+        dev = _lib.require_gpu()
+        x = x.detach().to(device=dev, dtype=torch.float32).contiguous()
+        brg = [b.detach().to(device=dev, dtype=torch.float32).contiguous() for b in fx_brg] if fx_brg else []
+        if self.force_torch:
+            return self._forward_torch(x, brg), None
+        hd = self._sync()
+        n, _, lh, lw = x.shape
+        L = len(self.synthesis_track)
+        logits = torch.empty((n, self._num_classes, lh * 2 ** L, lw * 2 ** L), dtype=torch.float32, device=dev)
+        brg_ptr = (ctypes.c_void_p * L)(*[b.data_ptr() for b in brg]) if brg else None
+        tap_arg, tapped = None, None
+        if taps:
+            plan = self.stage_plan()
+            raw, ab, size = [], [], (lh, lw)
+            for st in plan:
+                cout = st['weight'].shape[1 if st['up'] else 0]
+                if st['up']:
+                    size = (2 * size[0], 2 * size[1])
+                raw.append(torch.zeros((n, cout) + size, dtype=torch.float32, device=dev))
+                ab.append(torch.zeros((n, (cout + 7) // 8 * 8, 2), dtype=torch.float32, device=dev) if st['has_ab'] else None)
+            bab = [torch.zeros((n, (b.size(1) + 7) // 8 * 8, 2), dtype=torch.float32, device=dev) for b in brg]
+            arr = lambda ts: (ctypes.c_void_p * max(len(ts), 1))(*[None if t is None else t.data_ptr() for t in ts])
+            keep = (arr(raw), arr(ab), arr(bab))
+            tap_arg = ctypes.byref(_SegTaps(*[ctypes.cast(a, ctypes.POINTER(ctypes.c_void_p)) for a in keep]))
+            tapped = dict(plan=plan, raw=raw, ab=ab, bridge_ab=bab)
+        L_ = _lib.lib()
+        _lib.check(L_.cae_seg_forward(hd.ptr, x.data_ptr(), brg_ptr, n, lh, lw, logits.data_ptr(), tap_arg,
+                                      _lib.stream_ptr()))
+        ticket = L_.cae_seg_last_ticket()
+        torch.cuda.current_stream().synchronize()
+        _lib.check(L_.cae_seg_range_check(hd.ptr, ticket))  # FloatingPointError: never wrong logits
+        return (logits, tapped) if taps else (logits, None)
+
+    def _forward_torch(self, x: torch.Tensor, brg: List[torch.Tensor]) -> torch.Tensor:
+        """The same head as torch ops on the device."""
+        def gn(v, norm):
+            return v if isinstance(norm, nn.Identity) else F.group_norm(v, norm.num_groups, norm.weight, norm.bias, EPS)
+
+        def unit(v, u):
+            v = F.relu(gn(F.conv2d(v, u._c1.weight, padding=u._c1.padding), u._bn1))
+            v = F.relu(gn(F.conv2d(v, u._c2.weight, padding=1), u._bn2))
+            up = u._up_sample
+            return v if isinstance(up, nn.Identity) else F.conv_transpose2d(v, up.weight, up.bias, stride=2)
+
+        fx = unit(x, self.bottleneck)
+        for i, (p, u) in enumerate(zip(self.bridges_projection, self.synthesis_track)):
+            if self._concat_bridges:
+                b = F.relu(gn(brg[i], p._bn1))
+                b = F.relu(gn(F.conv2d(b, p._c2.weight, padding=1), p._bn2))
+                fx = torch.cat((b, fx), dim=1)
+            fx = unit(fx, u)
+        return F.conv2d(fx, self.fc.weight, self.fc.bias)
+
+
+SEG_MODELS = {'UNet': UNet, 'JNet': JNet}
+
+
+def setup_modules(segment_model_type, **kwargs):
+    return SEG_MODELS[segment_model_type](**kwargs)
+
+
+def load_state_dict(model, checkpoint_state):
+    if 'seg_model' in checkpoint_state.keys():
+        model.load_state_dict(checkpoint_state['seg_model'])
+
+
+def segmenter_from_state_dict(checkpoint, gpu=False, train=False):
+    """checkpoint: path or dict with 'segment_model_type', the constructor's keys and 'seg_model' (the state dict).
+    ``gpu`` is accepted for signature compatibility: the head always runs on the current HIP device."""
+    state = torch.load(checkpoint, map_location='cpu') if isinstance(checkpoint, str) else checkpoint
+    if state.get('segment_model_type', None) not in SEG_MODELS:
+        raise ValueError(f"segment_model_type must be one of {sorted(SEG_MODELS)}, got {state.get('segment_model_type')!r}")
+    if train:
+        raise NotImplementedError('training the segmentation head is not built (train=True)')
+    model = setup_modules(**state)
+    load_state_dict(model, state)
+    if torch.cuda.is_available():
+        model.cuda()
+    model.eval()
+    return model
+
+
+@torch.no_grad()
+def segment_compressed(bufs: Sequence[bytes], model, seg_model) -> torch.Tensor:
+    """Codec chunk byte strings of one tile size -> logits (B, classes, H, W): range decoding, the synthesis track with
+    its bridges, the head.  ``model``: the module dict of ``autoencoder_from_state_dict`` (or a
+    ``ConvolutionalAutoencoder``); ``seg_model``: a ``JNet`` in eval mode."""
+    from .codec import _module
+    model = getattr(model, '_model', model)
+    dec, eb = _module(model['decoder']), _module(model['fact_ent'])
+    level = len(dec.synthesis_track)
+    hw = {struct.unpack('>QQ', bytes(b[:16])) for b in bufs}
+    if len(hw) != 1:
+        raise ValueError('segment_compressed needs chunks of one tile size')
+    h, w = hw.pop()
+    lh, lw = h // 2 ** level, w // 2 ** level
+    dev = _lib.require_gpu()
+    sym_host = eb.decode_symbols([bytes(b[16:]) for b in bufs], lh * lw)
+    sym = torch.from_numpy(sym_host).to(dev).reshape(len(bufs), eb.channels, lh, lw)
+    y_q = eb.dequantize_symbols(sym)
+    _, fx_brg = dec(y_q)
+    return _module(seg_model)(y_q, fx_brg=fx_brg)[0]

@@ -38,7 +38,8 @@ enum cae_status {
     CAE_ERR_HIP = -2,      /* HIP runtime failure */
     CAE_ERR_NOMEM = -3,
     CAE_ERR_UNSUPPORTED = -4,
-    CAE_ERR_CORRUPT = -5   /* bitstream ran past its end */
+    CAE_ERR_CORRUPT = -5,  /* bitstream ran past its end */
+    CAE_ERR_RANGE = -6     /* cae_seg_range_check: the call left the valid range of f16x3, its results are invalid */
 };
 
 enum cae_track { CAE_ANALYSIS = 0, CAE_SYNTHESIS = 1 };
@@ -580,6 +581,68 @@ int cae_door_stats(cae_door_t *door, double *stats /* n */, int n, int reset);
 /* on != 0: the dispatcher starts no further batch (calls queue up; CAE_DOOR_STAT_QUEUED = the number waiting); 0: it
  * resumes.  Lets a caller -- and the tests -- form batches deterministically. */
 int cae_door_hold(cae_door_t *door, int on);
+
+/* ---- segmentation head -------------------------------------------------------------------------
+ * Eval-mode inference of the reference's JNet (models/tasks/_segmenters.py:307-328): the synthesis track of a UNet
+ * on the quantised latents and the decoder's per-level features ("bridges").  A handle of its own, separate from
+ * the codec model.
+ *
+ * Arithmetic.  Bottleneck: 1x1 conv (no bias) on the raw latents, GN, ReLU, 3x3 zero-padded conv, GN, ReLU, 2x2
+ * stride-2 transposed conv (bias).  Level i: [projection of bridge i: GN, ReLU, 3x3 conv, GN, ReLU; concatenated in
+ * front of the running features], 3x3 conv, GN, ReLU, 3x3 conv, GN, ReLU, [2x2 stride-2 transposed conv (bias); not
+ * at the last level]; then fc, a 1x1 conv with bias.  GN = GroupNorm with one group per channel: per (sample,
+ * channel) the mean and the BIASED variance of the plane, eps 1e-5 inside the root, affine (gamma, beta).  The kernels
+ * keep raw fp32 convolution outputs between layers; the consumer stages v = max(fmaf(a, x, b), 0) with
+ * a = gamma rstd, b = beta - mean a (one fp32 fmaf, one max), splits v into f16 halves and contracts on
+ * v_mfma_f32_32x32x16_f16 (f16x3, ACCURACY above).  Statistics are Welford partials per output tile (sums in
+ * double) merged in tile order (Chan, running values in double); nothing is accumulated with atomics: results are
+ * bitwise repeatable.  The inputs are never written.
+ *
+ * VALID RANGE.  Every staged value v (raw latents, transposed-convolution outputs, normalised activations) must be
+ * finite with |v| <= 65504.  The staging code raises the call's overflow word otherwise (also on NaN).  The head has
+ * no fp32 twin yet: after the stream work of the call has completed, cae_seg_range_check(h, cae_seg_last_ticket())
+ * returns CAE_ERR_RANGE for such a call and its logits must not be used.  Weights, gamma and beta outside the f16
+ * range are refused by cae_seg_create (CAE_ERR_ARG).  1024 calls per handle are tracked.
+ *
+ * cae_seg_config: level_channels[i] = channels of level i's unit, up_channels[i] = output channels of its transposed
+ * convolution (i < levels - 1; must equal level_channels[i + 1]); the bottleneck's transposed convolution writes
+ * level_channels[0]; bridge_channels[i] = channels of bridge i (used when concat_bridges).
+ * weights: host arrays in the reference's layouts, in this order (cae_seg_weight_count of them); [..] only with
+ * batch_norm, {..} only with concat_bridges:
+ *   bottleneck: _c1.weight [_bn1.weight _bn1.bias] _c2.weight [_bn2.weight _bn2.bias] _up_sample.weight _up_sample.bias
+ *   level i:    {[_bn1.weight _bn1.bias] _c2.weight [_bn2.weight _bn2.bias]}  (bridges_projection.i)
+ *               _c1.weight [_bn1.weight _bn1.bias] _c2.weight [_bn2.weight _bn2.bias]
+ *               _up_sample.weight _up_sample.bias  (i < levels - 1)                       (synthesis_track.i)
+ *   fc.weight fc.bias */
+typedef struct cae_seg cae_seg_t;
+typedef struct {
+    int channels_bn, seg_channels_bn, levels, num_classes, concat_bridges, batch_norm;
+    int bridge_channels[8], level_channels[8], up_channels[8];
+} cae_seg_config;
+/* Optional taps (tests): per stage s in launch order (cae_seg_stage_count: bottleneck _c1, _c2, _up_sample; per level
+ * {projection _c2} _c1 _c2 [_up_sample]; fc) raw[s] receives the stage's raw output as NCHW fp32 and ab[s] the (a, b)
+ * pairs computed from it, (n, 8 ceil(cout / 8), 2) floats (stages that feed no normalisation write none); bridge_ab[i]
+ * receives the pairs of bridge i, (n, 8 ceil(c / 8), 2).  Any entry may be NULL. */
+typedef struct {
+    float **raw, **ab, **bridge_ab;
+} cae_seg_taps;
+int cae_seg_weight_count(const cae_seg_config *cfg);
+int cae_seg_create(const cae_seg_config *cfg, const float *const *weights_host, int n_weights, cae_seg_t **out);
+void cae_seg_destroy(cae_seg_t *h);
+int cae_seg_stage_count(cae_seg_t *h);
+/* latents_dev (n, channels_bn, lh, lw), bridges_dev[i] (n, bridge_channels[i], lh 2^(i+1), lw 2^(i+1)) (NULL list when
+ * concat_bridges is off), logits_dev (n, num_classes, lh 2^levels, lw 2^levels), all float NCHW on the device.
+ * Workspace is owned by the handle and grown on demand; calls on one handle are ordered in call order whatever stream
+ * they name. */
+int cae_seg_forward(cae_seg_t *h, const float *latents_dev, const float *const *bridges_dev, int n, int lh, int lw,
+                    float *logits_dev, const cae_seg_taps *taps, void *stream);
+int64_t cae_seg_last_ticket(void); /* thread-local: range ticket of this thread's latest cae_seg_forward */
+int cae_seg_range_check(cae_seg_t *h, int64_t ticket); /* CAE_OK, or CAE_ERR_RANGE: the call's logits are invalid */
+/* Host packer of the head's weights (tests): halves written by cae_seg_pack, 0 for arguments it refuses.  up: the 2x2
+ * stride-2 transposed convolution as four pointwise matrices, rows (2 dy + dx) 8 ceil(cout / 8) + co. */
+size_t cae_seg_packed_halves(int cin_a, int cin_b, int cout, int ks, int up);
+int cae_seg_pack(const float *w, int cin_a, int cin_b, int cout, int ks, int up, uint16_t *out, size_t capacity);
+void cae_seg_tile(int *tx, int *ty); /* output tile of the head's convolution kernel, in pixels */
 
 #ifdef __cplusplus
 }
