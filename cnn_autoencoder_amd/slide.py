@@ -12,6 +12,7 @@ its uint8 wrap-around).
 from __future__ import annotations
 
 import math
+import time
 from typing import Dict, List, Sequence, Tuple
 
 import numpy as np
@@ -79,6 +80,37 @@ def _dev():
     return _lib.require_gpu()
 
 
+class _PinnedRing:
+    """A ring of pinned host buffers: slot ``k % slots`` serves batch k.  A slot remembers the event of the asynchronous
+    copy that still reads it and is handed out again only when that copy is done."""
+
+    def __init__(self, slots: int):
+        self.slots = slots
+        self._bufs = [None] * slots
+        self._readers = [None] * slots
+
+    def take(self, k: int, shape, dtype) -> torch.Tensor:
+        """the buffer of batch k, free of its last reader; a changed shape or dtype allocates it anew"""
+        i = k % self.slots
+        reader, self._readers[i] = self._readers[i], None
+        if reader is not None:
+            reader.synchronize()
+        buf = self._bufs[i]
+        if buf is None or buf.shape != tuple(shape) or buf.dtype != dtype:
+            buf = self._bufs[i] = torch.empty(tuple(shape), dtype=dtype, pin_memory=True)
+        return buf
+
+    def read_by(self, k: int, event) -> None:
+        """`event` is behind an asynchronous copy that reads the buffer of batch k"""
+        self._readers[k % self.slots] = event
+
+
+def _clock(tm, key, t0):
+    """the seconds since `t0` go to a driver's timers: one list per key, since several workers may append at once"""
+    if tm is not None:
+        tm[key].append(time.perf_counter() - t0)
+
+
 class SlideCoder:
     """Batched compress -> decompress of resident tile batches on this rank's GPU.
 
@@ -107,8 +139,7 @@ class SlideCoder:
         self.encode_threads, self.decode_threads = self._split_budget(coder_threads)
         import os
         self.depth = int(os.environ.get('CAE_PIPELINE_DEPTH', '3'))  # batches the analysis runs ahead of the synthesis in run()
-        self._pinned = {}
-        self._busy = {}  # pinned buffer key -> event of the asynchronous copy that is still reading it
+        self._rings = {}  # name -> _PinnedRing, see _ring()
         self._copy_stream = None  # side stream of the H2D copies
         self.timers = {}
 
@@ -152,22 +183,6 @@ class SlideCoder:
         y_q = self.eb.decompress(payloads, size, coder=self.coder)
         return self.dec.forward_scale_u8(y_q, scale) if scale else self.dec.forward_u8(y_q)
 
-    # ---- device coder: kernels on a stream per batch in flight, called from worker threads ----------------------
-    def _coder_stream(self, k):
-        if self._coder_streams is None:
-            self._coder_streams = [torch.cuda.Stream(_dev()) for _ in range(max(1, self.depth))]
-        return self._coder_streams[k % len(self._coder_streams)]
-
-    def _device_encode(self, k, sym):
-        """symbols of batch k (complete: the caller has waited for them) -> PackedStreams on the host"""
-        with torch.cuda.device(sym.device), torch.cuda.stream(self._coder_stream(k)):
-            return self.eb.encode_symbols_device(sym)
-
-    def _device_decode(self, k, payloads, hw):
-        """payloads -> (n, C, hw) int32 symbols in HBM, complete when this returns (allocated on the coder stream)"""
-        with torch.cuda.device(_dev()), torch.cuda.stream(self._coder_stream(k)):
-            return self.eb.decode_symbols_device(payloads, hw)
-
     @torch.no_grad()
     def tile_sse(self, rec: torch.Tensor, tiles: torch.Tensor) -> torch.Tensor:
         """per-tile sum of squared error of two (n,h,w,c) uint8 batches -> (n,) float64 on the GPU."""
@@ -189,40 +204,32 @@ class SlideCoder:
         stats = tile_stats([len(p) + 16 for p in payloads], sse.tolist(), h * w * c)
         return payloads, rec, stats
 
-    # ---- pipelined one-way streams (what compress.py / decompress.py do: encode only, decode only) ------------
-    def _to_device(self, batch, k, stream):
-        """A (n,h,w,c) uint8 batch on the GPU: CUDA tensors pass through, host arrays go through a pinned staging
-        buffer and an asynchronous H2D on `stream`.  -> (tensor, event | None)."""
-        if isinstance(batch, torch.Tensor) and batch.is_cuda:
-            return batch, None
-        arr = batch.numpy() if isinstance(batch, torch.Tensor) else np.ascontiguousarray(batch)
-        if arr.dtype != np.uint8 or arr.ndim != 4:
-            raise ValueError(f'expected a (n,h,w,c) uint8 batch, got {arr.dtype} {arr.shape}')
-        key = ('t', k % (self.depth + 1))
-        pin = self._pin(key, arr.shape, torch.uint8)
-        self._wait_free(key)  # the H2D that last read this staging buffer
-        pin.numpy()[...] = arr
-        with torch.cuda.stream(stream):
-            dev = pin.to(_dev(), non_blocking=True)
-            ev = torch.cuda.Event(blocking=True)
-            ev.record(stream)
-        self._busy[key] = ev
-        return dev, ev
-
-    def _redo_analysis(self, t, main):
-        """f16x3 range guard, rare path: the analysis of batch `t` overflowed the f16 range -> repeat it on the fp32
-        kernels.  Runs on the calling (worker) thread but on the MAIN stream, so the handle's workspace is used in
-        stream order; returns the symbols once they are complete."""
-        with torch.cuda.device(t.device), torch.cuda.stream(main):
-            sym = self.enc.forward_u8_symbols(t, self.eb)  # guarded call: falls back to fp32 by itself
-            done = torch.cuda.Event(blocking=True)
-            done.record(main)
-        done.synchronize()
-        return sym
-
-    def _redo_synthesis(self, payloads, h, w, main, scale=0):
-        with torch.cuda.device(_dev()), torch.cuda.stream(main):
-            return self.decompress(payloads, h, w, scale)  # guarded calls
+    # ---- pinned rings and streams of the pipelined drivers ----------------------------------------------------
+    def _ring(self, name: str) -> _PinnedRing:
+        """The pinned ring `name`.  The slot counts are in batches; d = `depth`, the batches a driver works ahead."""
+        d = self.depth
+        slots = {
+            # host tiles staged for their H2D (compress_batches): the batch being filled and the one before it, whose
+            # H2D may still run
+            't': 2,
+            # symbols pulled from the GPU: taken when the analysis of batch k is launched, read until batch k is
+            # encoded.  Both drivers launch batch k before they collect batch k-d, so k-d .. k are in use
+            'a': d + 1,
+            # decoded symbols: taken when the decode worker starts batch k, read until H2D(k) is done.  Both drivers hand
+            # batch k to the worker before they issue H2D(k-d), so k-d .. k are in use; one more slot, and the worker
+            # waits for H2D(k-d-2), done long ago, instead of H2D(k-d-1), issued a moment ago
+            'd': d + 2,
+            # reconstructions of decompress_batches(to_host=True): batch k stays valid until the generator has advanced
+            # two more times, and by the end of the second advance the fetches of k+1 .. k+3 have been submitted
+            'o': 4,
+            # per-tile errors of run(): batch k is finalised with a lag of two batches, so k-2 and k-1 are still
+            # pending when k takes its slot
+            's': 3,
+        }[name]
+        ring = self._rings.get(name)
+        if ring is None or ring.slots != slots:
+            ring = self._rings[name] = _PinnedRing(slots)
+        return ring
 
     # (events are created with blocking=True: a host thread that waits for one sleeps instead of spinning on a core --
     #  on a CPU share of 16 per GPU the spinning waiters took cycles from the coder pools)
@@ -231,10 +238,130 @@ class SlideCoder:
             self._copy_stream = torch.cuda.Stream(_dev())
         return self._copy_stream
 
-    def _wait_free(self, key):
-        ev = self._busy.pop(key, None)
-        if ev is not None:
-            ev.synchronize()
+    def _coder_stream(self, k):
+        """device coder: kernels on a stream per batch in flight, called from worker threads"""
+        if self._coder_streams is None:
+            self._coder_streams = [torch.cuda.Stream(_dev()) for _ in range(max(1, self.depth))]
+        return self._coder_streams[k % len(self._coder_streams)]
+
+    # ---- the stages of the pipelined drivers ------------------------------------------------------------------
+    # `main`: the stream of the analysis and synthesis kernels; `up`: the side stream of the H2D copies; `tm`: the
+    # timers of run() (None: not timed).
+    def _launch_analysis(self, k, t, main):
+        """Launches the analysis of batch k ((n,h,w,c) uint8 in HBM).  -> (symbols, range ticket, event behind
+        them, pinned slot the symbols will be pulled into | None with the device coder)."""
+        # quantiser fused into the last layer's epilogue; range check deferred to the worker that waits for `ready`
+        sym, guard = self.enc.forward_u8_symbols(t, self.eb, defer=True)
+        n, C = sym.size(0), sym.size(1)
+        pin = None if self.coder == 'device' else self._ring('a').take(k, (n, C, sym.numel() // (n * C)), torch.int32)
+        ready = torch.cuda.Event(blocking=True)
+        ready.record(main)
+        return sym, guard, ready, pin
+
+    def _in_range(self, out, guard, done, main):
+        """`out` of a deferred call (None: the caller has let go of it) once the event `done` behind the call has passed
+        and its range ticket has been asked; the result of the fp32 repeat if a value had left the f16 range."""
+        done.synchronize()
+        return self._repeat_fp32(guard, main) if guard.overflowed() else out
+
+    def _repeat_fp32(self, guard, main):
+        """f16x3 range guard, rare path: repeats the ticket's own call (same device tensors) on the fp32 kernels.  Runs on
+        the calling thread, often a worker, but on the MAIN stream, so the handle's workspace is used in stream order;
+        returns the result once it is complete."""
+        with torch.cuda.device(main.device), torch.cuda.stream(main):
+            out = guard.rerun()
+            done = torch.cuda.Event(blocking=True)
+            done.record(main)
+        done.synchronize()
+        return out
+
+    def _pull(self, sym, guard, ready, pin, main, tm):
+        """symbols of a launched analysis, complete and in range, pulled into their pinned slot"""
+        from . import _lib
+        sym = self._in_range(sym, guard, ready, main)
+        # D2H on the DMA engines from a worker thread of its own (cae_copy_to_host): a hipMemcpyAsync here runs as a
+        # blit kernel under PyTorch's HIP runtime and held the main stream up for the whole PCIe transfer; in the
+        # encode worker the 2 ms of the copy were serial with the 4-7 ms of range coding and set the step time
+        t0 = time.perf_counter()
+        _lib.check(_lib.lib().cae_copy_to_host(pin.data_ptr(), sym.data_ptr(), sym.numel() * 4))
+        _clock(tm, 'd2h_copy', t0)
+        return pin
+
+    def _host_encode(self, pulled, packed, tm):
+        pin = pulled.result()
+        t0 = time.perf_counter()
+        payloads = self.eb.encode_symbols(pin.numpy(), self.encode_threads, packed=packed)
+        _clock(tm, 'host_encode', t0)
+        return payloads
+
+    def _device_encode(self, k, sym, guard, ready, main, tm):
+        """symbols of a launched analysis, complete and in range, coded on batch k's coder stream -> PackedStreams on
+        the host"""
+        sym = self._in_range(sym, guard, ready, main)
+        t0 = time.perf_counter()
+        with torch.cuda.device(sym.device), torch.cuda.stream(self._coder_stream(k)):
+            payloads = self.eb.encode_symbols_device(sym)
+        _clock(tm, 'host_encode', t0)
+        return payloads
+
+    def _encode_async(self, k, t, main, pull_pool, enc_pool, packed, tm=None):
+        """Launches the analysis of batch k and hands its symbols to the workers.  -> future of the payloads.
+        Host coder: one worker pulls batch k+1 over the DMA engines while the next one encodes batch k.  Device coder:
+        the symbols stay in HBM, one worker per batch in flight, each on a coder stream (`pull_pool` is idle)."""
+        sym, guard, ready, pin = self._launch_analysis(k, t, main)
+        if self.coder == 'device':
+            return enc_pool.submit(self._device_encode, k, sym, guard, ready, main, tm)
+        pulled = pull_pool.submit(self._pull, sym, guard, ready, pin, main, tm)
+        return enc_pool.submit(self._host_encode, pulled, packed, tm)
+
+    def _decode(self, k, payloads, hw, tm=None):
+        """payloads of batch k -> its (n,C,hw) int32 symbols: in a pinned slot that is free again once H2D(k) has run, or
+        with the device coder in HBM (decoded on batch k's coder stream, complete when this returns)."""
+        t0 = time.perf_counter()
+        if self.coder == 'device':
+            stream = self._coder_stream(k)
+            with torch.cuda.device(stream.device), torch.cuda.stream(stream):
+                sym = self.eb.decode_symbols_device(payloads, hw)
+        else:
+            sym = self._ring('d').take(k, (len(payloads), self.eb.channels, hw), torch.int32)
+            self.eb.decode_symbols(payloads, hw, self.decode_threads, out=sym.numpy())
+        _clock(tm, 'host_decode', t0)
+        return sym
+
+    def _launch_synthesis(self, k, sym, lh, lw, main, up, scale=0):
+        """symbols of batch k as _decode left them -> H2D beside the kernels of the main stream, then the synthesis
+        launched on it.  -> (reconstruction (n,h,w,c) uint8, range ticket)."""
+        if self.coder != 'device':
+            with torch.cuda.stream(up):
+                sym = sym.to(main.device, non_blocking=True)
+                copied = torch.cuda.Event(blocking=True)
+                copied.record(up)
+            self._ring('d').read_by(k, copied)
+            main.wait_event(copied)
+        sym.record_stream(main)
+        # dequantiser fused into the layout conversion in front of the first synthesis layer
+        return self.dec.forward_symbols_u8(sym.reshape(sym.size(0), self.eb.channels, lh, lw), self.eb, defer=True,
+                                           scale=scale)
+
+    # ---- pipelined one-way streams (what compress.py / decompress.py do: encode only, decode only) ------------
+    def _to_device(self, batch, k, up, main):
+        """A (n,h,w,c) uint8 batch on the GPU, ready for the main stream: CUDA tensors pass through, host arrays go
+        through a pinned staging buffer and an asynchronous H2D on `up`."""
+        if isinstance(batch, torch.Tensor) and batch.is_cuda:
+            return batch
+        arr = batch.numpy() if isinstance(batch, torch.Tensor) else np.ascontiguousarray(batch)
+        if arr.dtype != np.uint8 or arr.ndim != 4:
+            raise ValueError(f'expected a (n,h,w,c) uint8 batch, got {arr.dtype} {arr.shape}')
+        pin = self._ring('t').take(k, arr.shape, torch.uint8)
+        pin.numpy()[...] = arr
+        with torch.cuda.stream(up):
+            dev = pin.to(_dev(), non_blocking=True)
+            copied = torch.cuda.Event(blocking=True)
+            copied.record(up)
+        self._ring('t').read_by(k, copied)
+        main.wait_event(copied)
+        dev.record_stream(main)
+        return dev
 
     @torch.no_grad()
     def compress_batches(self, batches):
@@ -242,48 +369,15 @@ class SlideCoder:
         the 16-byte chunk header), in order.  The GPU analyses up to `depth` batches ahead while a host worker pulls
         the symbols over the DMA engines and range-encodes them."""
         from concurrent.futures import ThreadPoolExecutor
-        from . import _lib
         main = torch.cuda.current_stream(_dev())
         up = self._h2d_stream()
         depth = self.depth
-
-        def stage(k, batch):
-            t, ev = self._to_device(batch, k, up)
-            if ev is not None:
-                main.wait_event(ev)
-                t.record_stream(main)
-            sym, guard = self.enc.forward_u8_symbols(t, self.eb, defer=True)
-            n, C = sym.size(0), sym.size(1)
-            hw = sym.numel() // (n * C)
-            pin = None if self.coder == 'device' else self._pin(('a', k % (depth + 1)), (n, C, hw), torch.int32)
-            ready = torch.cuda.Event(blocking=True)
-            ready.record(main)
-            return pin, ready, sym, guard, t
-
-        def pull(pin, ready, sym, guard, t):  # worker 1: DMA-engine D2H of batch k+1 while worker 2 encodes batch k
-            ready.synchronize()
-            if guard.overflowed():
-                sym = self._redo_analysis(t, main)
-            _lib.check(_lib.lib().cae_copy_to_host(pin.data_ptr(), sym.data_ptr(), sym.numel() * 4))
-            return pin
-
-        def encode(pulled):
-            return self.eb.encode_symbols(pulled.result().numpy(), self.encode_threads)
-
-        def device_encode(k, pin, ready, sym, guard, t):  # one worker per batch in flight, each on a coder stream
-            ready.synchronize()
-            if guard.overflowed():
-                sym = self._redo_analysis(t, main)
-            return self._device_encode(k, sym)
-
-        device = self.coder == 'device'
-        with ThreadPoolExecutor(max_workers=1) as d2h_pool, ThreadPoolExecutor(max_workers=depth if device else 1) as pool:
+        workers = depth if self.coder == 'device' else 1
+        with ThreadPoolExecutor(max_workers=1) as pull_pool, ThreadPoolExecutor(max_workers=workers) as enc_pool:
             inflight = []
             for k, batch in enumerate(batches):
-                if device:
-                    inflight.append(pool.submit(device_encode, k, *stage(k, batch)))
-                else:
-                    inflight.append(pool.submit(encode, d2h_pool.submit(pull, *stage(k, batch))))
+                inflight.append(self._encode_async(k, self._to_device(batch, k, up, main), main, pull_pool, enc_pool,
+                                                   packed=False))
                 if len(inflight) > depth:
                     yield inflight.pop(0).result()
             while inflight:
@@ -304,191 +398,81 @@ class SlideCoder:
         up = self._h2d_stream()
         depth = self.depth
         lh, lw = h // 2 ** self.level, w // 2 ** self.level
-        C = self.eb.channels
 
-        device = self.coder == 'device'
-
-        def decode(k, payloads):
-            if device:  # symbols straight into HBM; complete when this returns
-                return None, self._device_decode(k, payloads, lh * lw)
-            key = ('d', k % (depth + 2))
-            back = self._pin(key, (len(payloads), C, lh * lw), torch.int32)
-            self._wait_free(key)  # the H2D that last read this buffer
-            self.eb.decode_symbols(payloads, lh * lw, self.decode_threads, out=back.numpy())
-            return key, back
-
-        def synth(item):
-            key, back = item
-            if device:
-                sym = back
-            else:
-                with torch.cuda.stream(up):
-                    sym = back.to(_dev(), non_blocking=True)
-                    ev = torch.cuda.Event(blocking=True)
-                    ev.record(up)
-                self._busy[key] = ev
-                main.wait_event(ev)
-            sym.record_stream(main)
-            rec, guard = self.dec.forward_symbols_u8(sym.reshape(sym.size(0), C, lh, lw), self.eb, defer=True, scale=scale)
-            done = torch.cuda.Event(blocking=True)
-            done.record(main)
-            return rec, guard, done
-
-        def checked(rec, guard, done, payloads):
-            """the reconstruction once it is complete and known to be in range (f16x3 guard; rare fp32 repeat)"""
-            done.synchronize()
-            if guard.overflowed():
-                rec = self._redo_synthesis(payloads, h, w, main, scale)
-                torch.cuda.current_stream(rec.device).synchronize()
-            return rec
-
-        def fetch(j, rec, guard, done, payloads):
-            out = self._pin(('o', j % 4), tuple(rec.shape), torch.uint8)
-            rec = checked(rec, guard, done, payloads)
+        def fetch(k, rec, guard, done):
+            out = self._ring('o').take(k, tuple(rec.shape), torch.uint8)
+            rec = self._in_range(rec, guard, done, main)
             _lib.check(_lib.lib().cae_copy_to_host(out.data_ptr(), rec.data_ptr(), rec.numel()))
             return out.numpy()
 
-        with ThreadPoolExecutor(max_workers=depth if device else 1) as pool, ThreadPoolExecutor(max_workers=1) as out_pool:
-            inflight, outgoing, held, j = [], [], [], 0
+        workers = depth if self.coder == 'device' else 1
+        with ThreadPoolExecutor(max_workers=workers) as pool, ThreadPoolExecutor(max_workers=1) as out_pool:
+            inflight, outgoing, held = [], [], []
 
-            def emit(item, payloads):
-                nonlocal j
-                rec, guard, done = synth(item)
+            def emit(k, sym):
+                rec, guard = self._launch_synthesis(k, sym, lh, lw, main, up, scale)
+                done = torch.cuda.Event(blocking=True)
+                done.record(main)
                 if not to_host:
                     # one reconstruction is held back: its range check waits for its kernels, which run under the
                     # next batch's launch work instead of stalling the stream
-                    held.append((rec, guard, done, payloads))
-                    return [checked(*held.pop(0))] if len(held) > 1 else []
-                outgoing.append(out_pool.submit(fetch, j, rec, guard, done, payloads))
-                j += 1
+                    held.append((rec, guard, done, main))
+                    return [self._in_range(*held.pop(0))] if len(held) > 1 else []
+                outgoing.append(out_pool.submit(fetch, k, rec, guard, done))
                 # one reconstruction stays in flight: its D2H overlaps the next batch's synthesis
                 return [outgoing.pop(0).result()] if len(outgoing) > 1 else []
 
             for k, payloads in enumerate(payload_batches):
-                payloads = list(payloads)
-                inflight.append((pool.submit(decode, k, payloads), payloads))
+                inflight.append((k, pool.submit(self._decode, k, list(payloads), lh * lw)))
                 if len(inflight) > depth:
-                    fut, pl = inflight.pop(0)
-                    yield from emit(fut.result(), pl)
+                    j, fut = inflight.pop(0)
+                    yield from emit(j, fut.result())
             while inflight:
-                fut, pl = inflight.pop(0)
-                yield from emit(fut.result(), pl)
+                j, fut = inflight.pop(0)
+                yield from emit(j, fut.result())
             while held:
-                yield checked(*held.pop(0))
+                yield self._in_range(*held.pop(0))
             while outgoing:
                 yield outgoing.pop(0).result()
 
     # ---- pipelined slide pass ----------------------------------------------------------------
-    def _pin(self, key, shape, dtype):
-        buf = self._pinned.get(key)
-        if buf is None or buf.shape != tuple(shape) or buf.dtype != dtype:
-            buf = torch.empty(shape, dtype=dtype, pin_memory=True)
-            self._pinned[key] = buf
-        return buf
-
     @torch.no_grad()
     def run(self, batches: Sequence[torch.Tensor], keep_payloads: bool = False):
         """Round-trip every batch ((n,h,w,c) uint8 in HBM).  -> (stats (sum n, 3) float64 host tensor,
         payload lists if keep_payloads).  Work of batch k: A = analysis+quantise+D2H (GPU),
         B = rANS encode + decode (host worker), D = H2D+dequantise+synthesis+SSE (GPU)."""
-        import time
         from concurrent.futures import ThreadPoolExecutor
-        from . import _lib
-        dev = batches[0].device
-        main = torch.cuda.current_stream(dev)
+        main = torch.cuda.current_stream(batches[0].device)
         copy_up = self._h2d_stream()  # H2D beside the kernels of the main stream; D2H runs on the DMA engines (HSA)
         K = len(batches)
         # analysis runs DEPTH batches ahead of synthesis: the host always has a batch to code, and the GPU has analysis
         # work while the first batch crosses the host (D2H + encode + decode + H2D ~ 1.8 steps)
         DEPTH = self.depth
-        tm = dict(host_encode=0.0, host_decode=0.0, wait_host=0.0, d2h_copy=0.0)
+        tm = {key: [] for key in ('host_encode', 'host_decode', 'wait_host', 'd2h_copy')}
         all_payloads, stats_parts = [], []
-        # all pinned symbol buffers up front (hipHostMalloc of 100 MB costs ~10 ms: not inside the pipeline)
         device = self.coder == 'device'
+        # all pinned symbol buffers up front (hipHostMalloc of 100 MB costs ~10 ms: not inside the pipeline)
         n0, h0, w0, _ = batches[0].shape
         lh0, lw0 = self.enc.latent_size(h0, w0)
-        for j in range(0 if device else DEPTH + 2):
-            self._pin(('a', j), (n0, self.eb.channels, lh0 * lw0), torch.int32)
-        for j in range(0 if device else DEPTH + 2):
-            self._pin(('d', j), (n0, self.eb.channels, lh0 * lw0), torch.int32)
+        for ring in ([] if device else [self._ring('a'), self._ring('d')]):
+            for j in range(ring.slots):
+                ring.take(j, (n0, self.eb.channels, lh0 * lw0), torch.int32)
 
-        def stage_a(k):
-            t = batches[k]
-            # quantiser fused into the last layer's epilogue; range check deferred to the encode worker
-            sym, guard = self.enc.forward_u8_symbols(t, self.eb, defer=True)
-            n, C = sym.size(0), sym.size(1)
-            hw = sym.numel() // (n * C)
-            # (host coder: in use until encode(k) is done)
-            pin = None if device else self._pin(('a', k % (DEPTH + 2)), (n, C, hw), torch.int32)
-            ready = torch.cuda.Event(blocking=True)
-            ready.record(main)
-            return k, pin, ready, hw, sym, guard
+        def decode(k, encoded, hw):
+            payloads = encoded.result()
+            return payloads, self._decode(k, payloads, hw, tm)
 
-        def host_pull(k, pin, ready, hw, sym, guard):
-            # D2H on the DMA engines from a worker thread of its own (cae_copy_to_host): a hipMemcpyAsync here runs as a
-            # blit kernel under PyTorch's HIP runtime and held the main stream up for the whole PCIe transfer; in the
-            # encode worker the 2 ms of the copy were serial with the 4-7 ms of range coding and set the step time
-            ready.synchronize()
-            if guard.overflowed():  # f16x3 range guard: repeat this batch on the fp32 kernels
-                sym = self._redo_analysis(batches[k], main)
-            t0 = time.perf_counter()
-            _lib.check(_lib.lib().cae_copy_to_host(pin.data_ptr(), sym.data_ptr(), sym.numel() * 4))
-            tm['d2h_copy'] += time.perf_counter() - t0
-            return k, pin, hw
-
-        def host_encode(pull_future):
-            k, pin, hw = pull_future.result()
-            t0 = time.perf_counter()
-            payloads = self.eb.encode_symbols(pin.numpy(), self.encode_threads, packed=not keep_payloads)
-            return k, payloads, hw, pin.shape, time.perf_counter() - t0
-
-        def host_decode(enc_future):
-            k, payloads, hw, shape, te = enc_future.result()
-            t1 = time.perf_counter()
-            # decode straight into pinned memory; the set is free again once H2D(k) has run (DEPTH + 2 sets: the decode
-            # worker may be DEPTH batches ahead of the synthesis whose H2D is still queued)
-            back = self._pin(('d', k % (DEPTH + 2)), shape, torch.int32)
-            self.eb.decode_symbols(payloads, hw, self.decode_threads, out=back.numpy())
-            return payloads, back, te, time.perf_counter() - t1
-
-        # device coder: the same three stages with the symbols kept in HBM -- encode on batch k's coder stream, the bytes
-        # D2H, back H2D and decode on that stream; one worker per batch in flight in each stage
-        def device_encode(k, pin, ready, hw, sym, guard):
-            ready.synchronize()
-            if guard.overflowed():
-                sym = self._redo_analysis(batches[k], main)
-            t0 = time.perf_counter()
-            payloads = self._device_encode(k, sym)
-            return k, payloads, hw, tuple(sym.shape), time.perf_counter() - t0
-
-        def device_decode(enc_future):
-            k, payloads, hw, shape, te = enc_future.result()
-            t1 = time.perf_counter()
-            sym = self._device_decode(k, payloads, hw)
-            return payloads, sym, te, time.perf_counter() - t1
-
-        def stage_d(k, payloads, back):
+        def stage_d(k, payloads, sym):
             t = batches[k]
             n, h, w, c = t.shape
-            if device:
-                sym = back  # decoded into HBM, complete
-            else:
-                with torch.cuda.stream(copy_up):  # H2D beside the kernels of the main stream
-                    sym = back.to(dev, non_blocking=True)
-                    up = torch.cuda.Event(blocking=True)
-                    up.record(copy_up)
-                main.wait_event(up)
-            sym.record_stream(main)
-            lh, lw = h // 2 ** self.level, w // 2 ** self.level
-            # dequantiser fused into the layout conversion in front of the first synthesis layer
-            rec, guard = self.dec.forward_symbols_u8(sym.reshape(n, self.eb.channels, lh, lw), self.eb, defer=True)
+            rec, guard = self._launch_synthesis(k, sym, h // 2 ** self.level, w // 2 ** self.level, main, copy_up)
             sse = self.tile_sse(rec, t)
             # the per-tile errors go to the host on the copy stream, behind an event of their own: read with a plain
             # `.cpu()` on the main stream they queued behind whatever had been launched since (the next batch's kernels),
             # the main thread sat in that copy until the GPU had drained, and every step began with a ~0.2 ms idle gap
             got = torch.cuda.Event()
             got.record(main)
-            sse_host = self._pin(('s', k % 4), (n,), torch.float64)  # (finalised two batches later: 4 sets)
+            sse_host = self._ring('s').take(k, (n,), torch.float64)
             with torch.cuda.stream(copy_up):
                 copy_up.wait_event(got)
                 sse_host.copy_(sse, non_blocking=True)
@@ -497,34 +481,31 @@ class SlideCoder:
             sse.record_stream(copy_up)
             nbytes = ([payloads.nbytes(i) + 16 for i in range(len(payloads))] if hasattr(payloads, 'nbytes')
                       else [len(p) + 16 for p in payloads])
-            return (sse_host, landed), nbytes, h * w * c, guard, (k, payloads)
+            return k, sse_host, landed, guard, nbytes, h * w * c
 
-        pending = []  # ((pinned sse, landed event), nbytes list, samples, range guard, (k, payloads))
+        pending = []  # what stage_d returned, of the batches not yet finalised
 
-        def finalize(entry):
-            """statistics of a finished batch (its range check needs its kernels done: the `landed` event is behind them);
-            done with a lag of two batches inside the loop, so the payload buffers are released as the run proceeds --
-            released all at once after the loop they cost ~2 ms per batch of pure host time inside the timed region"""
-            (sse_pinned, landed), nbytes, samples, guard, (k, payloads) = entry
-            landed.synchronize()  # this batch's kernels and the copy of its errors are done (the range flag too)
+        def finalize(k, sse_pinned, landed, guard, nbytes, samples):
+            """statistics of a finished batch (its range check needs its kernels done: the `landed` event is behind them,
+            and behind the copy of its errors), done with a lag of two batches, so that it does not wait for the GPU"""
+            rec = self._in_range(None, guard, landed, main)
             sse_host = sse_pinned.tolist()
-            if guard.overflowed():  # f16x3 range guard: repeat this batch's synthesis on the fp32 kernels
-                t = batches[k]
-                rec = self._redo_synthesis(payloads, t.shape[1], t.shape[2], main)
-                sse_host = self.tile_sse(rec, t).cpu().tolist()
+            if rec is not None:  # the synthesis was repeated on the fp32 kernels
+                sse_host = self.tile_sse(rec, batches[k]).cpu().tolist()
             stats_parts.append(tile_stats(nbytes, sse_host, samples))
 
         # three host workers: batch k+2 is pulled while batch k+1 is range-encoded and batch k is decoded
+        # (device coder: the same stages with the symbols kept in HBM -- encode on batch k's coder stream, the bytes D2H,
+        # back H2D and decode on that stream; one worker per batch in flight in each stage)
         workers = DEPTH if device else 1
         with ThreadPoolExecutor(max_workers=1) as pull_pool, ThreadPoolExecutor(max_workers=workers) as enc_pool, \
                 ThreadPoolExecutor(max_workers=workers) as dec_pool:
             futs = {}
 
             def submit(k):
-                if device:
-                    futs[k] = dec_pool.submit(device_decode, enc_pool.submit(device_encode, *stage_a(k)))
-                else:
-                    futs[k] = dec_pool.submit(host_decode, enc_pool.submit(host_encode, pull_pool.submit(host_pull, *stage_a(k))))
+                lh, lw = self.enc.latent_size(*batches[k].shape[1:3])
+                encoded = self._encode_async(k, batches[k], main, pull_pool, enc_pool, not keep_payloads, tm)
+                futs[k] = dec_pool.submit(decode, k, encoded, lh * lw)
 
             for k in range(min(DEPTH, K)):
                 submit(k)
@@ -532,17 +513,17 @@ class SlideCoder:
                 if k + DEPTH < K:
                     submit(k + DEPTH)
                 t0 = time.perf_counter()
-                payloads, back, te, td = futs.pop(k).result()
-                tm['wait_host'] += time.perf_counter() - t0
-                tm['host_encode'] += te
-                tm['host_decode'] += td
-                pending.append(stage_d(k, payloads, back))
+                payloads, sym = futs.pop(k).result()
+                _clock(tm, 'wait_host', t0)
+                pending.append(stage_d(k, payloads, sym))
                 if keep_payloads:
                     all_payloads.append(payloads)
+                # the payload buffers are released as the run proceeds: released all at once after the loop they cost
+                # ~2 ms per batch of pure host time inside the timed region
                 del payloads
                 if len(pending) > 2:
-                    finalize(pending.pop(0))
+                    finalize(*pending.pop(0))
         while pending:
-            finalize(pending.pop(0))
-        self.timers = tm
+            finalize(*pending.pop(0))
+        self.timers = {key: sum(spans) for key, spans in tm.items()}
         return torch.cat(stats_parts), all_payloads

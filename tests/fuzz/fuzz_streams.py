@@ -18,7 +18,8 @@ for case in range(n_cases):
     codec = cae.ConvolutionalAutoencoder(checkpoint=synth.synthetic_state(cfg, seed=int(rng.integers(0, 1000))))
     coder = slide.SlideCoder(codec)
     coder.depth = int(rng.integers(1, 4))
-    h, w = 2 ** L * int(rng.integers(1, 6)), 2 ** L * int(rng.integers(1, 9))
+    least = 2 if cfg['kernel_size'] == 5 else 1  # the last level's input (2 per unit) must exceed the reflect padding
+    h, w = 2 ** L * int(rng.integers(least, 6)), 2 ** L * int(rng.integers(least, 9))
     K = int(rng.integers(1, 9))
     sizes = [int(rng.integers(1, 6)) for _ in range(K)]
     host = [rng.integers(0, 256, (n, h, w, 3), dtype=np.uint8) for n in sizes]

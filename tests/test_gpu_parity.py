@@ -496,6 +496,27 @@ def test_one_way_streams_equal_the_simple_calls(cae):
     assert len(host) == 7 and all(np.array_equal(a, b.cpu().numpy()) for a, b in zip(host, rec_want))
 
 
+def test_ring_slots_are_reused_across_batch_sizes(cae):
+    """Batch sizes cycling 3, 1, 2 at depth 1: every pinned ring slot is reallocated for another shape while its
+    neighbours are still in flight.  Both one-way streams and the round trip still equal the unpipelined calls."""
+    from cnn_autoencoder_amd import slide, synth
+    state = synth.synthetic_state(dict(synth.CANONICAL, channels_net=32, channels_bn=48), seed=6)
+    coder = slide.SlideCoder(cae.ConvolutionalAutoencoder(checkpoint=state))
+    coder.depth = 1
+    host = [synth.uniform_tiles(n, 64, 96, seed=10 + k) for k, n in enumerate([3, 1, 2] * 3)]
+    dev = [torch.from_numpy(b).cuda() for b in host]
+    want_p = [coder.compress(b) for b in dev]
+    want_r = [coder.decompress(p, 64, 96) for p in want_p]
+    assert list(coder.compress_batches(iter(host))) == want_p
+    got_r = [r.copy() for r in coder.decompress_batches(iter(want_p), 64, 96, to_host=True)]  # ring buffers: copy at once
+    assert len(got_r) == 9 and all(np.array_equal(a, b.cpu().numpy()) for a, b in zip(got_r, want_r))
+    stats, payloads = coder.run(dev, keep_payloads=True)
+    assert payloads == want_p
+    assert torch.equal(stats[:, 1], torch.cat([coder.tile_sse(r, d) for r, d in zip(want_r, dev)]).cpu())
+    assert stats[:, 0].tolist() == [len(p) + 16 for ps in want_p for p in ps]
+    assert stats[:, 2].tolist() == [64 * 96 * 3] * 18
+
+
 def test_metrics_match_the_oracle(cae):
     """SSIM / PSNR / RMSE per tile on the GPU against the float64 restatements (ragged size, 3 and 1 channels)."""
     from oracle import cae_oracle as O

@@ -185,7 +185,8 @@ def test_stress_state_through_the_codec(cae):
         assert diff.max() <= 1 and (diff > 0).mean() < 1e-3
 
 
-def test_pipelined_drivers_repeat_only_the_batches_that_overflow(cae):
+@pytest.mark.parametrize('coder', ['host', 'device'])
+def test_pipelined_drivers_repeat_only_the_batches_that_overflow(cae, coder):
     """Bright tiles overflow the f16 range in this (activation-free) model, dark ones do not: the pipelined round trip
     and the one-way streams repeat exactly those batches on fp32 and give the results of an all-fp32 run."""
     from oracle import cae_oracle as O
@@ -207,15 +208,15 @@ def test_pipelined_drivers_repeat_only_the_batches_that_overflow(cae):
     ref_codec = cae.ConvolutionalAutoencoder(checkpoint=state)
     for k in ('encoder', 'decoder'):
         ref_codec._model[k].module.precision = 'fp32'
-    ref = slide.SlideCoder(ref_codec)
+    ref = slide.SlideCoder(ref_codec, coder=coder)
     want = [ref.roundtrip(b) for b in batches]
 
     codec = cae.ConvolutionalAutoencoder(checkpoint=state)
-    coder = slide.SlideCoder(codec)
-    coder.depth = 2
+    sc = slide.SlideCoder(codec, coder=coder)
+    sc.depth = 2
     enc = codec._model['encoder'].module
     assert enc.precision_code() == 1
-    stats, payloads = coder.run(batches, keep_payloads=True)
+    stats, payloads = sc.run(batches, keep_payloads=True)
     assert enc.fp32_fallbacks == 2
     # dark batches ran on f16x3 (same symbols up to float-noise flips are not guaranteed bit for bit against fp32):
     # the bright ones must equal the fp32 run exactly, the dark ones within the flip allowance
@@ -225,8 +226,67 @@ def test_pipelined_drivers_repeat_only_the_batches_that_overflow(cae):
             assert torch.equal(stats[3 * k:3 * k + 3], st_ref)
         else:
             assert all(abs(len(a) - len(b)) <= 8 for a, b in zip(pl, pl_ref))
-    got = list(coder.compress_batches(iter(order)))
+    got = list(sc.compress_batches(iter(order)))
     assert enc.fp32_fallbacks == 4
     assert got[1] == want[1][0] and got[4] == want[4][0]
-    rec = list(coder.decompress_batches(iter([w[0] for w in want]), 64, 96))
+    rec = list(sc.decompress_batches(iter([w[0] for w in want]), 64, 96))
     assert len(rec) == 5 and all(int((r.int() - w[1].int()).abs().max()) <= 1 for r, w in zip(rec, want))
+
+
+@pytest.mark.parametrize('coder', ['host', 'device'])
+def test_pipelined_drivers_repeat_the_synthesis_of_batches_that_overflow(cae, coder):
+    """The decoder's turn: the latents of bright tiles drive this (activation-free) synthesis beyond the f16 range, those
+    of dark tiles round to zero and do not.  Every driver repeats exactly the bright batches on the fp32 kernels and
+    gives what a coder with an fp32 decoder gives (the encoders are the same, so the payloads are)."""
+    from oracle import cae_oracle as O
+    from cnn_autoencoder_amd import slide, synth
+    cfg = dict(synth.CANONICAL, channels_net=32, channels_bn=48, compression_level=3, act_layer_type=None)
+    state = synth.synthetic_state(cfg, seed=15)
+    state['decoder']['synthesis_track.0.model.0.weight'] *= 4.0e4
+    state['decoder']['synthesis_track.2.model.0.weight'] *= 2.5e-5
+    rng = np.random.default_rng(5)
+    dark = [rng.integers(0, 12, (3, 64, 96, 3), dtype=np.uint8) for _ in range(3)]
+    bright = [rng.integers(200, 256, (3, 64, 96, 3), dtype=np.uint8) for _ in range(2)]
+    enc_l, dec_l = oracle_layers(state, 'encoder'), oracle_layers(state, 'decoder')
+
+    def inner_maximum(t):  # of the synthesis of the rounded latents (CPU oracle)
+        y, _ = O.analysis_forward(torch.from_numpy(t).permute(0, 3, 1, 2).float() / 255.0, enc_l)
+        return max(_track_maxima(O, torch.round(y), dec_l, synthesis=True)[1][:-1])
+    assert all(inner_maximum(t) < 5e4 for t in dark)
+    assert all(inner_maximum(t) > 8e4 for t in bright)
+    order = [dark[0], bright[0], dark[1], dark[2], bright[1]]
+    over = (1, 4)
+    batches = [torch.from_numpy(b).cuda() for b in order]
+
+    ref_codec = cae.ConvolutionalAutoencoder(checkpoint=state)
+    ref_codec._model['decoder'].module.precision = 'fp32'
+    ref = slide.SlideCoder(ref_codec, coder=coder)
+    want = [ref.roundtrip(b) for b in batches]  # (payloads, reconstruction, statistics) per batch
+    want_stats = torch.cat([w[2] for w in want])
+
+    codec = cae.ConvolutionalAutoencoder(checkpoint=state)
+    sc = slide.SlideCoder(codec, coder=coder)
+    sc.depth = 2
+    enc, dec = codec._model['encoder'].module, codec._model['decoder'].module
+    assert enc.precision_code() == 1 and dec.precision_code() == 1
+    stats, payloads = sc.run(batches, keep_payloads=True)
+    assert [list(p) for p in payloads] == [w[0] for w in want]
+    for k in over:
+        assert torch.equal(stats[3 * k:3 * k + 3], want_stats[3 * k:3 * k + 3])
+    assert torch.equal(stats[:, 0], want_stats[:, 0])
+    assert (dec.fp32_fallbacks, enc.fp32_fallbacks) == (2, 0)
+    packed_stats, none = sc.run(batches, keep_payloads=False)  # the packed hand-off from encoder to decoder
+    assert torch.equal(packed_stats, stats) and none == []
+    assert (dec.fp32_fallbacks, enc.fp32_fallbacks) == (4, 0)
+
+    def check(recs):
+        assert len(recs) == 5
+        for k, (r, w) in enumerate(zip(recs, want)):
+            if k in over:
+                assert torch.equal(r, w[1].cpu())
+            else:
+                assert int((r.int() - w[1].cpu().int()).abs().max()) <= 1
+    check([r.cpu() for r in sc.decompress_batches(iter([w[0] for w in want]), 64, 96)])
+    assert dec.fp32_fallbacks == 6
+    check([torch.from_numpy(r.copy()) for r in sc.decompress_batches(iter([w[0] for w in want]), 64, 96, to_host=True)])
+    assert (dec.fp32_fallbacks, enc.fp32_fallbacks) == (8, 0)
