@@ -158,6 +158,9 @@ SYMBOLS = {
     'cae_seg_packed_halves': (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
     'cae_seg_pack': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_size_t]),
     'cae_seg_tile': (None, [ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
+    'cae_seg_predict': (c_int, [c_void_p, c_void_p, c_int, c_int, c_size_t, c_float, c_int, c_void_p, c_void_p, c_void_p,
+                                c_void_p, c_size_t, c_void_p]),
+    'cae_seg_predict_workspace': (c_size_t, [c_int, c_int, c_size_t]),
 }
 
 CAE_ANALYSIS, CAE_SYNTHESIS = 0, 1

@@ -9,6 +9,10 @@ on the hot path.  ``force_torch=True`` runs the same head as torch ops on the de
 a second opinion in the tests).  Not built, and raising ``NotImplementedError``: ``UNet`` with its own analysis track
 (image domain, ``MaxPool``), training the head, calling it while autograd is recording.
 
+``predict`` / ``class_metrics`` turn logits into what the reference's harness hands out (class map, scores, counts and
+metrics; ``cae_seg_predict``, csrc/cae_seg_predict.hip); ``slide.SlideCoder.segment_batches`` and ``zarrio.segment_image``
+run whole slides through codec, head and prediction.
+
 Unlike the reference (whose in-place ReLU overwrites the caller's bridges when ``batch_norm=False``) the head never
 writes its inputs.
 """
@@ -361,3 +365,90 @@ def segment_compressed(bufs: Sequence[bytes], model, seg_model) -> torch.Tensor:
     y_q = eb.dequantize_symbols(sym)
     _, fx_brg = dec(y_q)
     return _module(seg_model)(y_q, fx_brg=fx_brg)[0]
+
+
+# ---- what the reference's harness makes of the logits (test_cae_classifier.py:46-55, utils/_metrics.py:79-193) -------
+COUNT_KEYS = ('tp', 'tn', 'fp', 'fn', 'p', 'tp_top')  # the columns of a counts record
+
+
+def threshold_logit(threshold: float, threshold_on: str = 'scores') -> float:
+    """The fp32 value the one-class logits are compared with.  'scores': the logit of the score threshold,
+    float32(log(thr / (1 - thr))) evaluated in double, so that ``sigmoid(x) > thr`` (compute_metrics_per_image,
+    _metrics.py:172) becomes an exact fp32 compare the host can replay; 'logits': the threshold itself, compared with the
+    logit as save_pred2zarr does (test_cae_classifier.py:54)."""
+    thr = float(threshold)
+    if threshold_on == 'logits':
+        if not np.isfinite(thr):
+            raise ValueError(f'threshold must be finite, got {threshold!r}')
+        return float(np.float32(thr))
+    if threshold_on != 'scores':
+        raise ValueError(f"threshold_on must be 'scores' or 'logits', got {threshold_on!r}")
+    if not 0.0 < thr < 1.0:
+        raise ValueError(f"a threshold on the scores lies inside (0, 1), got {threshold!r}")
+    return float(np.float32(np.log(np.float64(thr) / (1.0 - np.float64(thr)))))
+
+
+@torch.no_grad()
+def predict(logits: torch.Tensor, target: Optional[torch.Tensor] = None, threshold: float = 0.5,
+            threshold_on: str = 'scores', top_k: int = 5, scores: bool = False) -> Dict:
+    """logits (N,C,...) fp32 on the device, read as they stand -> dict(cls, scores, counts) on the device
+    (cae_seg_predict, csrc/cae_seg_predict.hip; asynchronous on the current stream).
+    cls (N,...) uint8: ``logit > threshold_logit(...)`` for one class, else the index of the largest logit (the lowest
+    of equal ones).  scores (N,C,...) fp32 when asked for: sigmoid / softmax.  counts (N,6) int64
+    [tp, tn, fp, fn, p, tp_top] per image when a ``target`` (N,...) uint8 is given: one class -- the confusion table of
+    cls against target > 0; several -- tp = #{cls == target}, fp = fn = pixels - tp, tp_top = #{target among the
+    min(top_k, C) largest logits}."""
+    t = threshold_logit(threshold, threshold_on)  # ValueError before anything else
+    if int(top_k) != top_k or top_k < 1:
+        raise ValueError(f'top_k must be a positive integer, got {top_k!r}')
+    _lib.require_gpu()
+    if not isinstance(logits, torch.Tensor) or logits.dim() < 2 or logits.dtype != torch.float32 or not logits.is_cuda:
+        raise ValueError('expected fp32 logits (N,C,...) on the device')
+    if not 1 <= logits.size(1) <= 256:
+        raise ValueError(f'{logits.size(1)} classes outside 1..256')
+    logits = logits.contiguous()  # (a view of a larger buffer at any element offset is read in place)
+    n, c, space = logits.size(0), logits.size(1), tuple(logits.shape[2:])
+    hw = int(np.prod(space)) if space else 1
+    if n and hw < 1:
+        raise ValueError(f'empty planes: {tuple(logits.shape)}')
+    dev = logits.device
+    tgt = None
+    if target is not None:
+        if not isinstance(target, torch.Tensor) or target.dtype != torch.uint8 or target.numel() != n * hw:
+            raise ValueError(f'expected a uint8 target of {n} x {hw} labels')
+        tgt = target.to(dev).contiguous()
+    with torch.cuda.device(dev):
+        cls = torch.empty((n,) + space, dtype=torch.uint8, device=dev)
+        sc = torch.empty_like(logits) if scores else None
+        counts = ws = None
+        L = _lib.lib()
+        if tgt is not None:
+            counts = torch.empty((n, len(COUNT_KEYS)), dtype=torch.int64, device=dev)
+            ws = torch.empty(max(int(L.cae_seg_predict_workspace(n, c, hw)) // 8, 1), dtype=torch.int64, device=dev)
+        ptr = lambda v: None if v is None else v.data_ptr()
+        _lib.check(L.cae_seg_predict(logits.data_ptr(), ptr(tgt), n, c, max(hw, 1), t, int(top_k), cls.data_ptr(),
+                                     ptr(sc), ptr(counts), ptr(ws), 0 if ws is None else ws.numel() * 8,
+                                     _lib.stream_ptr()))
+    return dict(cls=cls, scores=sc, counts=counts)
+
+
+def class_metrics(counts, multiclass: bool = False) -> Dict:
+    """One counts record [tp, tn, fp, fn, p, tp_top] -- a tile's, or the sum of many tiles' -- (or an (M,6) array of
+    them, which is summed) -> the reference's metrics dictionary: tp tp_top tn fp fn p n acc top_acc prec rec f1, by the
+    formulas of compute_class_metrics_dask (_metrics.py:50-59; tn_top = tn).  A zero denominator gives 0.0 for prec /
+    rec / f1 (sklearn's zero_division=0 of the per-image variant) and NaN for acc / top_acc.  ``n`` = tn + fp, the
+    negatives of the confusion table; ``multiclass``: the reference's 0 for records of several classes (_metrics.py:105)."""
+    if isinstance(counts, torch.Tensor):
+        counts = counts.detach().cpu().numpy()
+    rec = np.asarray(counts, dtype=np.int64)
+    if rec.ndim == 2 and rec.shape[1] == len(COUNT_KEYS):
+        rec = rec.sum(axis=0)
+    if rec.shape != (len(COUNT_KEYS),):
+        raise ValueError(f'expected a counts record of {len(COUNT_KEYS)} integers, got shape {rec.shape}')
+    tp, tn, fp, fn, p, tp_top = (int(v) for v in rec)
+    total = tp + tn + fp + fn
+    ratio = lambda a, b: a / b if b > 0 else 0.0
+    return dict(tp=tp, tp_top=tp_top, tn=tn, fp=fp, fn=fn, p=p, n=0 if multiclass else tn + fp,
+                acc=(tp + tn) / total if total > 0 else float('nan'),
+                top_acc=(tp_top + tn) / total if total > 0 else float('nan'),
+                prec=ratio(tp, tp + fp), rec=ratio(tp, tp + fn), f1=ratio(2 * tp, 2 * tp + fp + fn))

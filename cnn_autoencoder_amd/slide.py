@@ -63,6 +63,32 @@ def gather_stats(local: torch.Tensor, counts: Sequence[int] = None) -> torch.Ten
     return torch.cat([b[:n] for b, n in zip(bufs, all_n)], dim=0)
 
 
+COUNTS_WIDTH = 6  # per tile: [tp, tn, fp, fn, p, tp_top] (segmenters.COUNT_KEYS)
+
+
+def gather_counts(local: torch.Tensor) -> torch.Tensor:
+    """gather_stats for the per-tile counts records of SlideCoder.segment_batches: (n_tiles, 6) int64 on this rank ->
+    (total_tiles, 6) on every rank, in rank order.  Ragged tile counts are padded to the largest for the collective and
+    trimmed afterwards."""
+    import torch.distributed as dist
+    local = torch.as_tensor(local)
+    if local.dim() != 2 or local.shape[1] != COUNTS_WIDTH or local.dtype != torch.int64:
+        raise ValueError(f'expected (n_tiles, {COUNTS_WIDTH}) int64 records, got {local.dtype} {tuple(local.shape)}')
+    if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size() == 1:
+        return local.clone()
+    world = dist.get_world_size()
+    dev = local.device
+    n_local = torch.tensor([local.shape[0]], dtype=torch.int64, device=dev)
+    all_n = [torch.zeros_like(n_local) for _ in range(world)]
+    dist.all_gather(all_n, n_local)
+    all_n = [int(t.item()) for t in all_n]
+    padded = torch.zeros((max(all_n), COUNTS_WIDTH), dtype=torch.int64, device=dev)
+    padded[:local.shape[0]] = local
+    bufs = [torch.empty_like(padded) for _ in range(world)]
+    dist.all_gather(bufs, padded)
+    return torch.cat([b[:n] for b, n in zip(bufs, all_n)], dim=0)
+
+
 def slide_summary(stats: torch.Tensor, pixels_per_tile: int) -> Dict[str, float]:
     """Slide-level rate / distortion from the gathered records."""
     s = stats.double().cpu()
@@ -225,6 +251,9 @@ class SlideCoder:
             # per-tile errors of run(): batch k is finalised with a lag of two batches, so k-2 and k-1 are still
             # pending when k takes its slot
             's': 3,
+            # class maps of segment_batches(to_host=True): as 'o' -- batch k stays valid until the generator has advanced
+            # two more times, one fetch is kept in flight
+            'c': 4,
         }[name]
         ring = self._rings.get(name)
         if ring is None or ring.slots != slots:
@@ -527,3 +556,127 @@ class SlideCoder:
             finalize(*pending.pop(0))
         self.timers = {key: sum(spans) for key, spans in tm.items()}
         return torch.cat(stats_parts), all_payloads
+
+    # ---- pipelined segmentation of compressed tiles ---------------------------------------------------------
+    def segment_batches(self, payload_batches, h: int, w: int, seg_model, targets=None, threshold: float = 0.5,
+                        threshold_on: str = 'scores', top_k: int = 5, scores: bool = False, keep_logits: bool = False,
+                        to_host: bool = False):
+        """Generator: for every list of chunk byte strings (the 16-byte '>QQ' tile size in front of the rANS payload, as
+        ZarrArray.read_chunk_bytes returns and segmenters.segment_compressed takes them; tiles of h x w pixels) the
+        prediction of the segmentation head ``seg_model`` (a JNet in eval mode), in order:
+        dict(cls (n,h,w) uint8, scores (n,C,h,w) fp32 | None, counts (n,6) int64 | None, logits (n,C,h,w) | None).
+        ``targets``: an iterable beside ``payload_batches`` of (n,h,w) uint8 label maps (host arrays or CUDA tensors);
+        with it the counts are made (segmenters.predict).  Results are CUDA tensors, or with ``to_host`` numpy arrays;
+        the class map then lies in a pinned ring buffer that stays valid until the generator has advanced two more times.
+
+        The stages of decompress_batches: a worker range-decodes up to `depth` batches ahead (host or device coder), the
+        symbols cross on the H2D side stream; then, on the main stream, dequantiser, synthesis track with its bridges
+        (Synthesizer.forward), head, cae_seg_predict; with ``to_host`` a second worker pulls each class map over the
+        DMA engines while the next batch runs.  A batch whose head call leaves the f16x3 range (FloatingPointError) is
+        repeated on the head's fp32 torch ops; ``self.timers`` holds the seconds per stage and 'head_fp32_repeats'.
+
+        ValueError before any work: seg_model in training mode, a head built for other latent channels than the
+        codec's, a bad threshold / threshold_on / top_k; and for every batch, before it is handed to the decoder: a chunk
+        whose header is not (h, w) -- chunks of mixed tile sizes."""
+        from .codec import _module
+        from . import segmenters
+        seg = _module(seg_model)
+        if seg.training:
+            raise ValueError('segment_batches needs the head in eval mode: call seg_model.eval()')
+        if seg._channels_bn != self.eb.channels:
+            raise ValueError(f'the head expects {seg._channels_bn} latent channels (channels_bn), the codec has '
+                             f'{self.eb.channels}')
+        segmenters.threshold_logit(threshold, threshold_on)
+        if int(top_k) != top_k or top_k < 1:
+            raise ValueError(f'top_k must be a positive integer, got {top_k!r}')
+        if h % 2 ** self.level or w % 2 ** self.level:
+            raise ValueError(f'tiles of {h} x {w} pixels are no multiple of 2^{self.level}')
+        return self._segment_batches(payload_batches, int(h), int(w), seg, targets,
+                                     dict(threshold=threshold, threshold_on=threshold_on, top_k=int(top_k), scores=scores),
+                                     keep_logits, to_host)
+
+    @torch.no_grad()
+    def _segment_batches(self, payload_batches, h, w, seg, targets, how, keep_logits, to_host):
+        import struct
+        from concurrent.futures import ThreadPoolExecutor
+        from . import _lib, segmenters
+        main = torch.cuda.current_stream(_dev())
+        up = self._h2d_stream()
+        depth = self.depth
+        lh, lw = h // 2 ** self.level, w // 2 ** self.level
+        head = struct.pack('>QQ', h, w)
+        tm = {key: [] for key in ('host_decode', 'synthesis', 'head', 'predict', 'copy')}
+        repeats = [0]
+        targets = iter(targets) if targets is not None else None
+
+        def strip(payloads):
+            payloads = [bytes(p) for p in payloads]
+            if any(p[:16] != head for p in payloads):
+                raise ValueError(f'segment_batches needs chunks of one tile size, {h} x {w}: a chunk header differs')
+            return [p[16:] for p in payloads]
+
+        def fetch(k, res, done):
+            done.synchronize()
+            t0 = time.perf_counter()
+            cls = res['cls']
+            out = self._ring('c').take(k, tuple(cls.shape), torch.uint8)
+            _lib.check(_lib.lib().cae_copy_to_host(out.data_ptr(), cls.data_ptr(), cls.numel()))
+            host = {key: None if v is None else v.cpu().numpy() for key, v in res.items() if key != 'cls'}
+            _clock(tm, 'copy', t0)
+            return dict(host, cls=out.numpy())
+
+        def launch(k, sym, target):
+            n = sym.size(0)
+            if self.coder != 'device':
+                with torch.cuda.stream(up):
+                    sym = sym.to(main.device, non_blocking=True)
+                    copied = torch.cuda.Event(blocking=True)
+                    copied.record(up)
+                self._ring('d').read_by(k, copied)
+                main.wait_event(copied)
+            sym.record_stream(main)
+            t0 = time.perf_counter()
+            y_q = self.eb.dequantize_symbols(sym.reshape(n, self.eb.channels, lh, lw))
+            _, fx_brg = self.dec(y_q)  # range-guarded: synchronises, repeats itself on the fp32 kernels
+            _clock(tm, 'synthesis', t0)
+            t0 = time.perf_counter()
+            try:
+                logits = seg(y_q, fx_brg=fx_brg)[0]
+            except FloatingPointError:  # f16x3 range of the head: its fp32 torch ops
+                repeats[0] += 1
+                logits = seg._forward_torch(y_q, list(fx_brg) if seg._concat_bridges else [])
+            _clock(tm, 'head', t0)
+            t0 = time.perf_counter()
+            if target is not None and not (isinstance(target, torch.Tensor) and target.is_cuda):
+                target = torch.as_tensor(np.ascontiguousarray(target)).to(main.device)
+            res = segmenters.predict(logits, target, **how)
+            res['logits'] = logits if keep_logits else None
+            done = torch.cuda.Event(blocking=True)
+            done.record(main)
+            _clock(tm, 'predict', t0)
+            return res, done
+
+        workers = depth if self.coder == 'device' else 1
+        try:
+            with ThreadPoolExecutor(max_workers=workers) as pool, ThreadPoolExecutor(max_workers=1) as out_pool:
+                inflight, outgoing = [], []
+
+                def emit(j, fut, target):
+                    res, done = launch(j, fut.result(), target)
+                    if not to_host:
+                        return [res]
+                    outgoing.append(out_pool.submit(fetch, j, res, done))
+                    # one class map stays in flight: its D2H overlaps the next batch's kernels
+                    return [outgoing.pop(0).result()] if len(outgoing) > 1 else []
+
+                for k, payloads in enumerate(payload_batches):
+                    target = next(targets) if targets is not None else None
+                    inflight.append((k, pool.submit(self._decode, k, strip(payloads), lh * lw, tm), target))
+                    if len(inflight) > depth:
+                        yield from emit(*inflight.pop(0))
+                while inflight:
+                    yield from emit(*inflight.pop(0))
+                while outgoing:
+                    yield outgoing.pop(0).result()
+        finally:
+            self.timers = dict({key: sum(spans) for key, spans in tm.items()}, head_fp32_repeats=repeats[0])

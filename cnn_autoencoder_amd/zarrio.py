@@ -500,3 +500,111 @@ def decompress_image(input_filename: str, data_group: str = '0/0', checkpoint=No
     f = 2 ** scale
     oy, ox = ty0 * ly * up, tx0 * lx * up
     return np.ascontiguousarray(out[y0 // f - oy:max(y0 // f, -(-y1 // f)) - oy, x0 // f - ox:max(x0 // f, -(-x1 // f)) - ox])
+
+
+def segment_image(input_filename: str, seg_model, output_filename: str, data_group: str = '0/0', checkpoint=None,
+                  target_group: Optional[str] = None, batch_tiles: int = 4, threshold: float = 0.5,
+                  threshold_on: str = 'scores', top_k: int = 5, scores: bool = False, coder: str = 'host') -> Dict:
+    """The reference's segmentation harness on a compressed slide (test_cae_classifier.py:46-55 and its metrics), without
+    decoding a pixel to the host: the chunk bytes of the 'cae'-coded array ``data_group`` of ``input_filename`` go through
+    SlideCoder.segment_batches (range decoder on ``coder``, synthesis track, the head ``seg_model``, cae_seg_predict)
+    and the class map is written to ``output_filename``:
+
+        class/0/0    (H, W), '|b1' for one class ('|u1' otherwise), chunks (patch, patch), Zlib(9)
+        scores/0/0   (C, H, W) float32, chunks (C, patch, patch), Zlib(9)            -- with ``scores``
+
+    ``checkpoint``: the codec's checkpoint, instead of the path stored in the array's metadata.  With
+    ``torch.distributed`` initialised every rank segments the tile block ``slide.tile_range(rank, world, n_tiles)`` and
+    rank 0 writes the metadata, as compress_image does.
+    ``target_group``: a (H, W) (or (H, W, 1)) uint8 label array of the input store, read tile by tile.  The counts are
+    made per chunk and cover the image's pixels only: the padding of an edge chunk is labelled so that the device
+    counts can be corrected exactly on the host (several classes: label 255, wrong in tp and tp_top, then fp = fn =
+    pixels - tp and p = pixels of the real part -- so a ragged image with a target needs at most 255 classes; one class:
+    label 0, and the padding's share of tn and fp is taken off from the class map).
+    -> segmenters.class_metrics of the slide's summed record, plus
+    'records': the (tiles, 6) int64 per-tile records of all ranks in tile order (slide.gather_counts), 'tiles' and
+    'head_fp32_repeats' (this rank's); without a target only the last two."""
+    import struct
+    import torch
+    from . import segmenters, slide
+    from .codec import ConvolutionalAutoencoder, _module
+    from .entropy import check_coder
+    check_coder(coder)
+    codec = None
+    if checkpoint is not None and not (isinstance(checkpoint, str) and not len(checkpoint)):
+        codec = ConvolutionalAutoencoder(checkpoint=checkpoint)
+    z = ZarrArray.open(input_filename, data_group, codec=codec)
+    if not isinstance(z.codec, ConvolutionalAutoencoder) or len(z.shape) != 3:
+        raise ValueError("segment_image needs a (H, W, C) array whose codec is 'cae'")
+    seg = _module(seg_model)
+    H, W = z.shape[0], z.shape[1]
+    ph, pw = z.chunks[0], z.chunks[1]
+    C = seg._num_classes
+    rank, world = _rank_world()
+    tz = None
+    if target_group is not None:
+        tz = ZarrArray.open(input_filename, target_group)
+        if tuple(tz.shape[:2]) != (H, W) or tz.dtype != np.uint8 or int(np.prod(tz.shape[2:])) != 1:
+            raise ValueError(f'the target must be a ({H}, {W}) uint8 array, got {tz.dtype} {tz.shape}')
+    if tz is not None and C > 255 and (H % ph or W % pw):
+        raise ValueError('a target on an image that is no multiple of its chunks needs at most 255 classes (label 255 '
+                         'marks the padding of the edge chunks)')
+    sc = slide.SlideCoder(z.codec, coder=coder)
+    zc = ZarrArray.create(output_filename, 'class/0/0', (H, W), (ph, pw), np.bool_ if C == 1 else np.uint8,
+                          codec=Zlib(9), write_meta=rank == 0)
+    zs = ZarrArray.create(output_filename, 'scores/0/0', (C, H, W), (C, ph, pw), np.float32, codec=Zlib(9),
+                          write_meta=rank == 0) if scores else None
+    tiles = z.chunk_indices()
+    lo, hi = slide.tile_range(rank, world, len(tiles))
+    groups = list(_batches(tiles[lo:hi], batch_tiles))
+
+    def chunks(group):
+        bufs = [z.read_chunk_bytes(i) for i in group]
+        if any(b is None for b in bufs):
+            raise ValueError('missing chunk file')
+        return bufs
+
+    def labels(group):
+        out = np.full((len(group), ph, pw), 255 if C > 1 else 0, dtype=np.uint8)
+        for t, (i, j, _) in enumerate(group):
+            part = tz[i * ph:min((i + 1) * ph, H), j * pw:min((j + 1) * pw, W)]
+            part = part.reshape(part.shape[0], part.shape[1])
+            out[t, :part.shape[0], :part.shape[1]] = part
+        return out
+
+    stream = sc.segment_batches((chunks(g) for g in groups), ph, pw, seg,
+                                targets=None if tz is None else (labels(g) for g in groups), threshold=threshold,
+                                threshold_on=threshold_on, top_k=top_k, scores=scores, to_host=True)
+    records = []
+    for group, res in zip(groups, stream):  # res['cls']: pinned ring buffer, written out before the generator advances
+        for t, (i, j, _) in enumerate(group):
+            ch, cw = min(ph, H - i * ph), min(pw, W - j * pw)
+            zc.write_chunk((i, j), res['cls'][t, :ch, :cw].astype(zc.dtype))
+            if zs is not None:
+                zs.write_chunk((0, i, j), res['scores'][t, :, :ch, :cw])
+        if res['counts'] is not None:
+            rec = np.array(res['counts'], dtype=np.int64)
+            for t, (i, j, _) in enumerate(group):
+                ch, cw = min(ph, H - i * ph), min(pw, W - j * pw)
+                if ch * cw == ph * pw:
+                    continue
+                if C > 1:  # the padding (label 255) is in neither tp nor tp_top
+                    rec[t, 1:5] = (0, ch * cw - rec[t, 0], ch * cw - rec[t, 0], ch * cw)
+                else:  # the padding (label 0) is tn where the class map is off and fp where it is on
+                    pad_on = int(np.count_nonzero(res['cls'][t])) - int(np.count_nonzero(res['cls'][t, :ch, :cw]))
+                    rec[t, 1] -= ph * pw - ch * cw - pad_on
+                    rec[t, 2] -= pad_on
+            records.append(torch.from_numpy(rec))
+    out = dict(tiles=hi - lo, head_fp32_repeats=sc.timers.get('head_fp32_repeats', 0))
+    if tz is not None:
+        local = torch.cat(records) if records else torch.zeros((0, slide.COUNTS_WIDTH), dtype=torch.int64)
+        try:
+            import torch.distributed as dist
+            if dist.is_available() and dist.is_initialized() and dist.get_backend() == 'nccl':
+                local = local.cuda()
+        except ImportError:
+            pass
+        allrec = slide.gather_counts(local).cpu().numpy()
+        out.update(segmenters.class_metrics(allrec.sum(axis=0), multiclass=C > 1), records=allrec)
+    _barrier()
+    return out

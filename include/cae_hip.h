@@ -644,6 +644,35 @@ size_t cae_seg_packed_halves(int cin_a, int cin_b, int cout, int ks, int up);
 int cae_seg_pack(const float *w, int cin_a, int cin_b, int cout, int ks, int up, uint16_t *out, size_t capacity);
 void cae_seg_tile(int *tx, int *ty); /* output tile of the head's convolution kernel, in pixels */
 
+/* ---- Prediction from the head's logits (csrc/cae_seg_predict.hip) ------------------------------
+ * What the reference's segmentation harness makes of a model's output (test_cae_classifier.py:46-55 save_pred2zarr,
+ * utils/_metrics.py:79-193), in one pass over the logits: class map, optional scores, optional per-image counts.
+ * logits_dev (n, c, hw) fp32, the head's NCHW output as it stands (any 4-byte aligned address); target_dev (n, hw)
+ * uint8 or NULL; cls_dev (n, hw) uint8; scores_dev (n, c, hw) fp32 or NULL; counts_dev (n, 6) int64 =
+ * [tp, tn, fp, fn, p, tp_top] or NULL (needs target_dev).
+ *
+ * c == 1: cls = logit > t, an exact fp32 compare (false for NaN).  The caller chooses t: the logit of a score
+ * threshold, t = (float)log(thr / (1 - thr)) evaluated in double (compute_metrics_per_image compares the sigmoid,
+ * _metrics.py:172), or a threshold on the logit itself (save_pred2zarr, test_cae_classifier.py:54).  scores =
+ * 1 / (1 + exp(-x)).  The target is binarised as target > 0; counts are the confusion table, p = tp + fn, tp_top = tp.
+ * 2 <= c <= 256: cls = index of the largest logit, the lowest index of equal ones (always inside 0..c-1, NaN or not);
+ * scores = softmax with the pixel's maximum subtracted; tp = #{cls == target}, fp = fn = hw - tp, tn = 0, p = hw
+ * (compute_class_metrics, _metrics.py:94-105); tp_top = #{rank < min(top_k, c)} with rank = #{j : l_j > l_t} +
+ * #{j < t : l_j == l_t} of the target's logit l_t.  A target value >= c counts as wrong in tp and tp_top and is never
+ * used as an index.
+ *
+ * Up to 16 classes every logit is read once; above, the planes of a pixel are read three times (the repeats out of the
+ * cache).  Counts are exact and bitwise repeatable: integer partials per (image, block) in workspace_dev
+ * (cae_seg_predict_workspace bytes, 8-byte aligned; only needed with counts_dev), merged by a second launch in fixed
+ * order; no atomics.  Neither outputs nor workspace need initialising.  Launches are asynchronous on `stream`.
+ * CAE_ERR_ARG before any launch: c outside 1..256, n < 0, hw < 1, top_k < 1, counts without a target, and for n >= 1
+ * a NULL logits_dev / cls_dev or, with counts, a workspace that is NULL, misaligned or too small.  n == 0: CAE_OK,
+ * nothing launched.  cae_seg_predict_workspace returns 0 for shapes cae_seg_predict refuses and for n == 0. */
+int cae_seg_predict(const float *logits_dev, const uint8_t *target_dev, int n, int c, size_t hw, float t, int top_k,
+                    uint8_t *cls_dev, float *scores_dev, int64_t *counts_dev, void *workspace_dev,
+                    size_t workspace_bytes, void *stream);
+size_t cae_seg_predict_workspace(int n, int c, size_t hw);
+
 #ifdef __cplusplus
 }
 #endif
