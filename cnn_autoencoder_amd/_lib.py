@@ -161,6 +161,10 @@ SYMBOLS = {
     'cae_seg_predict': (c_int, [c_void_p, c_void_p, c_int, c_int, c_size_t, c_float, c_int, c_void_p, c_void_p, c_void_p,
                                 c_void_p, c_size_t, c_void_p]),
     'cae_seg_predict_workspace': (c_size_t, [c_int, c_int, c_size_t]),
+    'cae_seg_roc_hist': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
+                                 c_size_t, c_void_p]),
+    'cae_seg_roc_workspace': (c_size_t, [c_int, c_int, c_int, c_int]),
+    'cae_seg_roc_blocks': (c_int, [c_int, c_int, c_int, c_int]),
 }
 
 CAE_ANALYSIS, CAE_SYNTHESIS = 0, 1

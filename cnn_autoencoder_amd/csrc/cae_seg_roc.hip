@@ -1,0 +1,203 @@
+// cae_seg_roc_hist: the logit histograms behind a slide's ROC curve and AUC, and their launcher (include/cae_hip.h,
+// "ROC histograms of a one-class head").
+//
+// First launch: a block takes a contiguous span of one image's counted pixels, keeps a private uint32 [2][2^bits]
+// histogram in dynamic LDS (128 KiB at 14 bits: one block per CU), counts with LDS integer adds and stores the whole
+// table as one partial [image][block][2][2^bits] in the workspace, work or not.  Loads as seg_predict_kernel: 16-byte
+// logit loads and 4-byte target loads behind the image's first aligned address, the pixels in front of it and behind the
+// last whole group one per lane (block 0 of the image).  Lanes of a wave that hit the first active lane's word add
+// once, by their number: a slide's background puts most of a wave on one or two words, and 64 adds to one LDS word
+// take 64 turns.  Second launch: the partials of an image, or of all images, summed into int64 in a fixed order.
+// No global atomics, no float atomics, nothing to initialise.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdint>
+
+#include "cae_launch.hpp"
+
+namespace cae {
+namespace {
+
+constexpr int kThreads = 1024;      // 16 waves: the one block a CU holds at 14 bits keeps its four SIMDs loading
+constexpr int kSumThreads = 512;    // roc_sum_kernel: 64 lanes x 4 entries, 8 waves that share the partials out
+constexpr size_t kSpanMin = 8192;   // pixels below which a block of its own only adds a partial
+constexpr int kMinBits = 8, kMaxBits = 14;
+
+// blocks of a launch at which more would only add partials: a partial is 2^(bits+3) bytes written and read again, as
+// much as 2^(bits+3) / 5 pixels of input; above 12 bits one block per CU of the 256 is all that runs at a time
+int blocks_target(int bits) { return bits > 12 ? 256 : 1024; }
+
+struct RocArgs {
+    const float *logits;
+    const uint8_t *target;
+    const int32_t *extent;  // [n][2] or null
+    uint32_t *partial;      // [n][bx][2][B]
+    int h, w, bits, bx;
+};
+
+// order-preserving key of an fp32 logit, cut to its top `bits` bits.  -0 counts as +0 and NaN as key 0; in integers, so
+// that no floating-point mode (denormals) has a say: x + 0.0f changes no other value
+__device__ __forceinline__ uint32_t roc_bin(float x, int shift) {
+    uint32_t u = __float_as_uint(x);
+    if (u == 0x80000000u) u = 0;
+    const uint32_t key = (u >> 31) ? ~u : (u | 0x80000000u);
+    return (u & 0x7fffffffu) > 0x7f800000u ? 0u : key >> shift;
+}
+
+// one pixel per lane into the block's histogram; `word` = positive * B + bin
+__device__ __forceinline__ void roc_add(uint32_t *hist, bool on, uint32_t word) {
+    if (on) {
+        const uint32_t lead = __builtin_amdgcn_readfirstlane(word);
+        const unsigned long long same = __ballot(word == lead);  // the lanes of this branch only; the first is among them
+        if (word != lead)
+            atomicAdd(&hist[word], 1u);
+        else if ((int)(threadIdx.x & 63) == __ffsll((long long)same) - 1)
+            atomicAdd(&hist[lead], (uint32_t)__popcll(same));
+    }
+}
+
+__global__ __launch_bounds__(kThreads) void roc_hist_kernel(RocArgs a) {
+    extern __shared__ uint32_t hist[];  // [2][B]
+    const int n = blockIdx.x / a.bx, x = blockIdx.x % a.bx, tid = threadIdx.x;
+    const uint32_t B = 1u << a.bits;
+    const int shift = 32 - a.bits;
+    for (uint32_t i = tid; i < 2 * B; i += kThreads) hist[i] = 0;
+    __syncthreads();
+
+    const size_t w = (size_t)a.w, hw = (size_t)a.h * w;
+    int rows = a.h, cols = a.w;
+    if (a.extent) {
+        rows = std::min(std::max(a.extent[2 * n], 0), a.h);
+        cols = std::min(std::max(a.extent[2 * n + 1], 0), a.w);
+    }
+    const size_t lim = cols > 0 ? (size_t)rows * w : 0;  // whole rows beyond `rows` are never loaded
+    const bool ragged = cols < a.w;                      // columns beyond `cols` are loaded and left out
+    const float *lg = a.logits + (size_t)n * hw;
+    const uint8_t *tg = a.target + (size_t)n * hw;
+
+    // pixels [head, tail) in groups of four behind 16-byte aligned addresses; the (at most six) others one per lane
+    const size_t head = std::min<size_t>(lim, (size_t)((0 - (reinterpret_cast<uintptr_t>(lg) >> 2)) & 3));
+    const size_t groups = (lim - head) / 4;
+    const size_t per_block = (groups + a.bx - 1) / a.bx;
+    const size_t g0 = std::min(groups, (size_t)x * per_block), g1 = std::min(groups, g0 + per_block);
+    const bool tg_vec = (reinterpret_cast<uintptr_t>(tg + head) & 3) == 0;
+    constexpr size_t step = 4 * (size_t)kThreads;
+    const size_t dcol = step % w;
+    size_t col = ragged && g0 + tid < g1 ? (head + 4 * (g0 + tid)) % w : 0;  // column of the group's first pixel
+    for (size_t g = g0 + tid; g < g1; g += kThreads) {
+        const size_t p = head + 4 * g;  // p + 3 < head + 4 groups <= lim <= hw
+        const float4 q = *reinterpret_cast<const float4 *>(lg + p);
+        uint32_t t4;
+        if (tg_vec)
+            t4 = *reinterpret_cast<const uint32_t *>(tg + p);
+        else
+            t4 = (uint32_t)tg[p] | (uint32_t)tg[p + 1] << 8 | (uint32_t)tg[p + 2] << 16 | (uint32_t)tg[p + 3] << 24;
+        const float v[4] = {q.x, q.y, q.z, q.w};
+        size_t c = col;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const bool on = !ragged || c < (size_t)cols;
+            roc_add(hist, on, (((t4 >> (8 * j)) & 255u) ? B : 0u) + roc_bin(v[j], shift));
+            if (++c == w) c = 0;
+        }
+        col += dcol;
+        if (col >= w) col -= w;
+    }
+    const size_t tail = head + 4 * groups, singles = head + (lim - tail);
+    if (x == 0 && (size_t)tid < singles) {
+        const size_t p = (size_t)tid < head ? (size_t)tid : tail + ((size_t)tid - head);  // < lim
+        const bool on = !ragged || p % w < (size_t)cols;
+        roc_add(hist, on, (tg[p] ? B : 0u) + roc_bin(lg[p], shift));
+    }
+    __syncthreads();
+
+    // every (image, block) stores its whole table; 16 bytes per lane (2 B >= 512 words, the partials 16-byte aligned)
+    uint4 *dst = reinterpret_cast<uint4 *>(a.partial + (size_t)blockIdx.x * 2 * B);
+    const uint4 *src = reinterpret_cast<const uint4 *>(hist);
+    for (uint32_t i = tid; i < B / 2; i += kThreads) dst[i] = src[i];
+}
+
+// hist[m][e] = the sum over the `sources` partials of output m of word e, e in 0 .. 2B: a block owns 256 words (four per
+// lane), its waves take the partials in turn, and the eight wave sums are added in wave order
+__global__ __launch_bounds__(kSumThreads) void roc_sum_kernel(const uint32_t *partial, int sources, uint32_t words,
+                                                              long long *out) {
+    constexpr int kWaves = kSumThreads / 64;
+    const uint32_t per_m = words / 256, m = blockIdx.x / per_m, first = (blockIdx.x % per_m) * 256u;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint32_t e = first + 4u * lane;  // < words: words is a multiple of 256
+    const uint32_t *src = partial + (size_t)m * sources * words + e;
+    unsigned long long s[4] = {0, 0, 0, 0};
+#pragma unroll 4
+    for (int b = wave; b < sources; b += kWaves) {
+        const uint4 v = *reinterpret_cast<const uint4 *>(src + (size_t)b * words);
+        s[0] += v.x, s[1] += v.y, s[2] += v.z, s[3] += v.w;
+    }
+    __shared__ unsigned long long wave_sum[kWaves][256];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) wave_sum[wave][4 * lane + j] = s[j];
+    __syncthreads();
+    if (threadIdx.x < 256) {
+        unsigned long long t = 0;
+#pragma unroll
+        for (int k = 0; k < kWaves; ++k) t += wave_sum[k][threadIdx.x];
+        out[(size_t)m * words + first + threadIdx.x] = (long long)t;
+    }
+}
+
+bool shape_ok(int n, int h, int w, int bits) { return n >= 1 && h >= 1 && w >= 1 && bits >= kMinBits && bits <= kMaxBits; }
+
+// blocks per image: one per kSpanMin pixels, fewer once the launch has blocks_target blocks
+int blocks_per_image(int n, int h, int w, int bits) {
+    const size_t hw = (size_t)h * (size_t)w;
+    const size_t spans = (hw + kSpanMin - 1) / kSpanMin;
+    const size_t cap = std::max<size_t>(1, (size_t)blocks_target(bits) / (size_t)n);
+    return (int)std::min(spans, cap);
+}
+
+}  // namespace
+}  // namespace cae
+
+using namespace cae;
+
+extern "C" int cae_seg_roc_blocks(int n, int h, int w, int bits) {
+    return shape_ok(n, h, w, bits) ? blocks_per_image(n, h, w, bits) : 0;
+}
+
+extern "C" size_t cae_seg_roc_workspace(int n, int h, int w, int bits) {
+    if (!shape_ok(n, h, w, bits)) return 0;
+    return (size_t)n * blocks_per_image(n, h, w, bits) * (sizeof(uint32_t) << (bits + 1));
+}
+
+extern "C" int cae_seg_roc_hist(const float *logits, const uint8_t *target, const int32_t *extent, int n, int h, int w,
+                                int bits, int per_image, int64_t *hist, void *workspace, size_t workspace_bytes,
+                                void *stream) {
+    if (bits < kMinBits || bits > kMaxBits)
+        return fail(CAE_ERR_ARG, "cae_seg_roc_hist: %d bits outside %d..%d", bits, kMinBits, kMaxBits);
+    if (n < 0 || h < 1 || w < 1) return fail(CAE_ERR_ARG, "cae_seg_roc_hist: bad shape n=%d h=%d w=%d", n, h, w);
+    if (n == 0) return CAE_OK;
+    if (!logits || !target || !hist) return fail(CAE_ERR_ARG, "cae_seg_roc_hist: NULL logits, target or histogram");
+    if (reinterpret_cast<uintptr_t>(logits) & 3) return fail(CAE_ERR_ARG, "cae_seg_roc_hist: logits not 4-byte aligned");
+    const size_t need = cae_seg_roc_workspace(n, h, w, bits);
+    if (!workspace || workspace_bytes < need)
+        return fail(CAE_ERR_ARG, "cae_seg_roc_hist: workspace too small: %zu bytes needed", need);
+    if ((reinterpret_cast<uintptr_t>(workspace) & 15) || (reinterpret_cast<uintptr_t>(hist) & 7))
+        return fail(CAE_ERR_ARG, "cae_seg_roc_hist: workspace not 16-byte or histogram not 8-byte aligned");
+    RocArgs a;
+    a.logits = logits, a.target = target, a.extent = extent, a.partial = static_cast<uint32_t *>(workspace);
+    a.h = h, a.w = w, a.bits = bits, a.bx = blocks_per_image(n, h, w, bits);
+    // a block's words are 32 bits wide: its span stays below 2^32 pixels
+    if (((size_t)h * (size_t)w + a.bx - 1) / a.bx >> 32)
+        return fail(CAE_ERR_ARG, "cae_seg_roc_hist: %d images of %d x %d pixels are too many for one call", n, h, w);
+    const int lds = (int)(sizeof(uint32_t) << (bits + 1));
+    CAE_TRY(ensure_lds(reinterpret_cast<const void *>(roc_hist_kernel), lds));
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(roc_hist_kernel, dim3((unsigned)((size_t)n * a.bx)), dim3(kThreads), lds, st, a);
+    HIP_TRY(hipGetLastError());
+    const uint32_t words = 2u << bits;
+    const int m = per_image ? n : 1, sources = per_image ? a.bx : n * a.bx;
+    hipLaunchKernelGGL(roc_sum_kernel, dim3((unsigned)((size_t)m * (words / 256))), dim3(kSumThreads), 0, st, a.partial, sources, words,
+                       reinterpret_cast<long long *>(hist));
+    HIP_TRY(hipGetLastError());
+    return CAE_OK;
+}

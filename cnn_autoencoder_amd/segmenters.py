@@ -11,7 +11,8 @@ a second opinion in the tests).  Not built, and raising ``NotImplementedError``:
 
 ``predict`` / ``class_metrics`` turn logits into what the reference's harness hands out (class map, scores, counts and
 metrics; ``cae_seg_predict``, csrc/cae_seg_predict.hip); ``slide.SlideCoder.segment_batches`` and ``zarrio.segment_image``
-run whole slides through codec, head and prediction.
+run whole slides through codec, head and prediction.  ``roc_histogram`` / ``roc_from_histogram`` give the threshold-free
+results of a one-class head, ROC curve and AUC, from exact logit histograms (``cae_seg_roc_hist``, csrc/cae_seg_roc.hip).
 
 Unlike the reference (whose in-place ReLU overwrites the caller's bridges when ``batch_norm=False``) the head never
 writes its inputs.
@@ -452,3 +453,114 @@ def class_metrics(counts, multiclass: bool = False) -> Dict:
                 acc=(tp + tn) / total if total > 0 else float('nan'),
                 top_acc=(tp_top + tn) / total if total > 0 else float('nan'),
                 prec=ratio(tp, tp + fp), rec=ratio(tp, tp + fn), f1=ratio(2 * tp, 2 * tp + fp + fn))
+
+
+# ---- threshold-free results of a one-class head: ROC curve and AUC from logit histograms (csrc/cae_seg_roc.hip) -------
+ROC_BITS = 14          # bins of the slide histograms: 2^14 per class, the most cae_seg_roc_hist takes
+ROC_BITS_RANGE = (8, 14)
+
+
+def _check_roc_bits(bits) -> int:
+    if isinstance(bits, bool) or int(bits) != bits or not ROC_BITS_RANGE[0] <= int(bits) <= ROC_BITS_RANGE[1]:
+        raise ValueError(f'roc bits must be an integer in {ROC_BITS_RANGE[0]}..{ROC_BITS_RANGE[1]}, got {bits!r}')
+    return int(bits)
+
+
+def roc_bin_edges(bits: int = ROC_BITS) -> np.ndarray:
+    """float32 (2^bits,): e_j, the smallest non-NaN fp32 value of bin j of cae_seg_roc_hist (include/cae_hip.h), NaN where
+    a bin holds NaN bit patterns only.  ``bin(x) >= j`` exactly when ``x >= e_j``, i.e. ``x > nextafter(e_j, -inf)``."""
+    bits = _check_roc_bits(bits)
+    shift = 32 - bits
+    low = np.arange(1 << bits, dtype=np.uint64) << np.uint64(shift)  # the lowest key of every bin
+    neg = low < (1 << 31)
+    # negative floats: key = ~u, keys below that of -inf (0x007fffff) are NaN patterns; the rest: key = u | 2^31
+    key = np.where(neg, np.maximum(low, 0x007FFFFF), low)
+    u = np.where(neg, ~key & np.uint64(0xFFFFFFFF), key & np.uint64(0x7FFFFFFF))
+    valid = np.where(neg, key < low + (1 << shift), u <= 0x7F800000)
+    edges = u.astype(np.uint32).view(np.float32).copy()
+    edges[~valid] = np.nan
+    return edges
+
+
+@torch.no_grad()
+def roc_histogram(logits: torch.Tensor, target: torch.Tensor, extent=None, bits: int = ROC_BITS,
+                  per_image: bool = False) -> torch.Tensor:
+    """fp32 logits (N,1,H,W) of a one-class head on the device, read as they stand, and a uint8 target (N,H,W) ->
+    int64 CUDA tensor (2, 2^bits) -- row 0 the negatives' (target == 0), row 1 the positives' counts per logit bin, summed
+    over the batch -- or (N, 2, 2^bits) with ``per_image`` (cae_seg_roc_hist; asynchronous on the current stream).
+    ``extent``: (N,2) integers (rows, cols): only the pixels y < rows, x < cols of each image are counted (values are
+    clamped to the plane).  Histograms are exact and add; ``roc_from_histogram`` makes curve and AUC of them."""
+    bits = _check_roc_bits(bits)
+    _lib.require_gpu()
+    if not isinstance(logits, torch.Tensor) or logits.dim() != 4 or logits.dtype != torch.float32 or not logits.is_cuda:
+        raise ValueError('expected fp32 logits (N,1,H,W) on the device')
+    if logits.size(1) != 1:
+        raise ValueError(f'the ROC histogram is built for a one-class head, got {logits.size(1)} classes')
+    n, _, h, w = logits.shape
+    if n and (h < 1 or w < 1):
+        raise ValueError(f'empty planes: {tuple(logits.shape)}')
+    if not isinstance(target, torch.Tensor) or target.dtype != torch.uint8 or target.numel() != n * h * w:
+        raise ValueError(f'expected a uint8 target of {n} x {h} x {w} labels')
+    logits = logits.contiguous()  # (a view of a larger buffer at any element offset is read in place)
+    dev = logits.device
+    tgt = target.to(dev).contiguous()
+    ext = None
+    if extent is not None:
+        ext = extent if isinstance(extent, torch.Tensor) else torch.as_tensor(np.asarray(extent))
+        if ext.is_floating_point() or ext.dtype == torch.bool or tuple(ext.shape) != (n, 2):
+            raise ValueError(f'expected an extent of {n} x 2 integers (rows, cols), got {ext.dtype} {tuple(ext.shape)}')
+        i32 = torch.iinfo(torch.int32)
+        ext = ext.clamp(i32.min, i32.max).to(device=dev, dtype=torch.int32).contiguous()
+    m = n if per_image else 1
+    with torch.cuda.device(dev):
+        if n == 0:
+            return torch.zeros((m, 2, 1 << bits) if per_image else (2, 1 << bits), dtype=torch.int64, device=dev)
+        L = _lib.lib()
+        hist = torch.empty((m, 2, 1 << bits), dtype=torch.int64, device=dev)
+        ws = torch.empty(int(L.cae_seg_roc_workspace(n, h, w, bits)) // 8, dtype=torch.int64, device=dev)
+        _lib.check(L.cae_seg_roc_hist(logits.data_ptr(), tgt.data_ptr(), None if ext is None else ext.data_ptr(), n, h, w,
+                                      bits, int(bool(per_image)), hist.data_ptr(), ws.data_ptr(), ws.numel() * 8,
+                                      _lib.stream_ptr()))
+    return hist if per_image else hist[0]
+
+
+def roc_from_histogram(hist) -> Dict:
+    """One histogram (2, B) of roc_histogram -- a tile's, or the sum of many tiles' -- or an (M, 2, B) array of them,
+    which is summed -> dict(fpr, tpr, thresholds, score_thresholds, auc, auc_slack, p, n); pure numpy on the host.
+    The curve starts at (0, 0) with threshold +inf and has one point per non-empty bin from the top down, at the bin's
+    edge e_j (``thresholds``, logits; ``score_thresholds``: their sigmoid in float64): fpr / tpr are the fp / (fp + tn)
+    and tp / (tp + fn) of ``predict(..., threshold=nextafter(e_j, -inf), threshold_on='logits')``, and the arrays are
+    sklearn's ``roc_curve(target, logits, drop_intermediate=False)`` for logits that sit on bin edges.
+    ``auc``: the trapezoid area under that curve, sum_b pos_b (2 neg_below_b + neg_b) / (2 P N) in Python integers with one
+    division; the AUC of the unbinned logits lies inside auc +- ``auc_slack`` = sum_b pos_b neg_b / (2 P N).  Both are NaN
+    without positives (the reference's rule, _metrics.py:128-131) or without negatives; fpr / tpr are then NaN too."""
+    if isinstance(hist, torch.Tensor):
+        hist = hist.detach().cpu().numpy()
+    hist = np.asarray(hist)
+    if hist.dtype.kind not in 'iu' or hist.ndim not in (2, 3) or hist.shape[-2] != 2:
+        raise ValueError(f'expected integer histograms (2, B) or (M, 2, B), got {hist.dtype} {hist.shape}')
+    hist = hist.astype(np.int64)
+    if hist.ndim == 3:
+        hist = hist.sum(axis=0)
+    B = hist.shape[1]
+    bits = B.bit_length() - 1
+    if B != 1 << bits or not ROC_BITS_RANGE[0] <= bits <= ROC_BITS_RANGE[1] or (hist < 0).any():
+        raise ValueError(f'expected non-negative counts in 2^{ROC_BITS_RANGE[0]}..2^{ROC_BITS_RANGE[1]} bins, got {B}')
+    neg, pos = hist[0], hist[1]
+    N, P = int(neg.sum()), int(pos.sum())
+    full = np.flatnonzero(neg + pos)[::-1]  # the non-empty bins from the top down
+    with np.errstate(invalid='ignore', divide='ignore', over='ignore'):
+        fpr = np.concatenate(([0.0], np.cumsum(neg[full]) / np.float64(N))) if N else np.full(full.size + 1, np.nan)
+        tpr = np.concatenate(([0.0], np.cumsum(pos[full]) / np.float64(P))) if P else np.full(full.size + 1, np.nan)
+        thr = np.concatenate(([np.inf], roc_bin_edges(bits)[full].astype(np.float64)))
+        score_thr = np.concatenate(([np.inf], 1.0 / (1.0 + np.exp(-thr[1:]))))
+    auc = slack = float('nan')
+    if P and N:
+        area = ties = 0
+        neg_below = np.concatenate(([0], np.cumsum(neg)[:-1]))
+        for b in np.flatnonzero(pos):  # Python integers: a slide's pos_b neg_b does not fit 64 bits
+            pb, nb = int(pos[b]), int(neg[b])
+            area += pb * (2 * int(neg_below[b]) + nb)
+            ties += pb * nb
+        auc, slack = area / (2 * P * N), ties / (2 * P * N)
+    return dict(fpr=fpr, tpr=tpr, thresholds=thr, score_thresholds=score_thr, auc=auc, auc_slack=slack, p=P, n=N)

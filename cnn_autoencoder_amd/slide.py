@@ -89,6 +89,21 @@ def gather_counts(local: torch.Tensor) -> torch.Tensor:
     return torch.cat([b[:n] for b, n in zip(bufs, all_n)], dim=0)
 
 
+def reduce_histogram(local: torch.Tensor) -> torch.Tensor:
+    """The slide's ROC histogram from this rank's (segmenters.roc_histogram, summed over the rank's batches): the int64
+    sum over the ranks of the default process group when torch.distributed is initialised, `local` itself otherwise.
+    Integers: exact in any order."""
+    import torch.distributed as dist
+    local = torch.as_tensor(local)
+    if local.dtype != torch.int64:
+        raise ValueError(f'expected an int64 histogram, got {local.dtype}')
+    if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size() == 1:
+        return local
+    total = local.clone() if dist.get_backend() == 'nccl' else local.cpu().clone()  # gloo sums host tensors
+    dist.all_reduce(total, op=dist.ReduceOp.SUM)
+    return total.to(local.device)
+
+
 def slide_summary(stats: torch.Tensor, pixels_per_tile: int) -> Dict[str, float]:
     """Slide-level rate / distortion from the gathered records."""
     s = stats.double().cpu()
@@ -560,7 +575,7 @@ class SlideCoder:
     # ---- pipelined segmentation of compressed tiles ---------------------------------------------------------
     def segment_batches(self, payload_batches, h: int, w: int, seg_model, targets=None, threshold: float = 0.5,
                         threshold_on: str = 'scores', top_k: int = 5, scores: bool = False, keep_logits: bool = False,
-                        to_host: bool = False):
+                        to_host: bool = False, roc_bits=None, extents=None):
         """Generator: for every list of chunk byte strings (the 16-byte '>QQ' tile size in front of the rANS payload, as
         ZarrArray.read_chunk_bytes returns and segmenters.segment_compressed takes them; tiles of h x w pixels) the
         prediction of the segmentation head ``seg_model`` (a JNet in eval mode), in order:
@@ -568,6 +583,10 @@ class SlideCoder:
         ``targets``: an iterable beside ``payload_batches`` of (n,h,w) uint8 label maps (host arrays or CUDA tensors);
         with it the counts are made (segmenters.predict).  Results are CUDA tensors, or with ``to_host`` numpy arrays;
         the class map then lies in a pinned ring buffer that stays valid until the generator has advanced two more times.
+        ``roc_bits`` (8..14; one-class heads, needs ``targets``): each result gains 'roc_hist' (2, 2^roc_bits) int64, the
+        batch's logit histograms of negatives and positives (segmenters.roc_histogram); ``extents``: an iterable beside
+        the batches of (n, 2) integers (rows, cols), the part of each tile that the histogram counts.  A histogram is
+        there to be summed over the slide (it adds exactly) and stays a CUDA tensor with ``to_host`` too.
 
         The stages of decompress_batches: a worker range-decodes up to `depth` batches ahead (host or device coder), the
         symbols cross on the H2D side stream; then, on the main stream, dequantiser, synthesis track with its bridges
@@ -576,7 +595,8 @@ class SlideCoder:
         repeated on the head's fp32 torch ops; ``self.timers`` holds the seconds per stage and 'head_fp32_repeats'.
 
         ValueError before any work: seg_model in training mode, a head built for other latent channels than the
-        codec's, a bad threshold / threshold_on / top_k; and for every batch, before it is handed to the decoder: a chunk
+        codec's, a bad threshold / threshold_on / top_k, roc_bits without targets, for a head of several classes or
+        outside 8..14, extents without roc_bits; and for every batch, before it is handed to the decoder: a chunk
         whose header is not (h, w) -- chunks of mixed tile sizes."""
         from .codec import _module
         from . import segmenters
@@ -591,12 +611,21 @@ class SlideCoder:
             raise ValueError(f'top_k must be a positive integer, got {top_k!r}')
         if h % 2 ** self.level or w % 2 ** self.level:
             raise ValueError(f'tiles of {h} x {w} pixels are no multiple of 2^{self.level}')
+        roc = None
+        if roc_bits is not None:
+            if targets is None:
+                raise ValueError('roc_bits needs targets: the histograms are those of the labelled pixels')
+            if seg._num_classes != 1:
+                raise ValueError(f'roc_bits needs a one-class head, this one has {seg._num_classes} classes')
+            roc = (segmenters._check_roc_bits(roc_bits), iter(extents) if extents is not None else None)
+        elif extents is not None:
+            raise ValueError('extents bound the ROC histograms: they need roc_bits')
         return self._segment_batches(payload_batches, int(h), int(w), seg, targets,
                                      dict(threshold=threshold, threshold_on=threshold_on, top_k=int(top_k), scores=scores),
-                                     keep_logits, to_host)
+                                     keep_logits, to_host, roc)
 
     @torch.no_grad()
-    def _segment_batches(self, payload_batches, h, w, seg, targets, how, keep_logits, to_host):
+    def _segment_batches(self, payload_batches, h, w, seg, targets, how, keep_logits, to_host, roc=None):
         import struct
         from concurrent.futures import ThreadPoolExecutor
         from . import _lib, segmenters
@@ -621,11 +650,12 @@ class SlideCoder:
             cls = res['cls']
             out = self._ring('c').take(k, tuple(cls.shape), torch.uint8)
             _lib.check(_lib.lib().cae_copy_to_host(out.data_ptr(), cls.data_ptr(), cls.numel()))
-            host = {key: None if v is None else v.cpu().numpy() for key, v in res.items() if key != 'cls'}
+            stay = {key: res[key] for key in ('roc_hist',) if key in res}  # there to be summed: left on the device
+            host = {key: None if v is None else v.cpu().numpy() for key, v in res.items() if key != 'cls' and key not in stay}
             _clock(tm, 'copy', t0)
-            return dict(host, cls=out.numpy())
+            return dict(host, cls=out.numpy(), **stay)
 
-        def launch(k, sym, target):
+        def launch(k, sym, target, extent):
             n = sym.size(0)
             if self.coder != 'device':
                 with torch.cuda.stream(up):
@@ -651,6 +681,8 @@ class SlideCoder:
                 target = torch.as_tensor(np.ascontiguousarray(target)).to(main.device)
             res = segmenters.predict(logits, target, **how)
             res['logits'] = logits if keep_logits else None
+            if roc is not None:
+                res['roc_hist'] = segmenters.roc_histogram(logits, target, extent=extent, bits=roc[0])
             done = torch.cuda.Event(blocking=True)
             done.record(main)
             _clock(tm, 'predict', t0)
@@ -661,8 +693,8 @@ class SlideCoder:
             with ThreadPoolExecutor(max_workers=workers) as pool, ThreadPoolExecutor(max_workers=1) as out_pool:
                 inflight, outgoing = [], []
 
-                def emit(j, fut, target):
-                    res, done = launch(j, fut.result(), target)
+                def emit(j, fut, target, extent):
+                    res, done = launch(j, fut.result(), target, extent)
                     if not to_host:
                         return [res]
                     outgoing.append(out_pool.submit(fetch, j, res, done))
@@ -671,7 +703,8 @@ class SlideCoder:
 
                 for k, payloads in enumerate(payload_batches):
                     target = next(targets) if targets is not None else None
-                    inflight.append((k, pool.submit(self._decode, k, strip(payloads), lh * lw, tm), target))
+                    extent = next(roc[1]) if roc is not None and roc[1] is not None else None
+                    inflight.append((k, pool.submit(self._decode, k, strip(payloads), lh * lw, tm), target, extent))
                     if len(inflight) > depth:
                         yield from emit(*inflight.pop(0))
                 while inflight:

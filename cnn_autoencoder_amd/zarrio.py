@@ -504,7 +504,8 @@ def decompress_image(input_filename: str, data_group: str = '0/0', checkpoint=No
 
 def segment_image(input_filename: str, seg_model, output_filename: str, data_group: str = '0/0', checkpoint=None,
                   target_group: Optional[str] = None, batch_tiles: int = 4, threshold: float = 0.5,
-                  threshold_on: str = 'scores', top_k: int = 5, scores: bool = False, coder: str = 'host') -> Dict:
+                  threshold_on: str = 'scores', top_k: int = 5, scores: bool = False, coder: str = 'host',
+                  roc_bits: Optional[int] = None) -> Dict:
     """The reference's segmentation harness on a compressed slide (test_cae_classifier.py:46-55 and its metrics), without
     decoding a pixel to the host: the chunk bytes of the 'cae'-coded array ``data_group`` of ``input_filename`` go through
     SlideCoder.segment_batches (range decoder on ``coder``, synthesis track, the head ``seg_model``, cae_seg_predict)
@@ -521,6 +522,14 @@ def segment_image(input_filename: str, seg_model, output_filename: str, data_gro
     counts can be corrected exactly on the host (several classes: label 255, wrong in tp and tp_top, then fp = fn =
     pixels - tp and p = pixels of the real part -- so a ragged image with a target needs at most 255 classes; one class:
     label 0, and the padding's share of tn and fp is taken off from the class map).
+    ``roc_bits`` (8..14, segmenters.ROC_BITS = 14; needs a target and a one-class head): the slide's threshold-free
+    results from logit histograms of 2^roc_bits bins per class (segmenters.roc_histogram over each tile's real pixels,
+    summed on the device, then over the ranks: slide.reduce_histogram).  The result gains 'auc', 'auc_slack' (the AUC of the
+    unbinned logits lies inside auc +- auc_slack) and 'roc' (segmenters.roc_from_histogram), and rank 0 writes the curve as
+    the reference does (test_cae_classifier.py:356-364), float32 1-D arrays in one chunk, Zlib(9):
+
+        image_level/fpr, image_level/tpr, image_level/thrsh (thresholds on the scores), image_level/thrsh_logit
+
     -> segmenters.class_metrics of the slide's summed record, plus
     'records': the (tiles, 6) int64 per-tile records of all ranks in tile order (slide.gather_counts), 'tiles' and
     'head_fp32_repeats' (this rank's); without a target only the last two."""
@@ -549,6 +558,10 @@ def segment_image(input_filename: str, seg_model, output_filename: str, data_gro
     if tz is not None and C > 255 and (H % ph or W % pw):
         raise ValueError('a target on an image that is no multiple of its chunks needs at most 255 classes (label 255 '
                          'marks the padding of the edge chunks)')
+    if roc_bits is not None:
+        if tz is None or C != 1:
+            raise ValueError('roc_bits needs a target_group and a one-class head')
+        roc_bits = segmenters._check_roc_bits(roc_bits)
     sc = slide.SlideCoder(z.codec, coder=coder)
     zc = ZarrArray.create(output_filename, 'class/0/0', (H, W), (ph, pw), np.bool_ if C == 1 else np.uint8,
                           codec=Zlib(9), write_meta=rank == 0)
@@ -572,11 +585,18 @@ def segment_image(input_filename: str, seg_model, output_filename: str, data_gro
             out[t, :part.shape[0], :part.shape[1]] = part
         return out
 
+    def extents(group):  # the real pixels of every tile: the padding of the edge chunks is in no histogram
+        return np.array([(min(ph, H - i * ph), min(pw, W - j * pw)) for i, j, _ in group], dtype=np.int32).reshape(-1, 2)
+
     stream = sc.segment_batches((chunks(g) for g in groups), ph, pw, seg,
                                 targets=None if tz is None else (labels(g) for g in groups), threshold=threshold,
-                                threshold_on=threshold_on, top_k=top_k, scores=scores, to_host=True)
+                                threshold_on=threshold_on, top_k=top_k, scores=scores, to_host=True, roc_bits=roc_bits,
+                                extents=None if roc_bits is None else (extents(g) for g in groups))
     records = []
+    roc_hist = None
     for group, res in zip(groups, stream):  # res['cls']: pinned ring buffer, written out before the generator advances
+        if roc_bits is not None:
+            roc_hist = res['roc_hist'] if roc_hist is None else roc_hist + res['roc_hist']
         for t, (i, j, _) in enumerate(group):
             ch, cw = min(ph, H - i * ph), min(pw, W - j * pw)
             zc.write_chunk((i, j), res['cls'][t, :ch, :cw].astype(zc.dtype))
@@ -606,5 +626,14 @@ def segment_image(input_filename: str, seg_model, output_filename: str, data_gro
             pass
         allrec = slide.gather_counts(local).cpu().numpy()
         out.update(segmenters.class_metrics(allrec.sum(axis=0), multiclass=C > 1), records=allrec)
+    if roc_bits is not None:
+        if roc_hist is None:  # a rank without tiles
+            roc_hist = torch.zeros((2, 1 << roc_bits), dtype=torch.int64, device='cuda')
+        roc = segmenters.roc_from_histogram(slide.reduce_histogram(roc_hist))
+        out.update(auc=roc['auc'], auc_slack=roc['auc_slack'], roc=roc)
+        if rank == 0:
+            for name, key in (('fpr', 'fpr'), ('tpr', 'tpr'), ('thrsh', 'score_thresholds'), ('thrsh_logit', 'thresholds')):
+                v = roc[key].astype(np.float32)
+                ZarrArray.create(output_filename, f'image_level/{name}', v.shape, v.shape, np.float32, codec=Zlib(9))[:] = v
     _barrier()
     return out

@@ -673,6 +673,40 @@ int cae_seg_predict(const float *logits_dev, const uint8_t *target_dev, int n, i
                     size_t workspace_bytes, void *stream);
 size_t cae_seg_predict_workspace(int n, int c, size_t hw);
 
+/* ---- ROC histograms of a one-class head (csrc/cae_seg_roc.hip) -----------------------------------
+ * The threshold-free results of the reference's harness -- the per-image auc (utils/_metrics.py:128-131), the
+ * slide-level ROC curve and its AUC (test_cae_classifier.py:233-264, 356-364) -- without sorting a score: the
+ * prediction is logit > t, so the curve is fixed by how many positive and how many negative pixels lie at or above each
+ * threshold.
+ * logits_dev (n, 1, h, w) fp32 contiguous, read where they stand (any 4-byte aligned address); target_dev (n, h, w)
+ * uint8 at any address; extent_dev int32 [n][2] = (rows, cols) on the device or NULL: only pixels with y < rows and
+ * x < cols are counted, values clamped to 0..h / 0..w, NULL = whole planes.
+ *   key:   x' = x + 0.0f (-0 becomes +0), u = the bits of x', key = (u >> 31) ? ~u : (u | 0x80000000); a NaN logit has
+ *          key 0: it lies below every threshold, as in cae_seg_predict, where logit > t is false for NaN.
+ *   bin:   key >> (32 - bits), 8 <= bits <= 14; monotone in the logit: bin(x) >= j exactly when x >= e_j, the smallest
+ *          non-NaN fp32 value of bin j, i.e. x > nextafter(e_j, -inf).  Bins that hold only NaN bit patterns stay
+ *          empty, except bin 0.
+ *   class: target > 0 is positive, the binarisation of cae_seg_predict.
+ *   hist_dev int64 [m][2][2^bits], row 0 the negatives and row 1 the positives; m = n with per_image, else 1 (the sum
+ *          over the batch).  Every entry is written, nothing is accumulated into what the buffer held; integers, exact
+ *          in any order, and they add across tiles, batches and ranks.
+ * From a histogram, with P_j = sum_{b >= j} pos_b and N_j = sum_{b >= j} neg_b: the curve starts at (0, 0) (threshold
+ * +inf) and has one point (N_j / N, P_j / P) per non-empty bin from the top down -- exactly the (fp, tp) of
+ * cae_seg_predict at t = nextafter(e_j, -inf) -- auc = sum_b pos_b (2 neg_below_b + neg_b) / (2 P N), and the AUC of
+ * the unbinned logits lies within auc_slack = sum_b pos_b neg_b / (2 P N) of it (equal when every logit is an e_j).
+ *
+ * Two launches, asynchronous on `stream`: blocks that count a contiguous span of an image's pixels in an LDS table of
+ * 2^(bits+3) bytes and store it as one partial per (image, block) in workspace_dev (cae_seg_roc_workspace bytes,
+ * 16-byte aligned), then the sum of the partials in a fixed order.  No global atomics; neither histogram nor workspace
+ * needs initialising.  CAE_ERR_ARG before any launch: bits outside 8..14, n < 0, h or w < 1, and for n >= 1 a NULL or
+ * misaligned pointer or a workspace that is too small.  n == 0: CAE_OK, nothing launched.  cae_seg_roc_workspace and
+ * cae_seg_roc_blocks (blocks per image, for the tests) return 0 for shapes cae_seg_roc_hist refuses and for n == 0. */
+int cae_seg_roc_hist(const float *logits_dev, const uint8_t *target_dev, const int32_t *extent_dev, int n, int h, int w,
+                     int bits, int per_image, int64_t *hist_dev, void *workspace_dev, size_t workspace_bytes,
+                     void *stream);
+size_t cae_seg_roc_workspace(int n, int h, int w, int bits);
+int cae_seg_roc_blocks(int n, int h, int w, int bits);
+
 #ifdef __cplusplus
 }
 #endif
