@@ -939,7 +939,7 @@ int cae_gdn_forward(cae_model_t *mm, int track, int index, const float *x, int n
 
 int cae_tile_sse(const uint8_t *a, const uint8_t *b, int n, size_t elems, double *sse, void *stream) {
     if (!a || !b || !sse) return fail(CAE_ERR_ARG, "NULL argument");
-    if (n < 1 || elems < 1) return fail(CAE_ERR_ARG, "bad shape");
+    if (n < 1 || n > 65535 || elems < 1) return fail(CAE_ERR_ARG, "bad shape");  // n is the grid's y dimension
     hipStream_t st = (hipStream_t)stream;
     // the float64 output doubles as the exact integer accumulator (same 8-byte cells)
     unsigned long long *acc = reinterpret_cast<unsigned long long *>(sse);

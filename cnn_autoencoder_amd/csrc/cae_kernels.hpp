@@ -1118,12 +1118,17 @@ tile_ssim_kernel(const uint8_t *a, const uint8_t *b, int H, int W, int C, int bx
                 for (int k = 0; k < WIN; ++k)
 #pragma unroll
                     for (int q = 0; q < 5; ++q) s[q] += hs[q][y + k][x];
-                const double ux = s[0] / 49.0, uy = s[1] / 49.0;
-                const double vx = cov_norm * (s[2] / 49.0 - ux * ux), vy = cov_norm * (s[3] / 49.0 - uy * uy);
-                const double vxy = cov_norm * (s[4] / 49.0 - ux * uy);
-                const double A1 = 2.0 * ux * uy + C1, A2 = 2.0 * vxy + C2;
-                const double B1 = ux * ux + uy * uy + C1, B2 = vx + vy + C2;
-                acc += (A1 * A2) / (B1 * B2);
+                {
+                    // no fused multiply-adds in the index: with one rounding in 2 ux uy + C1 and two in ux ux + uy uy +
+                    // C1 a window of two identical tiles would not give exactly 1
+#pragma clang fp contract(off)
+                    const double ux = s[0] / 49.0, uy = s[1] / 49.0;
+                    const double vx = cov_norm * (s[2] / 49.0 - ux * ux), vy = cov_norm * (s[3] / 49.0 - uy * uy);
+                    const double vxy = cov_norm * (s[4] / 49.0 - ux * uy);
+                    const double A1 = 2.0 * ux * uy + C1, A2 = 2.0 * vxy + C2;
+                    const double B1 = ux * ux + uy * uy + C1, B2 = vx + vy + C2;
+                    acc += (A1 * A2) / (B1 * B2);
+                }
             }
         }
     }
@@ -1157,6 +1162,9 @@ static __global__ void ssim_reduce_kernel(const double *part, int blocks_per_til
 // reference's harness calls them, test_cae.py:21-45): sRGB -> linear (table of the 256 levels) -> XYZ (sRGB / D65
 // matrix) -> L*a*b* (2-degree D65 white) -> Euclidean distance, all float64; per-block partial sums, fixed order.
 __device__ __forceinline__ void rgb_to_lab(const double *lin, const uint8_t *px, double &L, double &A, double &B) {
+    // no fused multiply-adds here or in the distance: fused across the two inlined copies, 116 y0 - 16 - (116 y1 - 16)
+    // of one colour is not 0, and identical tiles would not give exactly 0
+#pragma clang fp contract(off)
     const double r = lin[px[0]], g = lin[px[1]], b = lin[px[2]];
     double x = (0.412453 * r + 0.357580 * g + 0.180423 * b) / 0.95047;
     double y = (0.212671 * r + 0.715160 * g + 0.072169 * b) / 1.0;
@@ -1182,6 +1190,7 @@ tile_delta_e_kernel(const uint8_t *a, const uint8_t *b, size_t pixels, int block
     const uint8_t *pa = a + (size_t)tile * pixels * 3, *pb = b + (size_t)tile * pixels * 3;
     double acc = 0.0;
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < pixels; i += (size_t)blocks_per_tile * 256) {
+#pragma clang fp contract(off)
         double l0, a0, b0, l1, a1, b1;
         rgb_to_lab(lin, pa + 3 * i, l0, a0, b0);
         rgb_to_lab(lin, pb + 3 * i, l1, a1, b1);
@@ -1252,18 +1261,20 @@ msssim_level_kernel(const float *X, const float *Y, int H, int W, int bx_per_row
         sy[r][x] = ok ? py[(size_t)iy * W + ix] : 0.f;
     }
     __syncthreads();
-    // dimension 2 (rows) first, as pytorch_msssim's gaussian_filter does
+    // dimension 2 (rows) first, as pytorch_msssim's gaussian_filter does.  Every tap of both passes is an explicit fmaf:
+    // left to contraction the compiler fuses four of the five quantities (packed) and not the fifth, and then the
+    // filtered x x, y y and x y of X == Y differ in their last bits and the level is not exactly (1, 1)
     for (int i = threadIdx.x; i < T * IN; i += 256) {
         const int y = i / IN, x = i - y * IN;
         float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f, a4 = 0.f;
 #pragma unroll
         for (int k = 0; k < WIN; ++k) {
             const float u = sx[y + k][x], v = sy[y + k][x], w = g[k];
-            a0 += w * u;
-            a1 += w * v;
-            a2 += w * (u * u);
-            a3 += w * (v * v);
-            a4 += w * (u * v);
+            a0 = fmaf(w, u, a0);
+            a1 = fmaf(w, v, a1);
+            a2 = fmaf(w, u * u, a2);
+            a3 = fmaf(w, v * v, a3);
+            a4 = fmaf(w, u * v, a4);
         }
         vs[0][y][x] = a0;
         vs[1][y][x] = a1;
@@ -1281,14 +1292,19 @@ msssim_level_kernel(const float *X, const float *Y, int H, int W, int bx_per_row
 #pragma unroll
             for (int k = 0; k < WIN; ++k)
 #pragma unroll
-                for (int q = 0; q < 5; ++q) m[q] += g[k] * vs[q][y][x + k];
-            const float mu1 = m[0], mu2 = m[1];
-            const float mu1_sq = mu1 * mu1, mu2_sq = mu2 * mu2, mu12 = mu1 * mu2;
-            const float s1 = m[2] - mu1_sq, s2 = m[3] - mu2_sq, s12 = m[4] - mu12;
-            const float cs = (2.f * s12 + C2) / (s1 + s2 + C2);
-            const float ss = ((2.f * mu12 + C1) / (mu1_sq + mu2_sq + C1)) * cs;
-            ssum += (double)ss;
-            csum += (double)cs;
+                for (int q = 0; q < 5; ++q) m[q] = fmaf(g[k], vs[q][y][x + k], m[q]);
+            {
+                // and no fused multiply-adds in the index: a square fused into one variance and rounded in another
+                // makes s1, s2 and s12 of X == Y differ
+#pragma clang fp contract(off)
+                const float mu1 = m[0], mu2 = m[1];
+                const float mu1_sq = mu1 * mu1, mu2_sq = mu2 * mu2, mu12 = mu1 * mu2;
+                const float s1 = m[2] - mu1_sq, s2 = m[3] - mu2_sq, s12 = m[4] - mu12;
+                const float cs = (2.f * s12 + C2) / (s1 + s2 + C2);
+                const float ss = ((2.f * mu12 + C1) / (mu1_sq + mu2_sq + C1)) * cs;
+                ssum += (double)ss;
+                csum += (double)cs;
+            }
         }
     }
     red[0][threadIdx.x] = ssum;

@@ -263,7 +263,8 @@ int cae_copy_to_host(void *dst_pinned_host, const void *src_dev, size_t bytes);
 
 /* Per-tile sum of squared differences of two (n, elems) uint8 batches -> sse_dev[n] (float64).
  * The distortion half of the per-tile statistics record the slide driver all-gathers (the
- * reference's harness computes MSE/PSNR on the host, test_cae.py:55-68). */
+ * reference's harness computes MSE/PSNR on the host, test_cae.py:55-68).  n is at most 65535, as for cae_tile_ssim
+ * and cae_tile_delta_e (one grid row per tile): a larger n is CAE_ERR_ARG before anything is written. */
 int cae_tile_sse(const uint8_t *a_dev, const uint8_t *b_dev, int n, size_t elems, double *sse_dev, void *stream);
 
 /* ---- measurement ------------------------------------------------------------------------

@@ -23,8 +23,9 @@ def window(win_size, win_sigma, dtype=torch.float64):
     return g / g.sum()
 
 
-def level(X, Y, g, c1, c2):
-    """one scale: (ssim mean, cs mean) per (N, C); the window applied separably without padding, dimension 2 first"""
+def level_maps(X, Y, g, c1, c2):
+    """one scale: the per-pixel (ssim map, cs map), each (N, C, H - win + 1, W - win + 1) in the dtype of X; the window
+    applied separably without padding, dimension 2 first"""
     C = X.shape[1]
     k = g.to(X.dtype).view(1, 1, 1, -1).repeat(C, 1, 1, 1)
 
@@ -35,6 +36,12 @@ def level(X, Y, g, c1, c2):
     s1, s2, s12 = gauss(X * X) - mu1 * mu1, gauss(Y * Y) - mu2 * mu2, gauss(X * Y) - mu1 * mu2
     cs_map = (2 * s12 + c2) / (s1 + s2 + c2)
     ssim_map = ((2 * mu1 * mu2 + c1) / (mu1 * mu1 + mu2 * mu2 + c1)) * cs_map
+    return ssim_map, cs_map
+
+
+def level(X, Y, g, c1, c2):
+    """one scale: (ssim mean, cs mean) per (N, C) of level_maps"""
+    ssim_map, cs_map = level_maps(X, Y, g, c1, c2)
     return ssim_map.flatten(2).mean(-1), cs_map.flatten(2).mean(-1)
 
 
