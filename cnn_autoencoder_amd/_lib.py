@@ -165,6 +165,18 @@ SYMBOLS = {
                                  c_size_t, c_void_p]),
     'cae_seg_roc_workspace': (c_size_t, [c_int, c_int, c_int, c_int]),
     'cae_seg_roc_blocks': (c_int, [c_int, c_int, c_int, c_int]),
+    'cae_seg_set_weights': (c_int, [c_void_p, c_void_p, c_int, c_void_p]),
+    'cae_seg_pack_dev': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p]),
+    'cae_seg_conv2d_workspace': (c_size_t, [c_int] * 6),
+    'cae_seg_conv2d': (c_int, [c_void_p] * 4 + [c_int] * 6 + [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    'cae_seg_wgrad_splits': (c_int, [c_int] * 6),
+    'cae_seg_wgrad_workspace': (c_size_t, [c_int] * 6),
+    'cae_seg_wgrad': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
+                              c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    'cae_seg_norm_workspace': (c_size_t, [c_int, c_int]),
+    'cae_seg_norm_relu_backward': (c_int, [c_void_p] * 4 + [c_int, c_int, c_size_t] + [c_void_p] * 4 + [c_size_t, c_void_p]),
+    'cae_seg_channel_sums_workspace': (c_size_t, [c_int, c_int]),
+    'cae_seg_channel_sums': (c_int, [c_void_p, c_int, c_int, c_size_t, c_void_p, c_void_p, c_size_t, c_void_p]),
 }
 
 CAE_ANALYSIS, CAE_SYNTHESIS = 0, 1

@@ -322,6 +322,54 @@ int cae_seg_forward(cae_seg_t *h, const float *latents_dev, const float *const *
     return run(SegSrc{t2, ab2, planes(c.level_channels[L - 1])}, none, logits_dev, SEG_OUT_NCHW, lh << L, lw << L, nullptr);
 }
 
+int cae_seg_set_weights(cae_seg_t *h, const float *const *weights_dev, int n_weights, void *stream) {
+    Seg *s = reinterpret_cast<Seg *>(h);
+    if (!s || !weights_dev) return fail(CAE_ERR_ARG, "NULL argument");
+    const cae_seg_config &c = s->cfg;
+    if (n_weights != cae_seg_weight_count(&c))
+        return fail(CAE_ERR_ARG, "%d weight arrays given, this configuration has %d", n_weights, cae_seg_weight_count(&c));
+    for (int i = 0; i < n_weights; ++i)
+        if (!weights_dev[i]) return fail(CAE_ERR_ARG, "weight array %d is NULL", i);
+    hipStream_t st = (hipStream_t)stream;
+    std::lock_guard<std::mutex> lk(s->mu);
+    CAE_TRY(s->ensure_device());
+    CAE_TRY(s->order_stream(st));
+    const int64_t ticket = ++s->flag_seq;
+    *(volatile int *)(s->flags + ticket % Seg::kFlagSlots) = 0;
+    g_seg_ticket = ticket;
+    int *flag = s->flags_dev + ticket % Seg::kFlagSlots;
+    const bool bn = c.batch_norm != 0;
+    int k = 0, stage = 0;
+    // (the walk of cae_seg_create)
+    auto layer = [&](bool biased) -> int {
+        SegLayer &l = s->st[stage++];
+        CAE_TRY(launch_seg_pack_dev(weights_dev[k++], l.cin_a, l.cin_b, l.cout, l.ks, l.up, l.wp.get<char>(), flag, st));
+        if (biased) CAE_TRY(launch_seg_pad_vec(weights_dev[k++], l.cout, l.up, l.groups * l.ct * 32, false, l.bias.get<float>(), flag, st));
+        if (l.norm) {
+            CAE_TRY(launch_seg_pad_vec(weights_dev[k++], l.cout, false, l.cp, true, l.gamma.get<float>(), flag, st));
+            CAE_TRY(launch_seg_pad_vec(weights_dev[k++], l.cout, false, l.cp, true, l.beta.get<float>(), flag, st));
+        }
+        return CAE_OK;
+    };
+    CAE_TRY(layer(false));
+    CAE_TRY(layer(false));
+    CAE_TRY(layer(true));
+    for (int i = 0; i < c.levels; ++i) {
+        if (c.concat_bridges) {
+            if (bn) {
+                const int bc = c.bridge_channels[i], cp = (bc + 7) / 8 * 8;
+                CAE_TRY(launch_seg_pad_vec(weights_dev[k++], bc, false, cp, true, s->proj_gamma[i].get<float>(), flag, st));
+                CAE_TRY(launch_seg_pad_vec(weights_dev[k++], bc, false, cp, true, s->proj_beta[i].get<float>(), flag, st));
+            }
+            CAE_TRY(layer(false));
+        }
+        CAE_TRY(layer(false));
+        CAE_TRY(layer(false));
+        if (i + 1 < c.levels) CAE_TRY(layer(true));
+    }
+    return layer(true);
+}
+
 void cae_seg_tile(int *tx, int *ty) {
     if (tx) *tx = SEG_TX;
     if (ty) *ty = SEG_TY;

@@ -7,7 +7,9 @@ The module classes carry the reference's attribute names, so the ``state_dict`` 
 and its checkpoints load with ``strict=True``.  The parameter holders are ordinary torch layers; they are never called
 on the hot path.  ``force_torch=True`` runs the same head as torch ops on the device (the measurement's comparison and
 a second opinion in the tests).  Not built, and raising ``NotImplementedError``: ``UNet`` with its own analysis track
-(image domain, ``MaxPool``), training the head, calling it while autograd is recording.
+(image domain, ``MaxPool``), training the head, calling it while autograd is recording.  Training lives beside this module:
+``seg_train.JNetTrain`` is this ``JNet`` with a backward pass (same state dict), with the loader, forward function, losses
+and step of the reference's head training.
 
 ``predict`` / ``class_metrics`` turn logits into what the reference's harness hands out (class map, scores, counts and
 metrics; ``cae_seg_predict``, csrc/cae_seg_predict.hip); ``slide.SlideCoder.segment_batches`` and ``zarrio.segment_image``

@@ -645,6 +645,51 @@ size_t cae_seg_packed_halves(int cin_a, int cin_b, int cout, int ks, int up);
 int cae_seg_pack(const float *w, int cin_a, int cin_b, int cout, int ks, int up, uint16_t *out, size_t capacity);
 void cae_seg_tile(int *tx, int *ty); /* output tile of the head's convolution kernel, in pixels */
 
+/* ---- Training the head: backward pass per operation (csrc/cae_seg_train.hip, csrc/cae_kernels_seg_train.hpp) ----
+ * All tensors are NCHW fp32 on the device; (a, b) pairs have the layout of cae_seg_taps, (n, 8 ceil(c / 8), 2).  Every
+ * entry point is asynchronous on `stream`, returns CAE_ERR_ARG before any launch on bad shapes or NULL pointers and does
+ * nothing for n == 0.  Workspaces are the caller's.  flag_dev is a device int the caller zeroed: a staged value outside
+ * the valid range of f16x3 (finite, |v| <= 65504) sets it to 1 and the results of the call are then invalid.  Nothing is
+ * accumulated with atomics and every merge has a fixed order: results are bitwise repeatable.
+ *
+ * cae_seg_set_weights: refreshes a handle's packed weights, bias rows, gamma and beta from device tensors, in the order
+ * and layouts of cae_seg_create.  It draws a range ticket (cae_seg_last_ticket) of its own: a weight, gamma or beta
+ * outside the f16 range makes cae_seg_range_check fail for that ticket, and the handle must not be used until the
+ * weights have been set again.
+ * cae_seg_pack_dev: cae_seg_pack reading a device weight and writing device halves, byte for byte (flag_dev may be NULL).
+ * cae_seg_conv2d: out (n, cout, h, w) = stride-1 zero-padded ks x ks convolution (ks 1 or 3) of v with the device weight
+ * w (cout, cin, ks, ks) plus bias (or NULL); v = x (n, cin, h, w) when ab_dev is NULL, else max(fmaf(a, x, b), 0); the
+ * forward kernel on freshly packed weights.  With the flipped, transposed weight it is the data gradient of a layer.
+ * cae_seg_wgrad: gw (cout, cin_a + cin_b, ks, ks) = sum_{n,y,x} g[n,co,y,x] v[n,ci,y+ky-P,x+kx-P], v the concatenation of
+ * up to two sources staged as above (zero outside the plane), products gh vh + gh vl + gl vh on
+ * v_mfma_f32_32x32x16_f16 over the pixels.  The pixels are cut into cae_seg_wgrad_splits segments whose partials go to
+ * the workspace (cae_seg_wgrad_workspace bytes) and are added in segment order by a second launch.
+ * cae_seg_norm_relu_backward: v = relu(GroupNorm_C(x)) of (n, c, hw) planes.  g_u = g_v [fmaf(a, x, b) > 0];
+ * dbeta = sum g_u, dgamma = sum g_u xhat over samples and pixels; g_x = gamma rstd (g_u - mean g_u - xhat mean(g_u xhat))
+ * per plane, mean and rstd recomputed from x in two passes with double accumulators.  gx_dev may be NULL.  gamma_dev
+ * NULL (no normalisation): g_x = g_u only.  Workspace: cae_seg_norm_workspace bytes, 8-byte aligned.
+ * cae_seg_channel_sums: out[c] = sum over samples and pixels of g (n, c, hw), double accumulators (bias gradients): plane
+ * sums on a fixed tree into the workspace (cae_seg_channel_sums_workspace bytes, 8-byte aligned), then the samples in order. */
+int cae_seg_set_weights(cae_seg_t *h, const float *const *weights_dev, int n_weights, void *stream);
+int cae_seg_pack_dev(const float *w_dev, int cin_a, int cin_b, int cout, int ks, int up, uint16_t *out_dev, size_t capacity,
+                     int *flag_dev, void *stream);
+size_t cae_seg_conv2d_workspace(int n, int cin, int cout, int h, int w, int ks);
+int cae_seg_conv2d(const float *x_dev, const float *ab_dev, const float *w_dev, const float *bias_dev, int n, int cin,
+                   int cout, int h, int w, int ks, float *out_dev, int *flag_dev, void *workspace_dev,
+                   size_t workspace_bytes, void *stream);
+int cae_seg_wgrad_splits(int n, int h, int w, int cin, int cout, int ks);
+size_t cae_seg_wgrad_workspace(int n, int h, int w, int cin, int cout, int ks);
+int cae_seg_wgrad(const float *g_dev, const float *xa_dev, const float *aba_dev, int cin_a, const float *xb_dev,
+                  const float *abb_dev, int cin_b, int n, int cout, int h, int w, int ks, float *gw_dev, int *flag_dev,
+                  void *workspace_dev, size_t workspace_bytes, void *stream);
+size_t cae_seg_norm_workspace(int n, int c);
+int cae_seg_norm_relu_backward(const float *x_dev, const float *ab_dev, const float *gamma_dev, const float *gv_dev, int n,
+                               int c, size_t hw, float *gx_dev, float *dgamma_dev, float *dbeta_dev, void *workspace_dev,
+                               size_t workspace_bytes, void *stream);
+size_t cae_seg_channel_sums_workspace(int n, int c);
+int cae_seg_channel_sums(const float *g_dev, int n, int c, size_t hw, float *out_dev, void *workspace_dev,
+                         size_t workspace_bytes, void *stream);
+
 /* ---- Prediction from the head's logits (csrc/cae_seg_predict.hip) ------------------------------
  * What the reference's segmentation harness makes of a model's output (test_cae_classifier.py:46-55 save_pred2zarr,
  * utils/_metrics.py:79-193), in one pass over the logits: class map, optional scores, optional per-image counts.
