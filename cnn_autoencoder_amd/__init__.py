@@ -17,6 +17,6 @@ __all__ = ['Analyzer', 'Synthesizer', 'GDN', 'EntropyBottleneck', 'DownsamplingU
            'ResidualUpsamplingUnit',
            'initialize_weights', 'setup_modules', 'load_state_dict', 'autoencoder_from_state_dict',
            'ConvolutionalAutoencoder', 'ConvolutionalAutoencoderBottleneck', 'register_codecs',
-           'pmf_to_quantized_cdf', 'build', 'CaeError', 'LIB_PATH', 'PatchSampler']
+           'pmf_to_quantized_cdf', 'build', 'CaeError', 'LIB_PATH', 'PatchSampler', 'LabeledPatchSampler']
 from . import criteria, metrics, train  # noqa: F401,E402  (validation objective; GPU metrics of the reference harness)
-from .sampler import PatchSampler  # noqa: F401,E402  (training input: patches sampled and augmented on the device)
+from .sampler import LabeledPatchSampler, PatchSampler  # noqa: F401,E402  (training input: patches sampled and augmented on the device)

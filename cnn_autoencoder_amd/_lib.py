@@ -128,6 +128,10 @@ SYMBOLS = {
     'cae_t_sample_patches': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                      c_void_p, c_void_p, ctypes.c_uint64, ctypes.c_uint32, c_float, c_int, c_int, c_int,
                                      c_void_p, c_void_p]),
+    'cae_t_sample_labeled_patches': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
+                                             c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_uint64,
+                                             ctypes.c_uint32, c_float, c_int, c_int, c_int, c_int, c_void_p, c_size_t,
+                                             c_void_p, c_void_p, c_void_p]),
     'cae_cpu_budget': (c_int, []),
     'cae_coder_lockstep': (c_int, []),
     'cae_coder_threads': (c_int, [c_int, c_int]),

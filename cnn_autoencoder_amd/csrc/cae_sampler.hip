@@ -13,6 +13,18 @@
 //                                one contiguous 4 C-byte read, and one 16-byte store per channel plane (VEC: ps % 4 == 0
 //                                and a 16-byte aligned output; else dword stores with a tail)
 //   sample_rotate_kernel<C>      rotation: one output pixel per thread, the four bilinear taps regenerated
+//
+// Labelled patches (cae_t_sample_labeled_patches; reference: RandomRotationInputTarget, _augs.py:52-82, label_density == 2):
+// image and mask share crop and angle; the image is resampled by the exactly interpolating quartic B-spline with reflected
+// edges, the mask by its nearest neighbour.  The spline needs the patch's interpolation coefficients first -- a recursive
+// filter along every row, then every column -- so these kernels do exchange values between lanes:
+//   labeled_lds_kernel<C>        ps <= 128: one block per (sample, channel).  The plane of p is built in LDS (odd row
+//                                stride: a lane per row and a lane per column both walk distinct banks), filtered there
+//                                along rows then columns (one lane per line), and every output pixel reads its 5 x 5
+//                                coefficients from LDS; the block of channel 0 also writes the sample's mask
+//   prefilter_global_kernel      ps > 128: p is written to the workspace by sample_rows_kernel, filtered in place (one
+//   labeled_global_kernel<C>     lane per line, one launch per axis) and read back from global memory by the evaluation
+//   mask_rows_kernel             no rotation: t = m (x is sample_rows_kernel's p)
 #include "cae_hip.h"
 #include "cae_internal.hpp"
 #include "cae_launch.hpp"
@@ -225,13 +237,227 @@ void launch(const SampleArgs &a, int n, bool vec, hipStream_t st) {
     }
 }
 
-}  // namespace
+// ---- labelled patches: quartic B-spline rotation of the image, nearest neighbour of the mask ----------------------------
 
-extern "C" int cae_t_sample_patches(const uint8_t *pool_dev, int tiles, int h, int w, int c, const int32_t *tile_hw_dev,
-                                    const int32_t *tile_dev, const int32_t *y0_dev, const int32_t *x0_dev,
-                                    const int32_t *tile_host, const float *cos_dev, const float *sin_dev, uint64_t seed,
-                                    uint32_t sample_base, float noise_std, int normalize, int n, int ps, float *out_dev,
-                                    void *stream) {
+struct LabeledArgs {
+    SampleArgs s;           // the image side; s.out is x
+    const uint8_t *labels;  // [T][H][W][K]
+    float *t;               // [n][Kt][ps][ps], Kt = map_labels ? 1 : K
+    float *coef;            // the workspace, [n][C][ps][ps] (ps > LDS_PS only)
+    int K, map_labels;
+};
+
+constexpr int LDS_PS = 128;  // the largest patch whose plane is filtered and sampled in LDS
+
+// The poles of the quartic B-spline's inverse filter, sqrt(664 -+ sqrt(438976)) +- sqrt(304) - 19, and the gain of a line,
+// the product over both of (1 - z)(1 - 1 / z) = 384 (the samples of the spline are 1, 76, 230, 76, 1 over 384).
+constexpr float POLE1 = -0.36134122590021184f, POLE2 = -0.013725429297341663f;
+constexpr float SPLINE_GAIN = 384.0f;
+// The start of the causal recursion sums z^i over the whole line.  |POLE1|^28 < 2^-41: the terms from 28 on change no
+// float32 sum, and z^n is below 2^-93 from n = 64 on (the line's other end reaches the start with that weight).
+constexpr int START_TERMS = 28, POWER_TERMS = 64;
+
+// one pole over the line c[0], c[stride], ..., n values, in place; `gain` scales the line on the way in
+__device__ __forceinline__ void filter_pole(float *c, int n, int stride, float z, float gain) {
+    float zn = 1.0f;
+    for (int i = 0; i < min(n, POWER_TERMS); ++i) zn *= z;
+    if (n > POWER_TERMS) zn = 0.0f;
+    const float c0 = gain * c[0];
+    float acc = c0 + zn * (gain * c[(n - 1) * stride]), zi = z;
+    const int terms = min(n, START_TERMS);
+    for (int i = 1; i < terms; ++i) {
+        acc += zi * (gain * (c[i * stride] + zn * c[(n - 1 - i) * stride]));
+        zi *= z;
+    }
+    float v = c0 + z / (1.0f - zn * zn) * acc;
+    c[0] = v;
+    for (int i = 1; i < n; ++i) {
+        v = gain * c[i * stride] + z * v;
+        c[i * stride] = v;
+    }
+    v *= z / (z - 1.0f);
+    c[(n - 1) * stride] = v;
+    for (int i = n - 2; i >= 0; --i) {
+        v = z * (v - c[i * stride]);
+        c[i * stride] = v;
+    }
+}
+
+__device__ __forceinline__ void filter_line(float *c, int n, int stride) {
+    filter_pole(c, n, stride, POLE1, SPLINE_GAIN);
+    filter_pole(c, n, stride, POLE2, 1.0f);
+}
+
+// d c b a | a b c d | d c b a, as often as needed (|idx| is at most a few ps: see taps_of)
+__device__ __forceinline__ int reflect(int idx, int n) {
+    int m = idx % (2 * n);
+    if (m < 0) m += 2 * n;
+    return m >= n ? 2 * n - 1 - m : m;
+}
+
+// the quartic B-spline at distance d; 0 from 2.5 on
+__device__ __forceinline__ float bspline4(float d) {
+    d = fabsf(d);
+    if (d < 0.5f) return d * d * (d * d * 0.25f - 0.625f) + 115.0f / 192.0f;
+    if (d < 1.5f) return d * (d * (d * (5.0f / 6.0f - d * (1.0f / 6.0f)) - 1.25f) + 5.0f / 24.0f) + 55.0f / 96.0f;
+    const float e = fminf(d, 2.5f) - 2.5f;
+    return e * e * e * e * (1.0f / 24.0f);
+}
+
+// what output pixel (i, j) reads: five reflected rows and columns with their weights; the mask's nearest neighbour is the
+// middle tap
+struct Taps {
+    int ry[5], rx[5];
+    float wy[5], wx[5];
+};
+
+__device__ __forceinline__ void taps_of(int ps, float ca, float sa, int i, int j, Taps &t) {
+    const float c = 0.5f * (float)(ps - 1), di = (float)i - c, dj = (float)j - c;
+    // |cos|, |sin| <= 1 keep a source point within (-0.21 ps, 1.21 ps).  Whatever else the device arrays hold is clamped
+    // to [-ps, 2 ps] before the cast (fmaxf returns the bound for a NaN), so the tap indices stay within a few ps.
+    const float lo = -(float)ps, hi = 2.0f * (float)ps;
+    const float y = fminf(fmaxf(c + (ca * di + sa * dj), lo), hi);
+    const float x = fminf(fmaxf(c + (ca * dj - sa * di), lo), hi);
+    const int ny = (int)floorf(y + 0.5f), nx = (int)floorf(x + 0.5f);
+#pragma unroll
+    for (int k = 0; k < 5; ++k) {
+        const int ty = ny - 2 + k, tx = nx - 2 + k;
+        t.ry[k] = reflect(ty, ps);
+        t.rx[k] = reflect(tx, ps);
+        t.wy[k] = bspline4(y - (float)ty);
+        t.wx[k] = bspline4(x - (float)tx);
+    }
+}
+
+// the 25 taps over coefficients c[row * stride + column]
+__device__ __forceinline__ float spline_at(const float *c, int stride, const Taps &t) {
+    float acc = 0.0f;
+#pragma unroll
+    for (int a = 0; a < 5; ++a) {
+        const float *row = c + t.ry[a] * stride;
+        float r = 0.0f;
+#pragma unroll
+        for (int b = 0; b < 5; ++b) r += t.wx[b] * row[t.rx[b]];
+        acc += t.wy[a] * r;
+    }
+    return acc;
+}
+
+// t of output pixel `item` of sample s: m at patch pixel (my, mx), 0 outside the tile's valid extent
+__device__ __forceinline__ void write_mask(const LabeledArgs &a, const Placement &pl, int s, int my, int mx, int item) {
+    const SampleArgs &g = a.s;
+    const int iy = pl.y0 + my, ix = pl.x0 + mx;
+    const bool inside = iy >= 0 && iy < pl.hv && ix >= 0 && ix < pl.wv;
+    const int tl = g.tile[s];
+    const size_t tile = (tl >= 0 && tl < g.T) ? tl : 0;
+    const uint8_t *src = a.labels + ((tile * g.H + (inside ? iy : 0)) * g.W + (inside ? ix : 0)) * a.K;
+    const size_t plane = (size_t)g.ps * g.ps;
+    float *o = a.t + (size_t)s * (a.map_labels ? 1 : a.K) * plane + item;
+    float sum = 0.0f;
+    for (int k = 0; k < a.K; ++k) {
+        const float v = inside ? (float)src[k] : 0.0f;
+        if (a.map_labels)
+            sum += v;
+        else
+            o[k * plane] = v;
+    }
+    if (a.map_labels) o[0] = sum;
+}
+
+template <int C>
+__global__ void __launch_bounds__(256) labeled_lds_kernel(const LabeledArgs a) {
+    extern __shared__ float plane[];  // [ps][ps | 1]
+    const SampleArgs &g = a.s;
+    const int s = blockIdx.x / C, ch = blockIdx.x - s * C;
+    const int ps = g.ps, stride = ps | 1, tid = threadIdx.x;
+    const Placement pl = placement(g, s);
+    const uint8_t *img = tile_base<C>(g, s);
+    const uint32_t sample = g.sample_base + (uint32_t)s;
+    for (int item = tid; item < ps * ps; item += 256) {
+        const int py = item / ps, px = item - py * ps;
+        float p[C];
+        patch_pixel<C>(g, pl, img, sample, py, px, p);
+        float v = p[0];
+#pragma unroll
+        for (int k = 1; k < C; ++k) v = ch == k ? p[k] : v;
+        plane[py * stride + px] = v;
+    }
+    __syncthreads();
+    if (tid < ps) filter_line(plane + tid * stride, ps, 1);
+    __syncthreads();
+    if (tid < ps) filter_line(plane + tid, ps, stride);
+    __syncthreads();
+    const float ca = g.cosa[s], sa = g.sina[s];
+    float *x = g.out + ((size_t)s * C + ch) * ps * ps;
+    for (int item = tid; item < ps * ps; item += 256) {
+        const int i = item / ps, j = item - i * ps;
+        Taps t;
+        taps_of(ps, ca, sa, i, j, t);
+        x[item] = spline_at(plane, stride, t);
+        if (ch == 0) write_mask(a, pl, s, t.ry[2], t.rx[2], item);
+    }
+}
+
+// one lane per line of the workspace's planes: rows (columns = 0), then columns in a second launch
+__global__ void __launch_bounds__(64) prefilter_global_kernel(float *coef, long lines, int ps, int columns) {
+    const long line = (long)blockIdx.x * 64 + threadIdx.x;
+    if (line >= lines) return;
+    const long plane = line / ps;
+    const int l = (int)(line - plane * ps);
+    filter_line(coef + (size_t)plane * ps * ps + (columns ? (size_t)l : (size_t)l * ps), ps, columns ? ps : 1);
+}
+
+template <int C>
+__global__ void __launch_bounds__(256) labeled_global_kernel(const LabeledArgs a, int strips) {
+    const SampleArgs &g = a.s;
+    const int s = blockIdx.x / strips, strip = blockIdx.x - s * strips;
+    const int ps = g.ps, item = strip * 256 + threadIdx.x;
+    if (item >= ps * ps) return;
+    const int i = item / ps, j = item - i * ps;
+    Taps t;
+    taps_of(ps, g.cosa[s], g.sina[s], i, j, t);
+    const size_t plane = (size_t)ps * ps;
+#pragma unroll
+    for (int ch = 0; ch < C; ++ch)
+        g.out[((size_t)s * C + ch) * plane + item] = spline_at(a.coef + ((size_t)s * C + ch) * plane, ps, t);
+    write_mask(a, placement(g, s), s, t.ry[2], t.rx[2], item);
+}
+
+__global__ void __launch_bounds__(256) mask_rows_kernel(const LabeledArgs a, int strips) {
+    const int s = blockIdx.x / strips, strip = blockIdx.x - s * strips;
+    const int ps = a.s.ps, item = strip * 256 + threadIdx.x;
+    if (item >= ps * ps) return;
+    write_mask(a, placement(a.s, s), s, item / ps, item % ps, item);
+}
+
+template <int C>
+int launch_labeled(const LabeledArgs &a, int n, hipStream_t st) {
+    const int ps = a.s.ps, strips = (ps * ps + 255) / 256;
+    if (!a.s.cosa) {  // x = p, t = m
+        launch<C>(a.s, n, ps % 4 == 0 && ((uintptr_t)a.s.out & 15u) == 0, st);
+        hipLaunchKernelGGL(mask_rows_kernel, dim3((unsigned)(n * strips)), dim3(256), 0, st, a, strips);
+    } else if (ps <= LDS_PS) {
+        const int lds = ps * (ps | 1) * (int)sizeof(float);
+        CAE_TRY(ensure_lds((const void *)labeled_lds_kernel<C>, lds));
+        hipLaunchKernelGGL(labeled_lds_kernel<C>, dim3((unsigned)(n * C)), dim3(256), (size_t)lds, st, a);
+    } else {
+        SampleArgs fill = a.s;  // p into the workspace
+        fill.cosa = fill.sina = nullptr;
+        fill.out = a.coef;
+        launch<C>(fill, n, ps % 4 == 0 && ((uintptr_t)a.coef & 15u) == 0, st);
+        const long lines = (long)n * C * ps;
+        for (int columns = 0; columns < 2; ++columns)
+            hipLaunchKernelGGL(prefilter_global_kernel, dim3((unsigned)((lines + 63) / 64)), dim3(64), 0, st, a.coef, lines, ps,
+                               columns);
+        hipLaunchKernelGGL(labeled_global_kernel<C>, dim3((unsigned)(n * strips)), dim3(256), 0, st, a, strips);
+    }
+    return CAE_OK;
+}
+
+// the argument checks both entry points share; `out` is the image output
+int check_sample_args(const void *pool_dev, int tiles, int h, int w, int c, const int32_t *tile_dev, const int32_t *y0_dev,
+                      const int32_t *x0_dev, const int32_t *tile_host, const float *cos_dev, const float *sin_dev,
+                      float noise_std, int n, int ps, const void *out_dev) {
     if (c < 1 || c > 4) return fail(CAE_ERR_ARG, "1 to 4 channels per pixel, got %d", c);
     if (ps < 1 || ps > 16384) return fail(CAE_ERR_ARG, "patch size %d outside 1 .. 16384", ps);
     if (n < 0) return fail(CAE_ERR_ARG, "n = %d", n);
@@ -244,9 +470,14 @@ extern "C" int cae_t_sample_patches(const uint8_t *pool_dev, int tiles, int h, i
         for (int s = 0; s < n; ++s)
             if (tile_host[s] < 0 || tile_host[s] >= tiles)
                 return fail(CAE_ERR_ARG, "sample %d names tile %d of %d", s, tile_host[s], tiles);
-    if (n == 0) return CAE_OK;
     const long strips = cos_dev ? ((long)ps * ps + 255) / 256 : ((long)ps * ((ps + 3) / 4) + 255) / 256;
     if ((long)n * strips > 0x7fffffffL) return fail(CAE_ERR_ARG, "%d patches of %d^2 in one call: split the batch", n, ps);
+    return CAE_OK;
+}
+
+SampleArgs sample_args(const uint8_t *pool_dev, int tiles, int h, int w, const int32_t *tile_hw_dev, const int32_t *tile_dev,
+                       const int32_t *y0_dev, const int32_t *x0_dev, const float *cos_dev, const float *sin_dev,
+                       uint64_t seed, uint32_t sample_base, float noise_std, int normalize, int ps, float *out_dev) {
     SampleArgs a{};
     a.pool = pool_dev;
     a.tile_hw = tile_hw_dev;
@@ -257,6 +488,21 @@ extern "C" int cae_t_sample_patches(const uint8_t *pool_dev, int tiles, int h, i
     a.key0 = (uint32_t)seed, a.key1 = (uint32_t)(seed >> 32), a.sample_base = sample_base;
     a.noise_std = noise_std;
     a.normalize = normalize != 0;
+    return a;
+}
+
+}  // namespace
+
+extern "C" int cae_t_sample_patches(const uint8_t *pool_dev, int tiles, int h, int w, int c, const int32_t *tile_hw_dev,
+                                    const int32_t *tile_dev, const int32_t *y0_dev, const int32_t *x0_dev,
+                                    const int32_t *tile_host, const float *cos_dev, const float *sin_dev, uint64_t seed,
+                                    uint32_t sample_base, float noise_std, int normalize, int n, int ps, float *out_dev,
+                                    void *stream) {
+    CAE_TRY(check_sample_args(pool_dev, tiles, h, w, c, tile_dev, y0_dev, x0_dev, tile_host, cos_dev, sin_dev, noise_std, n,
+                              ps, out_dev));
+    if (n == 0) return CAE_OK;
+    const SampleArgs a = sample_args(pool_dev, tiles, h, w, tile_hw_dev, tile_dev, y0_dev, x0_dev, cos_dev, sin_dev, seed,
+                                     sample_base, noise_std, normalize, ps, out_dev);
     const bool vec = ps % 4 == 0 && ((uintptr_t)out_dev & 15u) == 0;
     hipStream_t st = (hipStream_t)stream;
     switch (c) {
@@ -264,6 +510,44 @@ extern "C" int cae_t_sample_patches(const uint8_t *pool_dev, int tiles, int h, i
         case 2: launch<2>(a, n, vec, st); break;
         case 3: launch<3>(a, n, vec, st); break;
         default: launch<4>(a, n, vec, st); break;
+    }
+    HIP_TRY(hipGetLastError());
+    return CAE_OK;
+}
+
+extern "C" int cae_t_sample_labeled_patches(const uint8_t *pool_dev, const uint8_t *labels_dev, int tiles, int h, int w, int c,
+                                            int k, const int32_t *tile_hw_dev, const int32_t *tile_dev,
+                                            const int32_t *y0_dev, const int32_t *x0_dev, const int32_t *tile_host,
+                                            const float *cos_dev, const float *sin_dev, uint64_t seed, uint32_t sample_base,
+                                            float noise_std, int normalize, int map_labels, int n, int ps,
+                                            void *workspace_dev, size_t workspace_bytes, float *x_dev, float *t_dev,
+                                            void *stream) {
+    if (k < 1 || k > 4) return fail(CAE_ERR_ARG, "1 to 4 label channels per pixel, got %d", k);
+    if (!labels_dev || !t_dev) return fail(CAE_ERR_ARG, "NULL argument");
+    CAE_TRY(check_sample_args(pool_dev, tiles, h, w, c, tile_dev, y0_dev, x0_dev, tile_host, cos_dev, sin_dev, noise_std, n,
+                              ps, x_dev));
+    // grids: n strips of 256 pixels (mask, global evaluation), n c planes, n c ps lines in blocks of 64
+    if ((long)n * (((long)ps * ps + 255) / 256) > 0x7fffffffL || (long)n * c > 0x7fffffffL ||
+        (long)n * c * ps > 0x7fffffffL * 64)
+        return fail(CAE_ERR_ARG, "%d patches of %d^2 in one call: split the batch", n, ps);
+    const size_t need = cos_dev && ps > LDS_PS ? (size_t)n * c * ps * ps * sizeof(float) : 0;
+    if (need && (!workspace_dev || workspace_bytes < need))
+        return fail(CAE_ERR_ARG, "the workspace holds %zu bytes, %d patches of %d x %d^2 need %zu",
+                    workspace_dev ? workspace_bytes : (size_t)0, n, c, ps, need);
+    if (n == 0) return CAE_OK;
+    LabeledArgs a{};
+    a.s = sample_args(pool_dev, tiles, h, w, tile_hw_dev, tile_dev, y0_dev, x0_dev, cos_dev, sin_dev, seed, sample_base,
+                      noise_std, normalize, ps, x_dev);
+    a.labels = labels_dev;
+    a.t = t_dev;
+    a.coef = (float *)workspace_dev;
+    a.K = k, a.map_labels = map_labels != 0;
+    hipStream_t st = (hipStream_t)stream;
+    switch (c) {
+        case 1: CAE_TRY(launch_labeled<1>(a, n, st)); break;
+        case 2: CAE_TRY(launch_labeled<2>(a, n, st)); break;
+        case 3: CAE_TRY(launch_labeled<3>(a, n, st)); break;
+        default: CAE_TRY(launch_labeled<4>(a, n, st)); break;
     }
     HIP_TRY(hipGetLastError());
     return CAE_OK;

@@ -7,6 +7,11 @@ that writes the fp32 NCHW batch ``train.train_step`` takes.  The random draws (t
 torchvision's policies; the per-pixel work, the Gaussian noise included (a counter-based Philox4x32-10 stream), is the
 kernel's.
 
+``LabeledPatchSampler`` stands where the same transform stands with ``label_density == 2`` (_augs.py:52-82, 240-299):
+image and pixel labels under one crop and one rotation, ``scipy.ndimage.rotate`` with reflected edges (spline order 4 on
+the image, nearest neighbour on the mask), in ``cae_t_sample_labeled_patches``; its batches ``(x, t)`` are what
+``seg_train.train_step`` takes.
+
 Under several ranks every rank builds its own sampler and passes ``draw`` / ``sample`` a generator seeded per rank (and
 a per-rank ``seed`` for the noise): the sampler itself shares nothing between ranks.
 """
@@ -51,6 +56,31 @@ def philox_normals(seed: int, sample: np.ndarray, pixel: np.ndarray) -> np.ndarr
         out[..., 2 * pair] = r * np.cos(2.0 * np.pi * u[2 * pair + 1])
         out[..., 2 * pair + 1] = r * np.sin(2.0 * np.pi * u[2 * pair + 1])
     return out
+
+
+def _zarr_tiles(stores, group: str):
+    """Every chunk of the ``group`` array (Y, X, C uint8; or Y, X) of each store as one tile, padded to the chunk shape:
+    ``(tiles, valid (rows, columns) per tile, [(Y, X) shape and chunks per store])``."""
+    from .zarrio import ZarrArray
+    tiles, hw, shape, geometry = [], [], None, []
+    for store in ([stores] if isinstance(stores, str) else stores):
+        arr = ZarrArray.open(store, group)
+        if len(arr.shape) not in (2, 3) or arr.dtype != np.uint8:
+            raise ValueError(f'{store}: expected a uint8 (Y, X, C) or (Y, X) array, got {arr.dtype} {arr.shape}')
+        if len(arr.shape) == 3 and arr.chunks[2] != arr.shape[2]:
+            raise ValueError(f'{store}: chunks must hold all channels of a pixel')
+        if shape is None:
+            shape = arr.chunks
+        elif arr.chunks != shape:
+            raise ValueError(f'{store}: chunk shape {arr.chunks} differs from {shape}; tiles must be of equal shape')
+        geometry.append((tuple(arr.shape[:2]), tuple(arr.chunks[:2])))
+        for idx in arr.chunk_indices():
+            data = arr[arr.chunk_slices(idx)]
+            hw.append(data.shape[:2])
+            tiles.append(arr.pad_chunk(data))
+    if not tiles:
+        raise ValueError('no store given')
+    return tiles, hw, geometry
 
 
 class PatchSampler:
@@ -113,24 +143,7 @@ class PatchSampler:
         """A sampler over every chunk of the ``data_group`` array (Y, X, C uint8; or Y, X) of each store, read through
         ``ZarrArray.__getitem__``.  One tile per chunk: all stores share one chunk shape; the chunks on the lower and
         right edges of an image are padded to it (``ZarrArray.pad_chunk``) and keep their valid size."""
-        from .zarrio import ZarrArray
-        tiles, hw, shape = [], [], None
-        for store in ([stores] if isinstance(stores, str) else stores):
-            arr = ZarrArray.open(store, data_group)
-            if len(arr.shape) not in (2, 3) or arr.dtype != np.uint8:
-                raise ValueError(f'{store}: expected a uint8 (Y, X, C) or (Y, X) array, got {arr.dtype} {arr.shape}')
-            if len(arr.shape) == 3 and arr.chunks[2] != arr.shape[2]:
-                raise ValueError(f'{store}: chunks must hold all channels of a pixel')
-            if shape is None:
-                shape = arr.chunks
-            elif arr.chunks != shape:
-                raise ValueError(f'{store}: chunk shape {arr.chunks} differs from {shape}; tiles must be of equal shape')
-            for idx in arr.chunk_indices():
-                data = arr[arr.chunk_slices(idx)]
-                hw.append(data.shape[:2])
-                tiles.append(arr.pad_chunk(data))
-        if not tiles:
-            raise ValueError('no store given')
+        tiles, hw, _ = _zarr_tiles(stores, data_group)
         return cls(np.stack(tiles), patch_size, tile_hw=np.asarray(hw, dtype=np.int32), **kwargs)
 
     # ---- host: the random draws --------------------------------------------------------------------------------------
@@ -157,8 +170,12 @@ class PatchSampler:
                                 for row in dims.tolist()], dtype=torch.int64).reshape(n, 2)
         angle = None
         if self.rotation:
-            angle = (torch.rand(n, generator=generator, dtype=torch.float64) * 2.0 - 1.0) * self.degrees
+            angle = self._draw_angle(n, generator)
         return tile.to(torch.int32), off[:, 0].to(torch.int32).contiguous(), off[:, 1].to(torch.int32).contiguous(), angle
+
+    def _draw_angle(self, n: int, generator) -> torch.Tensor:
+        """torchvision's RandomRotation: uniform in [-degrees, degrees]"""
+        return (torch.rand(n, generator=generator, dtype=torch.float64) * 2.0 - 1.0) * self.degrees
 
     # ---- device: the batch -------------------------------------------------------------------------------------------
     def _device_pool(self):
@@ -167,11 +184,9 @@ class PatchSampler:
             self._dev = (self.pool.to(dev), self.tile_hw.to(dev) if self._ragged else None)
         return self._dev
 
-    def gather(self, tile, y0, x0, angle=None, noise_seed: Optional[int] = None, sample_base: int = 0) -> torch.Tensor:
-        """The ``[n, C, ps, ps]`` fp32 batch of the given draw on the device.  ``angle`` in degrees (None: no rotation).
-        ``noise_seed`` keys the noise of this batch (None: the sampler's ``seed``); it is used with ``add_noise`` only.
-        ``sample_base`` is the index of the batch's first sample in the noise stream, so a batch can be gathered in
-        parts.  A tile index outside the pool raises ValueError before anything is launched."""
+    def _gather_args(self, tile, y0, x0, angle, noise_seed):
+        """the arguments of ``gather`` as the entry points take them: int32 host vectors, ``n``, cos / sin ([2, n] float32
+        or None), the noise seed and the noise's standard deviation"""
         tile, y0, x0 = (torch.as_tensor(v).to(torch.int32).cpu().reshape(-1).contiguous() for v in (tile, y0, x0))
         n = tile.numel()
         if y0.numel() != n or x0.numel() != n:
@@ -184,6 +199,14 @@ class PatchSampler:
             cs = torch.stack([torch.cos(a), torch.sin(a)]).to(torch.float32)  # float64 on the host, rounded once
         seed = self.seed if noise_seed is None else int(noise_seed) & _M64
         std = self.noise_std if self.add_noise else 0.0
+        return tile, y0, x0, n, cs, seed, std
+
+    def gather(self, tile, y0, x0, angle=None, noise_seed: Optional[int] = None, sample_base: int = 0) -> torch.Tensor:
+        """The ``[n, C, ps, ps]`` fp32 batch of the given draw on the device.  ``angle`` in degrees (None: no rotation).
+        ``noise_seed`` keys the noise of this batch (None: the sampler's ``seed``); it is used with ``add_noise`` only.
+        ``sample_base`` is the index of the batch's first sample in the noise stream, so a batch can be gathered in
+        parts.  A tile index outside the pool raises ValueError before anything is launched."""
+        tile, y0, x0, n, cs, seed, std = self._gather_args(tile, y0, x0, angle, noise_seed)
         if self.force_torch:
             g = self.torch_normals(n, seed, int(sample_base)) if std != 0.0 else None
             return self._gather_torch(tile, y0, x0, cs, std, g)
@@ -255,3 +278,187 @@ class PatchSampler:
         for _ in range(self.steps_per_epoch):
             x = self.sample(self.batch_size)
             yield x, x
+
+
+# ---- labelled patches: image and mask under one crop and one rotation ------------------------------------------------
+# the poles and the gain of the quartic B-spline's inverse filter (contract: include/cae_hip.h, cae_t_sample_labeled_patches)
+_SPLINE_POLES = (math.sqrt(664.0 - math.sqrt(438976.0)) + math.sqrt(304.0) - 19.0,
+                 math.sqrt(664.0 + math.sqrt(438976.0)) - math.sqrt(304.0) - 19.0)
+_SPLINE_GAIN = math.prod((1.0 - z) * (1.0 - 1.0 / z) for z in _SPLINE_POLES)
+_LDS_PATCH = 128  # the entry point needs a workspace for rotated patches larger than this
+
+
+def _spline_prefilter(c: np.ndarray) -> np.ndarray:
+    """force_torch: the interpolation coefficients along the last axis of float64 ``c``, every line at once"""
+    c = c * _SPLINE_GAIN
+    n = c.shape[-1]
+    for z in _SPLINE_POLES:
+        zn = z ** n
+        mirrored = c[..., ::-1]
+        acc = c[..., 0] + zn * mirrored[..., 0]
+        if n > 1:
+            acc = acc + ((c[..., 1:] + zn * mirrored[..., 1:]) * z ** np.arange(1, n)).sum(-1)
+        c[..., 0] += z / (1.0 - zn * zn) * acc
+        for i in range(1, n):
+            c[..., i] += z * c[..., i - 1]
+        c[..., n - 1] *= z / (z - 1.0)
+        for i in range(n - 2, -1, -1):
+            c[..., i] = z * (c[..., i + 1] - c[..., i])
+    return c
+
+
+def _spline_weight(d: np.ndarray) -> np.ndarray:
+    d = np.abs(d)
+    return np.where(d < 0.5, d * d * (d * d / 4.0 - 5.0 / 8.0) + 115.0 / 192.0,
+                    np.where(d < 1.5, d * (d * (d * (5.0 / 6.0 - d / 6.0) - 5.0 / 4.0) + 5.0 / 24.0) + 55.0 / 96.0,
+                             np.where(d < 2.5, (d - 2.5) ** 4 / 24.0, 0.0)))
+
+
+def _reflect(idx: np.ndarray, n: int) -> np.ndarray:
+    m = np.mod(idx, 2 * n)
+    return np.where(m >= n, 2 * n - 1 - m, m)
+
+
+class LabeledPatchSampler(PatchSampler):
+    """Pairs of an image patch and its pixel labels: ``PatchSampler`` over ``pool`` plus ``labels``, uint8 ``[T, H, W, K]``
+    (``[T, H, W]``: one channel), 1 <= K <= 4, of the pool's ``T, H, W``.  Image and mask share tile, crop window, ragged
+    extent (``tile_hw``) and angle; the kernel call is ``cae_t_sample_labeled_patches`` (contract in include/cae_hip.h).
+
+    Stands where ``get_zarr_transform`` with ``label_density == 2`` stands.  What differs from the unlabelled sampler is
+    the reference's own difference: ``rotation`` turns the pair by an angle uniform in [0, degrees) (not symmetric;
+    ``RandomRotationInputTarget``), the image through the exactly interpolating quartic B-spline and the mask through its
+    nearest neighbour, both with reflected edges.  ``map_labels`` sums the K label channels into one (``MapLabels``);
+    ``target_data_type`` is ``torch.float32`` or ``torch.int64`` (``ConvertTensorDtype``: a cast of the exact integer
+    values).  ``force_torch=True`` computes the same contract in float64 on the host and uploads it: a comparison path
+    that nothing but this flag selects.
+
+    Iterating yields ``steps_per_epoch`` batches ``(x, t)``: ``x`` fp32 ``[n, C, ps, ps]`` and ``t`` ``[n, Kt, ps, ps]``
+    (``Kt`` = 1 with ``map_labels``, else K), what ``seg_train.train_step`` and ``SegLoss('BCELoss')`` take; an int64 ``t``
+    with ``Kt`` = 1 is yielded as ``[n, ps, ps]``, the class map ``SegLoss('CELoss')`` takes.
+    """
+
+    def __init__(self, pool, labels, patch_size: int, data_mode: str = 'train', add_noise: bool = False,
+                 noise_std: float = 0.001, normalize: bool = False, rotation: bool = False, degrees: float = 30.0,
+                 seed: int = 0, force_torch: bool = False, tile_hw=None, batch_size: int = 16,
+                 steps_per_epoch: Optional[int] = None, map_labels: bool = False, target_data_type=torch.float32):
+        if target_data_type not in (torch.float32, torch.int64):
+            raise ValueError('Convertion to data type {} not supported'.format(target_data_type))
+        super().__init__(pool, patch_size, data_mode=data_mode, add_noise=add_noise, noise_std=noise_std, normalize=normalize,
+                         rotation=rotation, degrees=degrees, seed=seed, force_torch=force_torch, tile_hw=tile_hw,
+                         batch_size=batch_size, steps_per_epoch=steps_per_epoch)
+        labels = torch.as_tensor(labels)
+        if labels.dim() == 3:
+            labels = labels[..., None]
+        if labels.dim() != 4 or labels.dtype != torch.uint8:
+            raise ValueError(f'the labels are uint8 [T, H, W, K], got {labels.dtype} {tuple(labels.shape)}')
+        if tuple(labels.shape[:3]) != (self.T, self.H, self.W):
+            raise ValueError(f'the labels {tuple(labels.shape[:3])} do not match the pool {(self.T, self.H, self.W)}')
+        if not 1 <= labels.shape[3] <= 4:
+            raise ValueError(f'1 to 4 label channels, got {labels.shape[3]}')
+        self.labels = labels.to(self.pool.device).contiguous()
+        self.K = int(labels.shape[3])
+        self.map_labels = bool(map_labels)
+        self.Kt = 1 if self.map_labels else self.K
+        self.target_data_type = target_data_type
+        self._labels_dev = None
+
+    @classmethod
+    def from_zarr(cls, stores: Sequence[str], data_group: str = '0/0', labels_data_group: str = 'labels/0/0',
+                  patch_size: int = 128, **kwargs) -> 'LabeledPatchSampler':
+        """``PatchSampler.from_zarr`` for both arrays of each store: the image (Y, X, C) under ``data_group`` and the
+        labels (Y, X, K; or Y, X) under ``labels_data_group``, both read through ``ZarrArray``.  The two arrays of a store
+        must agree in Y / X shape and chunking (ValueError otherwise), so a chunk of one is the tile of the other; ragged
+        edge tiles keep their valid size for both."""
+        tiles, hw, geometry = _zarr_tiles(stores, data_group)
+        masks, mask_hw, mask_geometry = _zarr_tiles(stores, labels_data_group)
+        for store, g, mg in zip([stores] if isinstance(stores, str) else stores, geometry, mask_geometry):
+            if g != mg:
+                raise ValueError(f'{store}: image {data_group} has (Y, X) shape and chunks {g}, labels {labels_data_group} '
+                                 f'have {mg}; the two must agree')
+        assert hw == mask_hw
+        return cls(np.stack(tiles), np.stack(masks), patch_size, tile_hw=np.asarray(hw, dtype=np.int32), **kwargs)
+
+    def _draw_angle(self, n: int, generator) -> torch.Tensor:
+        """RandomRotationInputTarget: ``np.random.rand() * degrees``, uniform in [0, degrees)"""
+        return torch.rand(n, generator=generator, dtype=torch.float64) * self.degrees
+
+    def workspace_bytes(self, n: int, rotated: bool) -> int:
+        """the scratch ``cae_t_sample_labeled_patches`` needs for ``n`` patches (its contract's formula)"""
+        ps = self.patch_size
+        return int(n) * self.C * ps * ps * 4 if rotated and ps > _LDS_PATCH else 0
+
+    def gather(self, tile, y0, x0, angle=None, noise_seed: Optional[int] = None, sample_base: int = 0):
+        """``(x, t)`` of the given draw on the device: ``x`` fp32 ``[n, C, ps, ps]``, ``t`` ``[n, Kt, ps, ps]`` in
+        ``target_data_type``.  The arguments are those of ``PatchSampler.gather``; one ``angle`` turns image and mask."""
+        tile, y0, x0, n, cs, seed, std = self._gather_args(tile, y0, x0, angle, noise_seed)
+        ps = self.patch_size
+        if self.force_torch:
+            g = self.torch_normals(n, seed, int(sample_base)) if std != 0.0 else None
+            x, t = self._gather_host(tile, y0, x0, cs, std, g)
+            return x, t.to(self.target_data_type)
+        pool, tile_hw = self._device_pool()
+        if self._labels_dev is None:
+            self._labels_dev = self.labels.to(pool.device)
+        idx = torch.stack([tile, y0, x0]).to(pool.device)
+        cs_dev = cs.to(pool.device) if cs is not None else None
+        x = torch.empty((n, self.C, ps, ps), dtype=torch.float32, device=pool.device)
+        t = torch.empty((n, self.Kt, ps, ps), dtype=torch.float32, device=pool.device)
+        ws_bytes = self.workspace_bytes(n, cs is not None)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=pool.device) if ws_bytes else None
+        with torch.cuda.device(pool.device):
+            _lib.check(_lib.lib().cae_t_sample_labeled_patches(
+                pool.data_ptr(), self._labels_dev.data_ptr(), self.T, self.H, self.W, self.C, self.K,
+                tile_hw.data_ptr() if tile_hw is not None else None, idx[0].data_ptr(), idx[1].data_ptr(), idx[2].data_ptr(),
+                tile.data_ptr(), cs_dev[0].data_ptr() if cs is not None else None,
+                cs_dev[1].data_ptr() if cs is not None else None, seed, int(sample_base) & 0xFFFFFFFF, std,
+                int(self.normalize), int(self.map_labels), n, ps, ws.data_ptr() if ws is not None else None, ws_bytes,
+                x.data_ptr(), t.data_ptr(), _lib.stream_ptr()))
+        return x, t.to(self.target_data_type)
+
+    def _gather_host(self, tile, y0, x0, cs, std, g):
+        """The contract in float64 numpy on the host, uploaded as float32 to the pool's device.  The patch ``p`` is
+        ``PatchSampler``'s torch form; the label window is gathered the same way."""
+        n, ps, dev = tile.numel(), self.patch_size, self.pool.device
+        p = self._gather_torch(tile, y0, x0, None, std, g)  # [n, C, ps, ps] float32: p of the contract
+        t_ = tile.to(dev).long()
+        r = torch.arange(ps, device=dev)
+        iy, ix = y0.to(dev).long()[:, None] + r, x0.to(dev).long()[:, None] + r
+        hw = self.tile_hw.to(dev).long()[t_]
+        vy, vx = (iy >= 0) & (iy < hw[:, :1]), (ix >= 0) & (ix < hw[:, 1:])
+        m = self.labels[t_[:, None, None], iy.clamp(0, self.H - 1)[:, :, None], ix.clamp(0, self.W - 1)[:, None, :]]
+        m = torch.where((vy[:, :, None] & vx[:, None, :])[..., None], m, torch.zeros((), dtype=m.dtype, device=dev))
+        m = m.permute(0, 3, 1, 2).to(torch.float32)
+        if self.map_labels:
+            m = m.sum(dim=1, keepdim=True)
+        if cs is None:
+            return p, m.contiguous()
+        coef = _spline_prefilter(p.cpu().numpy().astype(np.float64))                # rows
+        coef = _spline_prefilter(coef.swapaxes(-1, -2).copy()).swapaxes(-1, -2)     # columns
+        mask = m.cpu().numpy()
+        c = (ps - 1) / 2.0
+        i, j = np.meshgrid(np.arange(ps, dtype=np.float64), np.arange(ps, dtype=np.float64), indexing='ij')
+        x_out, t_out = np.zeros((n, self.C, ps, ps)), np.empty((n, self.Kt, ps, ps), dtype=np.float32)
+        for s in range(n):
+            ca, sa = float(cs[0, s]), float(cs[1, s])
+            y, x = ca * (i - c) + sa * (j - c) + c, -sa * (i - c) + ca * (j - c) + c
+            ny, nx = np.floor(y + 0.5).astype(np.int64), np.floor(x + 0.5).astype(np.int64)
+            t_out[s] = mask[s][:, _reflect(ny, ps), _reflect(nx, ps)]
+            for a in range(5):
+                wy, ry = _spline_weight(y - (ny - 2 + a)), _reflect(ny - 2 + a, ps)
+                for b in range(5):
+                    x_out[s] += wy * _spline_weight(x - (nx - 2 + b)) * coef[s][:, ry, _reflect(nx - 2 + b, ps)]
+        return torch.from_numpy(x_out.astype(np.float32)).to(dev), torch.from_numpy(t_out).to(dev)
+
+    def sample(self, n: int, generator: Optional[torch.Generator] = None):
+        """``draw`` then ``gather`` -> ``(x, t)``; every call takes the next per-batch noise seed."""
+        tile, y0, x0, angle = self.draw(n, generator)
+        pair = self.gather(tile, y0, x0, angle, noise_seed=self.batch_seed(self._batch))
+        self._batch += 1
+        return pair
+
+    def __iter__(self):
+        if self.data_mode == 'test':
+            self._next_tile = 0
+        for _ in range(self.steps_per_epoch):
+            x, t = self.sample(self.batch_size)
+            yield x, (t[:, 0] if self.Kt == 1 and self.target_data_type == torch.int64 else t)

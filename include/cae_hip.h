@@ -474,6 +474,66 @@ int cae_t_sample_patches(const uint8_t *pool_dev, int tiles, int h, int w, int c
                          const float *cos_dev, const float *sin_dev, uint64_t seed, uint32_t sample_base, float noise_std,
                          int normalize, int n, int ps, float *out_dev, void *stream);
 
+/* ---- training input with pixel labels: image and mask under one crop and one rotation (csrc/cae_sampler.hip) ---------
+ * Replaces the pair transform of utils/datasets/_augs.py:52-82, 240-299 (get_zarr_transform with label_density == 2:
+ * the transforms above, then RandomRotationInputTarget(30) = scipy.ndimage.rotate(reshape=False, mode='reflect') with
+ * spline order 4 on the image and order 0 on the mask, and MapLabels).  One call writes both batches seg_train's
+ * train_step takes.
+ *
+ * Inputs.  Everything of the entry point above, with the same meaning, and:
+ *   labels_dev      uint8 [tiles][h][w][k] on the device, 1 <= k <= 4: the label pool.  It shares the tile geometry of
+ *                   the image pool (tile_hw_dev, tile, y0, x0 address both).
+ *   map_labels      1: the k channels are summed into one (MapLabels); 0: they stay apart.  kt = map_labels ? 1 : k.
+ *   workspace_dev, workspace_bytes   device scratch of at least
+ *                       (cos_dev != NULL && ps > 128) ? n * c * ps * ps * sizeof(float) : 0
+ *                   bytes (NULL / 0 where that is 0).  What it holds before the call does not matter.
+ *   x_dev           float [n][c][ps][ps];   t_dev   float [n][kt][ps][ps].
+ *
+ * Patch p.  Exactly the p of the contract above: the crop window (y0, x0), u8 / 255 correctly rounded, the Philox noise
+ * keyed by (seed, sample_base + sample index, py * ps + px), clamp, normalisation, 0 (-1 after normalisation) outside the
+ * tile's valid extent.  (The kernels call the same code.)
+ * Mask patch m.  The same window of the label pool as float values, 0 outside the valid extent; with map_labels the sum
+ * over the k channels (summing commutes with nearest-neighbour sampling).
+ * No rotation (cos_dev == sin_dev == NULL).  x = p bit for bit and t = m exactly.
+ * Rotation, about cc = (ps - 1) / 2.  Output pixel (i, j) (row, column) reads the source point
+ *     y =  cos a * (i - cc) + sin a * (j - cc) + cc
+ *     x = -sin a * (i - cc) + cos a * (j - cc) + cc
+ * (the same turn as above: a positive angle is counter-clockwise as displayed).  Every row or column index q that follows
+ * is reflected half-sample symmetrically, as often as needed (d c b a | a b c d | d c b a):
+ *     refl(q) = r < ps ? r : 2 ps - 1 - r,  r = q mod 2 ps  (0 <= r < 2 ps).
+ * Repeated reflection matters where ps is smaller than the tap support.  There is no zero fill.
+ *   Mask.   t = m[refl(floor(y + 0.5))][refl(floor(x + 0.5))].
+ *   Image.  x = sum over a, b = 0..4 of w(y - (ys + a)) w(x - (xs + b)) coef[refl(ys + a)][refl(xs + b)], with
+ *           ys = floor(y + 0.5) - 2, xs = floor(x + 0.5) - 2 and the quartic B-spline
+ *               w(d) = d^2 (d^2 / 4 - 5 / 8) + 115 / 192                              |d| < 0.5
+ *                      |d| (|d| (|d| (5 / 6 - |d| / 6) - 5 / 4) + 5 / 24) + 55 / 96   |d| < 1.5
+ *                      (|d| - 2.5)^4 / 24                                             |d| < 2.5,  else 0.
+ *           There is no clipping afterwards: the spline overshoots, as the reference's does.
+ *   coef.   The interpolation coefficients of each channel plane of p: every row is filtered, then every column.  A line
+ *           c[0..n-1] (n = ps) is scaled by the gain, the product over both poles of (1 - z)(1 - 1 / z) (= 384), and then,
+ *           for z1 = sqrt(664 - sqrt(438976)) + sqrt(304) - 19 and after it z2 = sqrt(664 + sqrt(438976)) - sqrt(304) - 19:
+ *               c[0]   = c0 + z / (1 - z^(2n)) * (c0 + z^n c[n-1] + sum_{i=1..n-1} z^i (c[i] + z^n c[n-1-i])),  c0 = c[0]
+ *               c[i]  += z c[i-1]                 i = 1 .. n-1
+ *               c[n-1] *= z / (z - 1)
+ *               c[i]   = z (c[i+1] - c[i])        i = n-2 .. 0.
+ *           This start is the exact one for the reflected line, so the spline interpolates: at angle 0, x = p up to
+ *           rounding for every ps >= 1.  scipy's own result parts from this form below about 12 pixels per side (by
+ *           about |z1|^(2n): 3e-3 at n = 2, 5e-8 at n = 8); the contract is the exact form.  The kernels work in float32
+ *           and drop terms of the start that are below float32 resolution (z^i from i = 28, z^n from n = 64).
+ * Results are bitwise repeatable, independent of the launch shape and of what x_dev, t_dev and the workspace held, and
+ * independent of how a batch is split over calls by sample_base.
+ *
+ * CAE_ERR_ARG before any launch: everything the entry point above refuses (with x_dev as its out_dev), k outside 1..4, a
+ * NULL labels_dev or t_dev, and a workspace that is NULL or smaller than the size above where that size is not 0 (the
+ * message names the bytes needed).  No device-side value faults here either: tiles, offsets and tile_hw are treated as
+ * above, and cos / sin that are NaN or huge are clamped as source coordinates to [-ps, 2 ps] before any integer cast. */
+int cae_t_sample_labeled_patches(const uint8_t *pool_dev, const uint8_t *labels_dev, int tiles, int h, int w, int c, int k,
+                                 const int32_t *tile_hw_dev, const int32_t *tile_dev, const int32_t *y0_dev,
+                                 const int32_t *x0_dev, const int32_t *tile_host, const float *cos_dev, const float *sin_dev,
+                                 uint64_t seed, uint32_t sample_base, float noise_std, int normalize, int map_labels, int n,
+                                 int ps, void *workspace_dev, size_t workspace_bytes, float *x_dev, float *t_dev,
+                                 void *stream);
+
 /* compressai NonNegativeParametrizer (GDN beta / gamma; layers/gdn.py via _autoencoders.py GDN units) under autograd:
  * out = max(x, bound)^2 - pedestal;  g_x = g 2 max(x, bound) where x >= bound or that value is negative (LowerBound rule). */
 int cae_t_reparam_forward(const float *x, long n, float bound, float pedestal, float *out, void *stream);

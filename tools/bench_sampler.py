@@ -16,6 +16,11 @@ Columns: plain, noise only (std 0.001), rotation only (+-30 degrees), both.  Per
   cpu      patches/s of the float32 torch-CPU transform, one patch at a time as the reference's dataset does it (crop,
            / 255, + randn * std, clip, normalise, affine_grid + grid_sample), on 16 threads: 16 workers of one thread
            each, and one worker with 16 intra-op threads.
+Labelled columns (key 'labeled'; cae_t_sample_labeled_patches through LabeledPatchSampler.gather, a label pool of K = 2
+with the image pool): batches of 128 and 16 patches of 3 x 128^2 (planes filtered in LDS) and 3 x 256^2 (the global-memory
+variant), plain and rotated, the same measurement rule (HIP events around gather, median of --steps after --warmup).  Next
+to each, the unlabelled PatchSampler.gather of the same batch -- for rotation the bilinear sample_rotate_kernel, the
+yardstick the labelled path is reported against -- and the ratio of the two.  --labeled-only measures nothing else.
 Prints one JSON line (and writes it to --out).  There is no CPU path for the first two: without a GPU this fails.
 """
 import argparse
@@ -87,6 +92,22 @@ def measure_device(pool, n, steps, warmup, train_ms, kernel_only=False):
     return out
 
 
+def measure_labeled(pool, labels, n, ps, steps, warmup):
+    from cnn_autoencoder_amd.sampler import LabeledPatchSampler, PatchSampler
+    out = {}
+    for name, rotation in (('plain', False), ('rotation', True)):
+        kw = dict(normalize=True, rotation=rotation, seed=1)
+        s, u = LabeledPatchSampler(pool, labels, ps, **kw), PatchSampler(pool, ps, **kw)
+        tile, y0, x0, angle = s.draw(n, torch.Generator().manual_seed(n))
+        row = dict(labeled=device_ms(lambda: s.gather(tile, y0, x0, angle), steps, warmup),
+                   unlabeled=device_ms(lambda: u.gather(tile, y0, x0, angle), steps, warmup))
+        row['labeled_over_unlabeled'] = row['labeled']['median_ms'] / row['unlabeled']['median_ms']
+        out[name] = row
+        print('labeled', n, ps, name, {k: round(v['median_ms'], 4) for k, v in row.items() if isinstance(v, dict)},
+              round(row['labeled_over_unlabeled'], 2), file=sys.stderr)
+    return out
+
+
 def cpu_patch(pool, tile, y0, x0, angle, noise):
     """one patch as the reference's transform makes it (the offsets here lie inside the tile)"""
     x = pool[tile, y0:y0 + PS, x0:x0 + PS].permute(2, 0, 1).to(torch.float32).div(255)
@@ -131,6 +152,7 @@ def main():
     ap.add_argument('--out')
     ap.add_argument('--no-cpu', action='store_true')
     ap.add_argument('--kernel-only', action='store_true', help='the kernel columns only (for a kernel trace)')
+    ap.add_argument('--labeled-only', action='store_true', help='the labelled columns only')
     args = ap.parse_args()
     assert torch.cuda.is_available(), 'this benchmark measures an MI355X; there is no CPU path'
     train_ms = {}
@@ -142,9 +164,12 @@ def main():
     pool = pool_cpu.cuda()
     res = dict(device=torch.cuda.get_device_name(0), steps=args.steps, warmup=args.warmup, tiles=TILES, tile=TILE, patch=PS,
                channels=C, normalize=True, noise_std=0.001, degrees=30.0, train_step_ms=train_ms)
-    for n in (128, 16):
+    labels = torch.from_numpy(np.random.default_rng(1).integers(0, 2, (TILES, TILE, TILE, 2), dtype=np.uint8)).cuda()
+    res['labeled'] = {f'batch{n}_patch{ps}': measure_labeled(pool, labels, n, ps, args.steps, args.warmup)
+                      for n in (128, 16) for ps in (128, 256)}
+    for n in () if args.labeled_only else (128, 16):
         res[f'batch{n}'] = measure_device(pool, n, args.steps, args.warmup, train_ms, args.kernel_only)
-    if not args.kernel_only:
+    if not (args.kernel_only or args.labeled_only):
         res['kernel_faster_than_torch_at_128'] = all(v['kernel_faster_than_torch'] for v in res['batch128'].values())
         if not args.no_cpu:
             res['cpu'] = measure_cpu(pool_cpu)
