@@ -152,6 +152,8 @@ SYMBOLS = {
     'cae_door_decode': (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_size_t]),
     'cae_door_stats': (c_int, [c_void_p, c_void_p, c_int, c_int]),
     'cae_door_hold': (c_int, [c_void_p, c_int]),
+    'cae_seg_plan': (c_int, [c_void_p, c_void_p, c_int]),
+    'cae_seg_workspace_bytes': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p]),
     'cae_seg_weight_count': (c_int, [c_void_p]),
     'cae_seg_create': (c_int, [c_void_p, c_void_p, c_int, ctypes.POINTER(c_void_p)]),
     'cae_seg_destroy': (None, [c_void_p]),

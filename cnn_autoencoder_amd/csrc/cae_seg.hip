@@ -15,21 +15,29 @@ namespace cae {
 
 thread_local int64_t g_seg_ticket = 0;  // range ticket of this thread's latest cae_seg_forward
 
-// One convolution of the head with the GroupNorm that follows it (if any)
+// One convolution of the head as seg_plan states it from the config alone: the public record (include/cae_hip.h) and
+// where the stage runs.  Every walk over the head is a loop over these.
+struct SegStage : cae_seg_stage_info {
+    char name[48];          // the reference's state-dict name with the level index, "synthesis_track.1._c2"
+    int src_a, src_b, dst;  // Seg::X0 .. RP; -1: no such source / the caller's logits.  A bridge is staged into src_a first
+    int ab_r, ab_w;         // the Seg::AB1 .. ABP slot source A is read through / this stage's statistics go to; -1: none
+    int outmode, shift;     // SEG_OUT_*; the stage's input planes are (lh << shift, lw << shift)
+};
+
+// The device side of one stage: packed weight, bias rows, the gamma / beta of the GroupNorm behind it (batch_norm only)
 struct SegLayer {
-    int ks = 1, cin_a = 0, cin_b = 0, cout = 0;
-    bool up = false;
     int ct = 1, groups = 1, chunks = 1, cp = 8;  // cp: channels of the output's plane grid
     DevBuf wp, bias;
-    bool norm = false;  // followed by GroupNorm + ReLU (applied by the consumer)
     DevBuf gamma, beta;  // [cp], zero padded
 };
 
 struct Seg {
     cae_seg_config cfg;
-    std::vector<SegLayer> st;  // in launch order
-    DevBuf proj_gamma[8], proj_beta[8];  // the projection units' _bn1 (on the bridges)
-    enum { X0, T1, T2, U, BC, RP, AB, STATS, NWS };
+    std::vector<SegStage> plan;  // in launch order
+    std::vector<SegLayer> st;    // one per stage
+    DevBuf proj_gamma[8], proj_beta[8];  // the _bn1 in front of a bridge's stage (on the bridges)
+    enum { X0, T1, T2, U, BC, RP, AB, STATS, NWS };  // workspaces
+    enum { AB1, AB2, ABB, ABP, NSLOTS };             // the (a, b) slots inside AB
     DevBuf ws[NWS];
     std::mutex mu;
     static constexpr int kFlagSlots = 1024;
@@ -67,6 +75,13 @@ struct Seg {
         last_stream_set = true;
         return CAE_OK;
     }
+    // a fresh range ticket for this thread's call (after ensure_device) -> the device word its launches raise
+    int *draw_ticket() {
+        const int64_t ticket = ++flag_seq;
+        *(volatile int *)(flags + ticket % kFlagSlots) = 0;
+        g_seg_ticket = ticket;
+        return flags_dev + ticket % kFlagSlots;
+    }
     ~Seg() {
         if (order_event) (void)hipEventDestroy(order_event);
         if (flags) (void)hipHostFree(flags);
@@ -79,14 +94,15 @@ static int padded_upload(DevBuf &dst, const float *v, int c, int cp) {
     return dst.upload(p);
 }
 
-static int make_layer(SegLayer &l, const char *name, int ks, int cin_a, int cin_b, int cout, bool up, const float *w,
-                      const float *bias, const float *gamma, const float *beta) {
+static int make_layer(SegLayer &l, const SegStage &p, const float *w, const float *bias, const float *gamma,
+                      const float *beta) {
+    const int ks = p.ks, cin_a = p.cin_a, cin_b = p.cin_b, cout = p.cout;
+    const bool up = p.up != 0;
     const size_t nw = (size_t)(cin_a + cin_b) * cout * (up ? 4 : ks * ks);
-    if (!w || (up && !bias)) return fail(CAE_ERR_ARG, "%s: NULL weight", name);
+    if (!w || (up && !bias)) return fail(CAE_ERR_ARG, "%s: NULL weight", p.name);
     if (!fits_f16(w, nw) || (gamma && !(fits_f16(gamma, cout) && fits_f16(beta, cout))))
         return fail(CAE_ERR_ARG, "%s: a weight, gamma or beta entry is outside the f16 range (|v| <= 65504, finite); "
-                                 "the head has no fp32 path", name);
-    l.ks = ks, l.cin_a = cin_a, l.cin_b = cin_b, l.cout = cout, l.up = up;
+                                 "the head has no fp32 path", p.name);
     const int m = seg_rows(cout, up);
     l.ct = seg_ct(m, ks), l.groups = seg_groups(m, ks), l.chunks = seg_chunks(cin_a, cin_b);
     l.cp = (cout + 7) / 8 * 8;
@@ -99,7 +115,6 @@ static int make_layer(SegLayer &l, const char *name, int ks, int cin_a, int cin_
         }
         CAE_TRY(l.bias.upload(b));
     }
-    l.norm = gamma != nullptr;
     if (gamma) {
         CAE_TRY(padded_upload(l.gamma, gamma, cout, l.cp));
         CAE_TRY(padded_upload(l.beta, beta, cout, l.cp));
@@ -107,17 +122,93 @@ static int make_layer(SegLayer &l, const char *name, int ks, int cin_a, int cin_
     return CAE_OK;
 }
 
-static int check_config(const cae_seg_config &c) {
-    if (c.levels < 1 || c.levels > 8) return fail(CAE_ERR_ARG, "compression_level %d outside 1..8", c.levels);
-    if (c.channels_bn < 1 || c.seg_channels_bn < 1 || c.num_classes < 1) return fail(CAE_ERR_ARG, "channel counts must be >= 1");
-    for (int i = 0; i < c.levels; ++i) {
-        if (c.level_channels[i] < 1 || (c.concat_bridges && c.bridge_channels[i] < 1) ||
-            (i + 1 < c.levels && c.up_channels[i] < 1))
-            return fail(CAE_ERR_ARG, "level %d: channel counts must be >= 1", i);
-        if (i + 1 < c.levels && c.up_channels[i] != c.level_channels[i + 1])
-            return fail(CAE_ERR_ARG, "level %d hands %d channels to a level of %d", i, c.up_channels[i], c.level_channels[i + 1]);
+// The head's structure, stated once (levels inside 1..8): bottleneck _c1 _c2 _up_sample, per level {projection of bridge
+// i: _bn1 on the bridge, _c2} _c1 _c2 [_up_sample], fc.  The running features go T1 -> T2 -> U, a bridge BC -> RP, and RP
+// is contracted in front of U by the level's _c1.
+static std::vector<SegStage> seg_plan(const cae_seg_config &c) {
+    std::vector<SegStage> plan;
+    const int gn = c.batch_norm ? 2 : 0, L = c.levels, sbn = c.seg_channels_bn;
+    auto producer = [&](int buf) {  // the latest stage that wrote `buf`; -1: the latents or a bridge, -2: no source
+        int k = buf < 0 ? -2 : (int)plan.size() - 1;
+        while (k >= 0 && plan[k].dst != buf) --k;
+        return k;
+    };
+    auto add = [&](const char *unit, int level, const char *conv, int ks, int cin_a, int cin_b, int cout, int src_a, int ab_r,
+                   int dst, int ab_w, int shift, int bridge = -1) {
+        SegStage s{};
+        if (level < 0) snprintf(s.name, sizeof s.name, "%s%s", unit, conv);
+        else snprintf(s.name, sizeof s.name, "%s.%d%s", unit, level, conv);
+        s.ks = ks, s.cin_a = cin_a, s.cin_b = cin_b, s.cout = cout, s.bridge = bridge, s.shift = shift;
+        s.src_a = src_a, s.src_b = cin_b ? Seg::U : -1, s.dst = dst, s.ab_r = ab_r, s.ab_w = ab_w;
+        s.up = dst == Seg::U, s.biased = s.up || dst < 0, s.norm = ab_w >= 0;
+        s.outmode = s.up ? SEG_OUT_SHUFFLE : dst < 0 ? SEG_OUT_NCHW : SEG_OUT_C8;
+        s.src_a_stage = producer(s.src_a), s.src_b_stage = producer(s.src_b), s.src_a_transformed = ab_r >= 0;
+        s.n_weights = (bridge >= 0 ? gn : 0) + 1 + s.biased + (s.norm ? gn : 0);
+        plan.push_back(s);
+    };
+    add("bottleneck", -1, "._c1", 1, c.channels_bn, 0, sbn, Seg::X0, -1, Seg::T1, Seg::AB1, 0);
+    add("bottleneck", -1, "._c2", 3, sbn, 0, sbn, Seg::T1, Seg::AB1, Seg::T2, Seg::AB2, 0);
+    add("bottleneck", -1, "._up_sample", 1, sbn, 0, c.level_channels[0], Seg::T2, Seg::AB2, Seg::U, -1, 0);
+    for (int i = 0; i < L; ++i) {
+        const int ch = c.level_channels[i], cat = c.concat_bridges;
+        if (cat) add("bridges_projection", i, "._c2", 3, c.bridge_channels[i], 0, ch, Seg::BC, Seg::ABB, Seg::RP, Seg::ABP, i + 1, i);
+        add("synthesis_track", i, "._c1", 3, cat ? ch : 0, ch, ch, cat ? Seg::RP : -1, cat ? Seg::ABP : -1, Seg::T1, Seg::AB1, i + 1);
+        add("synthesis_track", i, "._c2", 3, ch, 0, ch, Seg::T1, Seg::AB1, Seg::T2, Seg::AB2, i + 1);
+        if (i + 1 < L) add("synthesis_track", i, "._up_sample", 1, ch, 0, c.up_channels[i], Seg::T2, Seg::AB2, Seg::U, -1, i + 1);
+    }
+    add("fc", -1, "", 1, c.level_channels[L - 1], 0, c.num_classes, Seg::T2, Seg::AB2, -1, -1, L);
+    return plan;
+}
+
+// the plan of a config, or CAE_ERR_ARG: every stage has channels, and a source has the channels its producer writes
+static int checked_plan(const cae_seg_config *c, std::vector<SegStage> &plan) {
+    if (!c) return fail(CAE_ERR_ARG, "NULL config");
+    if (c->levels < 1 || c->levels > 8) return fail(CAE_ERR_ARG, "compression_level %d outside 1..8", c->levels);
+    plan = seg_plan(*c);
+    for (const SegStage &p : plan) {
+        if (p.cout < 1 || (p.src_a >= 0 && p.cin_a < 1) || (p.src_b >= 0 && p.cin_b < 1))
+            return fail(CAE_ERR_ARG, "%s: channel counts must be >= 1", p.name);
+        if (p.src_b_stage >= 0 && plan[p.src_b_stage].cout != p.cin_b)
+            return fail(CAE_ERR_ARG, "%s hands %d channels to %s, which takes %d", plan[p.src_b_stage].name,
+                        plan[p.src_b_stage].cout, p.name, p.cin_b);
     }
     return CAE_OK;
+}
+
+static int plan_weights(const std::vector<SegStage> &plan) {
+    int k = 0;
+    for (const SegStage &p : plan) k += p.n_weights;
+    return k;
+}
+
+static int check_extent(const cae_seg_config &c, int n, int lh, int lw) {
+    if (n < 1 || lh < 1 || lw < 1) return fail(CAE_ERR_ARG, "n, lh, lw must be >= 1 (got %d, %d, %d)", n, lh, lw);
+    if (((long)lh << c.levels) * ((long)lw << c.levels) > INT_MAX) return fail(CAE_ERR_ARG, "output plane of more than 2^31 - 1 pixels");
+    return CAE_OK;
+}
+
+static size_t seg_tiles(int hh, int ww) { return (size_t)((hh + SEG_TY - 1) / SEG_TY) * ((ww + SEG_TX - 1) / SEG_TX); }
+
+// workspace sizes: the largest extent each buffer takes over the plan -> need[]; returns the floats of one (a, b) slot
+static size_t seg_workspace(const std::vector<SegStage> &plan, int n, int lh, int lw, size_t need[Seg::NWS]) {
+    auto c8 = [&](int ch, size_t hw) { return (size_t)n * ((ch + 7) / 8) * hw * 32; };
+    auto grow = [&](int which, size_t bytes) { if (which >= 0) need[which] = std::max(need[which], bytes); };
+    size_t cpmax = 0;
+    std::fill(need, need + Seg::NWS, (size_t)0);
+    for (const SegStage &p : plan) {
+        const int hh = lh << p.shift, ww = lw << p.shift;
+        const size_t hw = (size_t)hh * ww, cp = (p.cout + 7) / 8 * 8;
+        grow(p.src_a, c8(p.cin_a, hw));
+        grow(p.src_b, c8(p.cin_b, hw));
+        grow(p.dst, c8(p.cout, hw * (p.up ? 4 : 1)));
+        if (p.bridge >= 0) cpmax = std::max(cpmax, (size_t)(p.cin_a + 7) / 8 * 8);
+        if (p.norm) {
+            cpmax = std::max(cpmax, cp);
+            grow(Seg::STATS, seg_tiles(hh, ww) * n * cp * 12);
+        }
+    }
+    need[Seg::AB] = Seg::NSLOTS * (size_t)n * cpmax * 2 * sizeof(float);
+    return (size_t)n * cpmax * 2;
 }
 
 }  // namespace cae
@@ -126,62 +217,58 @@ using namespace cae;
 
 extern "C" {
 
-int cae_seg_weight_count(const cae_seg_config *c) {
-    if (!c) return fail(CAE_ERR_ARG, "NULL config");
-    const int nb = c->batch_norm ? 2 : 0;
-    int k = (1 + nb) * 2 + 2;  // bottleneck
-    for (int i = 0; i < c->levels; ++i) k += (c->concat_bridges ? nb + 1 + nb : 0) + (1 + nb) * 2 + (i + 1 < c->levels ? 2 : 0);
-    return k + 2;
+int cae_seg_plan(const cae_seg_config *cfg, cae_seg_stage_info *out, int capacity) {
+    std::vector<SegStage> plan;
+    CAE_TRY(checked_plan(cfg, plan));
+    for (int k = 0; out && k < capacity && k < (int)plan.size(); ++k) out[k] = plan[k];
+    return (int)plan.size();
+}
+
+int cae_seg_workspace_bytes(const cae_seg_config *cfg, int n, int lh, int lw, size_t *out) {
+    std::vector<SegStage> plan;
+    CAE_TRY(checked_plan(cfg, plan));
+    if (!out) return fail(CAE_ERR_ARG, "NULL argument");
+    CAE_TRY(check_extent(*cfg, n, lh, lw));
+    seg_workspace(plan, n, lh, lw, out);
+    return CAE_OK;
+}
+
+int cae_seg_weight_count(const cae_seg_config *cfg) {
+    std::vector<SegStage> plan;
+    CAE_TRY(checked_plan(cfg, plan));
+    return plan_weights(plan);
 }
 
 int cae_seg_create(const cae_seg_config *cfg, const float *const *weights, int n_weights, cae_seg_t **out) {
     if (!cfg || !weights || !out) return fail(CAE_ERR_ARG, "NULL argument");
-    CAE_TRY(check_config(*cfg));
-    if (n_weights != cae_seg_weight_count(cfg))
-        return fail(CAE_ERR_ARG, "%d weight arrays given, this configuration has %d", n_weights, cae_seg_weight_count(cfg));
+    std::vector<SegStage> plan;
+    CAE_TRY(checked_plan(cfg, plan));
+    const int want = plan_weights(plan);
+    if (n_weights != want) return fail(CAE_ERR_ARG, "%d weight arrays given, this configuration has %d", n_weights, want);
     for (int i = 0; i < n_weights; ++i)
         if (!weights[i]) return fail(CAE_ERR_ARG, "weight array %d is NULL", i);
     Seg *s = new (std::nothrow) Seg;
     if (!s) return fail(CAE_ERR_NOMEM, "out of memory");
     s->cfg = *cfg;
-    const cae_seg_config &c = s->cfg;
-    const bool bn = c.batch_norm != 0;
-    int k = 0, rc = CAE_OK;
-    auto next = [&]() { return weights[k++]; };
-    auto conv = [&](const char *name, int ks, int ca, int cb, int co, bool has_norm) {
-        if (rc) return;
-        const float *w = next(), *g = nullptr, *b = nullptr;
-        if (has_norm && bn) g = next(), b = next();
-        s->st.emplace_back();
-        rc = make_layer(s->st.back(), name, ks, ca, cb, co, false, w, nullptr, g, b);
-    };
-    auto biased = [&](const char *name, int ci, int co, bool up) {
-        if (rc) return;
-        const float *w = next(), *b = next();
-        s->st.emplace_back();
-        rc = make_layer(s->st.back(), name, 1, ci, 0, co, up, w, b, nullptr, nullptr);
-    };
-    conv("bottleneck._c1", 1, c.channels_bn, 0, c.seg_channels_bn, true);
-    conv("bottleneck._c2", 3, c.seg_channels_bn, 0, c.seg_channels_bn, true);
-    biased("bottleneck._up_sample", c.seg_channels_bn, c.level_channels[0], true);
-    for (int i = 0; i < c.levels && !rc; ++i) {
-        const int ch = c.level_channels[i];
-        if (c.concat_bridges) {
-            if (bn) {
-                const float *g = next(), *b = next();
-                if (!fits_f16(g, c.bridge_channels[i]) || !fits_f16(b, c.bridge_channels[i]))
-                    rc = fail(CAE_ERR_ARG, "bridges_projection.%d._bn1: gamma or beta outside the f16 range (|v| <= 65504)", i);
-                const int cp = (c.bridge_channels[i] + 7) / 8 * 8;
-                if (!rc) rc = padded_upload(s->proj_gamma[i], g, c.bridge_channels[i], cp);
-                if (!rc) rc = padded_upload(s->proj_beta[i], b, c.bridge_channels[i], cp);
-            }
-            conv("bridges_projection._c2", 3, c.bridge_channels[i], 0, ch, true);
+    s->plan = std::move(plan);
+    const bool bn = s->cfg.batch_norm != 0;
+    const float *const *w = weights;  // consumed in the plan's order: [_bn1 gamma beta] weight [bias] [gamma beta]
+    int rc = CAE_OK;
+    for (const SegStage &p : s->plan) {
+        if (p.bridge >= 0 && bn) {
+            const float *g = *w++, *b = *w++;
+            const int cp = (p.cin_a + 7) / 8 * 8;
+            if (!fits_f16(g, p.cin_a) || !fits_f16(b, p.cin_a))
+                rc = fail(CAE_ERR_ARG, "the _bn1 in front of %s: gamma or beta outside the f16 range (|v| <= 65504)", p.name);
+            if (!rc) rc = padded_upload(s->proj_gamma[p.bridge], g, p.cin_a, cp);
+            if (!rc) rc = padded_upload(s->proj_beta[p.bridge], b, p.cin_a, cp);
         }
-        conv("synthesis_track._c1", 3, c.concat_bridges ? ch : 0, ch, ch, true);
-        conv("synthesis_track._c2", 3, ch, 0, ch, true);
-        if (i + 1 < c.levels) biased("synthesis_track._up_sample", ch, c.up_channels[i], true);
+        const float *wt = *w++, *bias = p.biased ? *w++ : nullptr, *g = nullptr, *b = nullptr;
+        if (p.norm && bn) g = *w++, b = *w++;
+        s->st.emplace_back();
+        if (!rc) rc = make_layer(s->st.back(), p, wt, bias, g, b);
+        if (rc) break;
     }
-    biased("fc", c.level_channels[c.levels - 1], c.num_classes, false);
     if (rc) {
         delete s;
         return rc;
@@ -194,7 +281,7 @@ void cae_seg_destroy(cae_seg_t *h) { delete reinterpret_cast<Seg *>(h); }
 
 int cae_seg_stage_count(cae_seg_t *h) {
     Seg *s = reinterpret_cast<Seg *>(h);
-    return s ? (int)s->st.size() : fail(CAE_ERR_ARG, "NULL handle");
+    return s ? (int)s->plan.size() : fail(CAE_ERR_ARG, "NULL handle");
 }
 
 int64_t cae_seg_last_ticket(void) { return g_seg_ticket; }
@@ -216,12 +303,10 @@ int cae_seg_forward(cae_seg_t *h, const float *latents_dev, const float *const *
     Seg *s = reinterpret_cast<Seg *>(h);
     if (!s || !latents_dev || !logits_dev) return fail(CAE_ERR_ARG, "NULL argument");
     const cae_seg_config &c = s->cfg;
-    const int L = c.levels;
-    if (n < 1 || lh < 1 || lw < 1) return fail(CAE_ERR_ARG, "n, lh, lw must be >= 1 (got %d, %d, %d)", n, lh, lw);
-    if (((long)lh << L) * ((long)lw << L) > INT_MAX) return fail(CAE_ERR_ARG, "output plane of more than 2^31 - 1 pixels");
+    CAE_TRY(check_extent(c, n, lh, lw));
     if (c.concat_bridges) {
         if (!bridges_dev) return fail(CAE_ERR_ARG, "this head concatenates bridges: bridges_dev is NULL");
-        for (int i = 0; i < L; ++i)
+        for (int i = 0; i < c.levels; ++i)
             if (!bridges_dev[i]) return fail(CAE_ERR_ARG, "bridge %d is NULL", i);
     }
     if (taps && (!taps->raw || !taps->ab || (c.concat_bridges && !taps->bridge_ab))) return fail(CAE_ERR_ARG, "NULL tap list");
@@ -230,144 +315,85 @@ int cae_seg_forward(cae_seg_t *h, const float *latents_dev, const float *const *
     CAE_TRY(s->ensure_device());
     CAE_TRY(s->order_stream(st));
 
-    // workspace sizes: the largest extent each buffer takes
-    auto c8 = [&](int ch, size_t hw) { return (size_t)n * ((ch + 7) / 8) * hw * 32; };
-    size_t need[Seg::NWS] = {0}, cpmax = (c.seg_channels_bn + 7) / 8 * 8;
-    const size_t hw0 = (size_t)lh * lw;
-    need[Seg::X0] = c8(c.channels_bn, hw0);
-    need[Seg::T1] = need[Seg::T2] = c8(c.seg_channels_bn, hw0);
-    auto tiles_of = [](int hh, int ww) { return (size_t)((hh + SEG_TY - 1) / SEG_TY) * ((ww + SEG_TX - 1) / SEG_TX); };
-    need[Seg::STATS] = tiles_of(lh, lw) * n * cpmax * 12;
-    for (int i = 0; i < L; ++i) {
-        const size_t hw = hw0 << (2 * (i + 1));
-        const int ch = c.level_channels[i];
-        need[Seg::U] = std::max(need[Seg::U], c8(ch, hw));
-        need[Seg::T1] = std::max(need[Seg::T1], c8(ch, hw));
-        need[Seg::T2] = std::max(need[Seg::T2], c8(ch, hw));
-        size_t cpl = (ch + 7) / 8 * 8;
-        if (c.concat_bridges) {
-            need[Seg::BC] = std::max(need[Seg::BC], c8(c.bridge_channels[i], hw));
-            need[Seg::RP] = std::max(need[Seg::RP], c8(ch, hw));
-            cpmax = std::max(cpmax, (size_t)(c.bridge_channels[i] + 7) / 8 * 8);
-        }
-        cpmax = std::max(cpmax, cpl);
-        need[Seg::STATS] = std::max(need[Seg::STATS], tiles_of(lh << (i + 1), lw << (i + 1)) * n * cpl * 12);
-    }
-    const size_t ab_floats = (size_t)n * cpmax * 2;
-    need[Seg::AB] = 4 * ab_floats * sizeof(float);
+    size_t need[Seg::NWS];
+    const size_t ab_floats = seg_workspace(s->plan, n, lh, lw, need);
     for (int w = 0; w < Seg::NWS; ++w)
         if (need[w]) CAE_TRY(s->ensure_ws(w, need[w]));
+    int *flag = s->draw_ticket();
 
-    const int64_t ticket = ++s->flag_seq;
-    *(volatile int *)(s->flags + ticket % Seg::kFlagSlots) = 0;
-    g_seg_ticket = ticket;
-    int *flag = s->flags_dev + ticket % Seg::kFlagSlots;
-
-    float *ab1 = s->ws[Seg::AB].get<float>(), *ab2 = ab1 + ab_floats, *abb = ab2 + ab_floats, *abp = abb + ab_floats;
-    int stage = 0;
-    // one convolution: its launch, its statistics -> (a, b) for the consumer, its taps
-    auto run = [&](SegSrc A, SegSrc B, float *dst, int outmode, int hh, int ww, float *ab_out) -> int {
+    auto buf = [&](int which) { return which < 0 ? nullptr : s->ws[which].get<float>(); };
+    auto slot = [&](int which) { return which < 0 ? nullptr : s->ws[Seg::AB].get<float>() + which * ab_floats; };
+    auto planes = [](int ch) { return (ch + 7) / 8; };
+    // one convolution: its inputs staged, its launch, its statistics -> (a, b) for the consumer, its taps
+    for (size_t stage = 0; stage < s->plan.size(); ++stage) {
+        const SegStage &p = s->plan[stage];
         SegLayer &l = s->st[stage];
+        const int hh = lh << p.shift, ww = lw << p.shift;
+        const size_t hw = (size_t)hh * ww;
+        float *dst = p.dst < 0 ? logits_dev : buf(p.dst), *ab_out = slot(p.ab_w);
+        if (p.src_a == Seg::X0) CAE_TRY(launch_seg_nchw_to_c8(latents_dev, buf(p.src_a), n, p.cin_a, hw, st));  // the latents
+        if (p.bridge >= 0) {  // the bridge, and the (a, b) pairs of the _bn1 on it
+            const float *b = bridges_dev[p.bridge];
+            CAE_TRY(launch_seg_nchw_to_c8(b, buf(p.src_a), n, p.cin_a, hw, st));
+            CAE_TRY(launch_seg_plane_moments(b, n, p.cin_a, planes(p.cin_a) * 8, hw, s->proj_gamma[p.bridge].get<float>(),
+                                             s->proj_beta[p.bridge].get<float>(), slot(p.ab_r), st));
+            if (taps && taps->bridge_ab[p.bridge])
+                HIP_TRY(hipMemcpyAsync(taps->bridge_ab[p.bridge], slot(p.ab_r), (size_t)n * planes(p.cin_a) * 64,
+                                       hipMemcpyDeviceToDevice, st));
+        }
         SegConvArgs a{};
-        a.A = A, a.B = B;
+        a.A = SegSrc{buf(p.src_a), slot(p.ab_r), planes(p.cin_a)}, a.B = SegSrc{buf(p.src_b), nullptr, planes(p.cin_b)};
         a.wp = l.wp.get<char>(), a.bias = l.bias.get<float>(), a.out = dst, a.flag = flag;
-        a.stats = (ab_out && l.norm) ? s->ws[Seg::STATS].get<float>() : nullptr;
-        a.N = n, a.H = hh, a.W = ww, a.chunks = l.chunks, a.cout = l.cout, a.out_planes = l.cp / 8, a.outmode = outmode;
-        CAE_TRY(launch_seg_conv(l.ks, l.ct, l.groups, a, st));
-        if (ab_out)
-            CAE_TRY(launch_seg_finalize(a.stats, (int)tiles_of(hh, ww), n, l.cp, l.norm ? l.gamma.get<float>() : nullptr,
-                                        l.beta.get<float>(), ab_out, st));
+        a.stats = (ab_out && l.gamma) ? s->ws[Seg::STATS].get<float>() : nullptr;
+        a.N = n, a.H = hh, a.W = ww, a.chunks = l.chunks, a.cout = p.cout, a.out_planes = l.cp / 8, a.outmode = p.outmode;
+        CAE_TRY(launch_seg_conv(p.ks, l.ct, l.groups, a, st));
+        if (ab_out)  // (without batch_norm too: no statistics, no gamma -> the identity pairs)
+            CAE_TRY(launch_seg_finalize(a.stats, (int)seg_tiles(hh, ww), n, l.cp, l.gamma.get<float>(), l.beta.get<float>(),
+                                        ab_out, st));
         if (taps) {
-            const size_t ohw = (size_t)hh * ww * (outmode == SEG_OUT_SHUFFLE ? 4 : 1);
+            const size_t ohw = hw * (p.up ? 4 : 1);
             if (taps->raw[stage]) {
-                if (outmode == SEG_OUT_NCHW)
-                    HIP_TRY(hipMemcpyAsync(taps->raw[stage], dst, (size_t)n * l.cout * ohw * 4, hipMemcpyDeviceToDevice, st));
+                if (p.dst < 0)
+                    HIP_TRY(hipMemcpyAsync(taps->raw[stage], dst, (size_t)n * p.cout * ohw * 4, hipMemcpyDeviceToDevice, st));
                 else
-                    CAE_TRY(launch_seg_c8_to_nchw(dst, taps->raw[stage], n, l.cout, ohw, st));
+                    CAE_TRY(launch_seg_c8_to_nchw(dst, taps->raw[stage], n, p.cout, ohw, st));
             }
             if (ab_out && taps->ab[stage])
                 HIP_TRY(hipMemcpyAsync(taps->ab[stage], ab_out, (size_t)n * l.cp * 8, hipMemcpyDeviceToDevice, st));
         }
-        ++stage;
-        return CAE_OK;
-    };
-    auto planes = [](int ch) { return (ch + 7) / 8; };
-    const SegSrc none{nullptr, nullptr, 0};
-    float *x0 = s->ws[Seg::X0].get<float>(), *t1 = s->ws[Seg::T1].get<float>(), *t2 = s->ws[Seg::T2].get<float>();
-    float *u = s->ws[Seg::U].get<float>(), *bc = s->ws[Seg::BC].get<float>(), *rp = s->ws[Seg::RP].get<float>();
-
-    CAE_TRY(launch_seg_nchw_to_c8(latents_dev, x0, n, c.channels_bn, hw0, st));
-    CAE_TRY(run(SegSrc{x0, nullptr, planes(c.channels_bn)}, none, t1, SEG_OUT_C8, lh, lw, ab1));
-    CAE_TRY(run(SegSrc{t1, ab1, planes(c.seg_channels_bn)}, none, t2, SEG_OUT_C8, lh, lw, ab2));
-    CAE_TRY(run(SegSrc{t2, ab2, planes(c.seg_channels_bn)}, none, u, SEG_OUT_SHUFFLE, lh, lw, nullptr));
-    for (int i = 0; i < L; ++i) {
-        const int hh = lh << (i + 1), ww = lw << (i + 1), ch = c.level_channels[i];
-        const size_t hw = (size_t)hh * ww;
-        const SegSrc up{u, nullptr, planes(ch)};
-        if (c.concat_bridges) {
-            const int bch = c.bridge_channels[i];
-            CAE_TRY(launch_seg_nchw_to_c8(bridges_dev[i], bc, n, bch, hw, st));
-            CAE_TRY(launch_seg_plane_moments(bridges_dev[i], n, bch, planes(bch) * 8, hw, s->proj_gamma[i].get<float>(),
-                                             s->proj_beta[i].get<float>(), abb, st));
-            if (taps && taps->bridge_ab[i])
-                HIP_TRY(hipMemcpyAsync(taps->bridge_ab[i], abb, (size_t)n * planes(bch) * 64, hipMemcpyDeviceToDevice, st));
-            CAE_TRY(run(SegSrc{bc, abb, planes(bch)}, none, rp, SEG_OUT_C8, hh, ww, abp));
-            CAE_TRY(run(SegSrc{rp, abp, planes(ch)}, up, t1, SEG_OUT_C8, hh, ww, ab1));
-        } else {
-            CAE_TRY(run(SegSrc{nullptr, nullptr, 0}, up, t1, SEG_OUT_C8, hh, ww, ab1));
-        }
-        CAE_TRY(run(SegSrc{t1, ab1, planes(ch)}, none, t2, SEG_OUT_C8, hh, ww, ab2));
-        if (i + 1 < L) CAE_TRY(run(SegSrc{t2, ab2, planes(ch)}, none, u, SEG_OUT_SHUFFLE, hh, ww, nullptr));
     }
-    return run(SegSrc{t2, ab2, planes(c.level_channels[L - 1])}, none, logits_dev, SEG_OUT_NCHW, lh << L, lw << L, nullptr);
+    return CAE_OK;
 }
 
 int cae_seg_set_weights(cae_seg_t *h, const float *const *weights_dev, int n_weights, void *stream) {
     Seg *s = reinterpret_cast<Seg *>(h);
     if (!s || !weights_dev) return fail(CAE_ERR_ARG, "NULL argument");
-    const cae_seg_config &c = s->cfg;
-    if (n_weights != cae_seg_weight_count(&c))
-        return fail(CAE_ERR_ARG, "%d weight arrays given, this configuration has %d", n_weights, cae_seg_weight_count(&c));
+    const int want = plan_weights(s->plan);
+    if (n_weights != want) return fail(CAE_ERR_ARG, "%d weight arrays given, this configuration has %d", n_weights, want);
     for (int i = 0; i < n_weights; ++i)
         if (!weights_dev[i]) return fail(CAE_ERR_ARG, "weight array %d is NULL", i);
     hipStream_t st = (hipStream_t)stream;
     std::lock_guard<std::mutex> lk(s->mu);
     CAE_TRY(s->ensure_device());
     CAE_TRY(s->order_stream(st));
-    const int64_t ticket = ++s->flag_seq;
-    *(volatile int *)(s->flags + ticket % Seg::kFlagSlots) = 0;
-    g_seg_ticket = ticket;
-    int *flag = s->flags_dev + ticket % Seg::kFlagSlots;
-    const bool bn = c.batch_norm != 0;
-    int k = 0, stage = 0;
-    // (the walk of cae_seg_create)
-    auto layer = [&](bool biased) -> int {
-        SegLayer &l = s->st[stage++];
-        CAE_TRY(launch_seg_pack_dev(weights_dev[k++], l.cin_a, l.cin_b, l.cout, l.ks, l.up, l.wp.get<char>(), flag, st));
-        if (biased) CAE_TRY(launch_seg_pad_vec(weights_dev[k++], l.cout, l.up, l.groups * l.ct * 32, false, l.bias.get<float>(), flag, st));
-        if (l.norm) {
-            CAE_TRY(launch_seg_pad_vec(weights_dev[k++], l.cout, false, l.cp, true, l.gamma.get<float>(), flag, st));
-            CAE_TRY(launch_seg_pad_vec(weights_dev[k++], l.cout, false, l.cp, true, l.beta.get<float>(), flag, st));
+    int *flag = s->draw_ticket();
+    const float *const *w = weights_dev;  // consumed as cae_seg_create consumes the host arrays
+    for (size_t stage = 0; stage < s->plan.size(); ++stage) {
+        const SegStage &p = s->plan[stage];
+        SegLayer &l = s->st[stage];
+        if (p.bridge >= 0 && s->cfg.batch_norm) {
+            const int cp = (p.cin_a + 7) / 8 * 8;
+            CAE_TRY(launch_seg_pad_vec(*w++, p.cin_a, false, cp, true, s->proj_gamma[p.bridge].get<float>(), flag, st));
+            CAE_TRY(launch_seg_pad_vec(*w++, p.cin_a, false, cp, true, s->proj_beta[p.bridge].get<float>(), flag, st));
         }
-        return CAE_OK;
-    };
-    CAE_TRY(layer(false));
-    CAE_TRY(layer(false));
-    CAE_TRY(layer(true));
-    for (int i = 0; i < c.levels; ++i) {
-        if (c.concat_bridges) {
-            if (bn) {
-                const int bc = c.bridge_channels[i], cp = (bc + 7) / 8 * 8;
-                CAE_TRY(launch_seg_pad_vec(weights_dev[k++], bc, false, cp, true, s->proj_gamma[i].get<float>(), flag, st));
-                CAE_TRY(launch_seg_pad_vec(weights_dev[k++], bc, false, cp, true, s->proj_beta[i].get<float>(), flag, st));
-            }
-            CAE_TRY(layer(false));
+        CAE_TRY(launch_seg_pack_dev(*w++, p.cin_a, p.cin_b, p.cout, p.ks, p.up != 0, l.wp.get<char>(), flag, st));
+        if (p.biased) CAE_TRY(launch_seg_pad_vec(*w++, p.cout, p.up != 0, l.groups * l.ct * 32, false, l.bias.get<float>(), flag, st));
+        if (l.gamma) {
+            CAE_TRY(launch_seg_pad_vec(*w++, p.cout, false, l.cp, true, l.gamma.get<float>(), flag, st));
+            CAE_TRY(launch_seg_pad_vec(*w++, p.cout, false, l.cp, true, l.beta.get<float>(), flag, st));
         }
-        CAE_TRY(layer(false));
-        CAE_TRY(layer(false));
-        if (i + 1 < c.levels) CAE_TRY(layer(true));
     }
-    return layer(true);
+    return CAE_OK;
 }
 
 void cae_seg_tile(int *tx, int *ty) {

@@ -35,7 +35,7 @@ import torch.nn.functional as F
 
 from . import _lib
 from . import segmenters
-from .segmenters import JNet, _SegTaps
+from .segmenters import JNet
 
 JOINT = ('joint training of codec and segmentation head is not built: y_q and the bridges are constants of the head '
          '(detach them, or run the codec under torch.no_grad() as seg_train.setup_forward_func does)')
@@ -222,10 +222,7 @@ class JNetTrain(JNet):
                 out = super().forward(x, fx_brg, taps=taps)
             self._check_weights()
             return out
-        brg = self._check(x, fx_brg) or []
-        dev = _lib.require_gpu()
-        x = x.detach().to(device=dev, dtype=torch.float32).contiguous()
-        brg = [b.detach().to(device=dev, dtype=torch.float32).contiguous() for b in brg]
+        x, brg = self._stage(x, self._check(x, fx_brg))
         if self.force_torch:
             return self._forward_torch(x, brg), None
         params = self._weight_list()
@@ -235,28 +232,8 @@ class JNetTrain(JNet):
 
     def _forward_taps(self, x, brg):
         """cae_seg_forward with every tap, asynchronous: the range ticket is checked by the backward"""
-        dev = x.device
-        hd = self._sync()
-        n, _, lh, lw = x.shape
-        L = len(self.synthesis_track)
-        plan = self.stage_plan()
-        logits = torch.empty((n, self._num_classes, lh * 2 ** L, lw * 2 ** L), dtype=torch.float32, device=dev)
-        raw, ab, size = [], [], (lh, lw)
-        for st in plan:
-            cout = st['weight'].shape[1 if st['up'] else 0]
-            if st['up']:
-                size = (2 * size[0], 2 * size[1])
-            raw.append(torch.empty((n, cout) + size, dtype=torch.float32, device=dev))
-            ab.append(torch.zeros((n, (cout + 7) // 8 * 8, 2), dtype=torch.float32, device=dev) if st['has_ab'] else None)
-        bab = [torch.zeros((n, (b.size(1) + 7) // 8 * 8, 2), dtype=torch.float32, device=dev) for b in brg]
-        arr = lambda ts: (ctypes.c_void_p * max(len(ts), 1))(*[None if t is None else t.data_ptr() for t in ts])
-        keep = (arr(raw), arr(ab), arr(bab))
-        tap_arg = ctypes.byref(_SegTaps(*[ctypes.cast(a, ctypes.POINTER(ctypes.c_void_p)) for a in keep]))
-        brg_ptr = (ctypes.c_void_p * L)(*[b.data_ptr() for b in brg]) if brg else None
-        lib = _lib.lib()
-        _lib.check(lib.cae_seg_forward(hd.ptr, x.data_ptr(), brg_ptr, n, lh, lw, logits.data_ptr(), tap_arg,
-                                       _lib.stream_ptr()))
-        return logits, dict(plan=plan, raw=raw, ab=ab, bridge_ab=bab, ticket=lib.cae_seg_last_ticket())
+        logits, saved, ticket = self._launch(x, brg, taps=True)
+        return logits, dict(saved, ticket=ticket)
 
     def _backward(self, x, brg, saved, g_logits) -> List[Optional[torch.Tensor]]:
         plan, raw, ab, bab = saved['plan'], saved['raw'], saved['ab'], saved['bridge_ab']
@@ -355,18 +332,7 @@ def setup_modules(segment_model_type='JNet', **kwargs):
 
 def segmenter_from_state_dict(checkpoint, gpu=False, train=True):
     """The reference's loader (``_segmenters.py:347``) -> ``JNetTrain``; ``gpu`` is accepted for signature compatibility."""
-    state = torch.load(checkpoint, map_location='cpu') if isinstance(checkpoint, str) else checkpoint
-    if state.get('segment_model_type', None) not in segmenters.SEG_MODELS:
-        raise ValueError(f"segment_model_type must be one of {sorted(segmenters.SEG_MODELS)}, got "
-                         f"{state.get('segment_model_type')!r}")
-    model = setup_modules(**state)
-    segmenters.load_state_dict(model, state)
-    if torch.cuda.is_available():
-        model.cuda()
-    model.train(bool(train))
-    for p in model.parameters():
-        p.requires_grad_(bool(train))
-    return model
+    return segmenters.load_segmenter(checkpoint, setup_modules, train, trainable=True)
 
 
 def setup_forward_func(enabled_modules: Sequence[str] = ('encoder', 'fact_ent', 'decoder', 'seg_model'),

@@ -7,9 +7,11 @@ The module classes carry the reference's attribute names, so the ``state_dict`` 
 and its checkpoints load with ``strict=True``.  The parameter holders are ordinary torch layers; they are never called
 on the hot path.  ``force_torch=True`` runs the same head as torch ops on the device (the measurement's comparison and
 a second opinion in the tests).  Not built, and raising ``NotImplementedError``: ``UNet`` with its own analysis track
-(image domain, ``MaxPool``), training the head, calling it while autograd is recording.  Training lives beside this module:
-``seg_train.JNetTrain`` is this ``JNet`` with a backward pass (same state dict), with the loader, forward function, losses
-and step of the reference's head training.
+(image domain, ``MaxPool``).  Training lives beside this module: ``seg_train.JNetTrain`` is this ``JNet`` with a backward
+pass (same state dict), with the loader, forward function, losses and step of the reference's head training; this
+``JNet`` itself refuses train mode and calls while autograd is recording.
+
+The head's structure is stated once, in the library (``cae_seg_plan``); ``JNet.stage_plan()`` mirrors it with the tensors.
 
 ``predict`` / ``class_metrics`` turn logits into what the reference's harness hands out (class map, scores, counts and
 metrics; ``cae_seg_predict``, csrc/cae_seg_predict.hip); ``slide.SlideCoder.segment_batches`` and ``zarrio.segment_image``
@@ -265,39 +267,51 @@ class JNet(nn.Module):
         """y_q (B,channels_bn,h,w), fx_brg: the decoder's bridges (coarsest first, the reconstruction last) ->
         (logits (B,num_classes,h 2^L,w 2^L), None).  taps=True (tests): (logits, dict of every stage's raw output and
         (a, b) pairs)."""
-        fx_brg = self._check(x, fx_brg)
-        dev = _lib.require_gpu()
-        x = x.detach().to(device=dev, dtype=torch.float32).contiguous()
-        brg = [b.detach().to(device=dev, dtype=torch.float32).contiguous() for b in fx_brg] if fx_brg else []
+        x, brg = self._stage(x, self._check(x, fx_brg))
         if self.force_torch:
             return self._forward_torch(x, brg), None
+        logits, tapped, ticket = self._launch(x, brg, taps)
+        torch.cuda.current_stream().synchronize()
+        _lib.check(_lib.lib().cae_seg_range_check(self._handle.ptr, ticket))  # FloatingPointError: never wrong logits
+        return logits, tapped
+
+    def _stage(self, x, fx_brg):
+        """the checked inputs as constants on the device -> (latents, list of bridges), contiguous fp32"""
+        dev = _lib.require_gpu()
+        put = lambda t: t.detach().to(device=dev, dtype=torch.float32).contiguous()
+        return put(x), [put(b) for b in fx_brg or []]
+
+    def _taps(self, x, brg) -> Dict:
+        """the taps of stage_plan(): raw outputs (cae_seg_forward writes each whole), (a, b) pairs, the bridges' pairs"""
+        n, _, lh, lw = x.shape
+        pairs = lambda c: torch.zeros((n, (c + 7) // 8 * 8, 2), dtype=torch.float32, device=x.device)
+        plan, raw, ab, size = self.stage_plan(), [], [], (lh, lw)
+        for st in plan:
+            cout = st['weight'].shape[1 if st['up'] else 0]
+            if st['up']:
+                size = (2 * size[0], 2 * size[1])
+            raw.append(torch.empty((n, cout) + size, dtype=torch.float32, device=x.device))
+            ab.append(pairs(cout) if st['has_ab'] else None)
+        return dict(plan=plan, raw=raw, ab=ab, bridge_ab=[pairs(b.size(1)) for b in brg])
+
+    def _launch(self, x, brg, taps: bool):
+        """one cae_seg_forward of staged inputs, asynchronous on the current stream -> (logits, the taps or None, the
+        call's range ticket, to be checked once the stream work has completed)"""
         hd = self._sync()
         n, _, lh, lw = x.shape
         L = len(self.synthesis_track)
-        logits = torch.empty((n, self._num_classes, lh * 2 ** L, lw * 2 ** L), dtype=torch.float32, device=dev)
+        logits = torch.empty((n, self._num_classes, lh * 2 ** L, lw * 2 ** L), dtype=torch.float32, device=x.device)
         brg_ptr = (ctypes.c_void_p * L)(*[b.data_ptr() for b in brg]) if brg else None
-        tap_arg, tapped = None, None
+        tap_arg = tapped = None
         if taps:
-            plan = self.stage_plan()
-            raw, ab, size = [], [], (lh, lw)
-            for st in plan:
-                cout = st['weight'].shape[1 if st['up'] else 0]
-                if st['up']:
-                    size = (2 * size[0], 2 * size[1])
-                raw.append(torch.zeros((n, cout) + size, dtype=torch.float32, device=dev))
-                ab.append(torch.zeros((n, (cout + 7) // 8 * 8, 2), dtype=torch.float32, device=dev) if st['has_ab'] else None)
-            bab = [torch.zeros((n, (b.size(1) + 7) // 8 * 8, 2), dtype=torch.float32, device=dev) for b in brg]
+            tapped = self._taps(x, brg)
             arr = lambda ts: (ctypes.c_void_p * max(len(ts), 1))(*[None if t is None else t.data_ptr() for t in ts])
-            keep = (arr(raw), arr(ab), arr(bab))
+            keep = [arr(tapped[k]) for k in ('raw', 'ab', 'bridge_ab')]
             tap_arg = ctypes.byref(_SegTaps(*[ctypes.cast(a, ctypes.POINTER(ctypes.c_void_p)) for a in keep]))
-            tapped = dict(plan=plan, raw=raw, ab=ab, bridge_ab=bab)
-        L_ = _lib.lib()
-        _lib.check(L_.cae_seg_forward(hd.ptr, x.data_ptr(), brg_ptr, n, lh, lw, logits.data_ptr(), tap_arg,
-                                      _lib.stream_ptr()))
-        ticket = L_.cae_seg_last_ticket()
-        torch.cuda.current_stream().synchronize()
-        _lib.check(L_.cae_seg_range_check(hd.ptr, ticket))  # FloatingPointError: never wrong logits
-        return (logits, tapped) if taps else (logits, None)
+        lib = _lib.lib()
+        _lib.check(lib.cae_seg_forward(hd.ptr, x.data_ptr(), brg_ptr, n, lh, lw, logits.data_ptr(), tap_arg,
+                                       _lib.stream_ptr()))
+        return logits, tapped, lib.cae_seg_last_ticket()
 
     def _forward_torch(self, x: torch.Tensor, brg: List[torch.Tensor]) -> torch.Tensor:
         """The same head as torch ops on the device."""
@@ -332,20 +346,28 @@ def load_state_dict(model, checkpoint_state):
         model.load_state_dict(checkpoint_state['seg_model'])
 
 
-def segmenter_from_state_dict(checkpoint, gpu=False, train=False):
-    """checkpoint: path or dict with 'segment_model_type', the constructor's keys and 'seg_model' (the state dict).
-    ``gpu`` is accepted for signature compatibility: the head always runs on the current HIP device."""
+def load_segmenter(checkpoint, setup, train, trainable):
+    """The loader behind both ``segmenter_from_state_dict``: ``setup(**state)`` builds the module, ``trainable`` says
+    whether it has a backward pass (then ``train`` also sets the parameters' requires_grad)."""
     state = torch.load(checkpoint, map_location='cpu') if isinstance(checkpoint, str) else checkpoint
     if state.get('segment_model_type', None) not in SEG_MODELS:
         raise ValueError(f"segment_model_type must be one of {sorted(SEG_MODELS)}, got {state.get('segment_model_type')!r}")
-    if train:
+    if train and not trainable:
         raise NotImplementedError('training the segmentation head is not built (train=True)')
-    model = setup_modules(**state)
+    model = setup(**state)
     load_state_dict(model, state)
     if torch.cuda.is_available():
         model.cuda()
-    model.eval()
+    model.train(bool(train))
+    for p in model.parameters() if trainable else ():
+        p.requires_grad_(bool(train))
     return model
+
+
+def segmenter_from_state_dict(checkpoint, gpu=False, train=False):
+    """checkpoint: path or dict with 'segment_model_type', the constructor's keys and 'seg_model' (the state dict).
+    ``gpu`` is accepted for signature compatibility: the head always runs on the current HIP device."""
+    return load_segmenter(checkpoint, setup_modules, train, trainable=False)
 
 
 @torch.no_grad()

@@ -668,22 +668,32 @@ int cae_door_hold(cae_door_t *door, int on);
  * cae_seg_config: level_channels[i] = channels of level i's unit, up_channels[i] = output channels of its transposed
  * convolution (i < levels - 1; must equal level_channels[i + 1]); the bottleneck's transposed convolution writes
  * level_channels[0]; bridge_channels[i] = channels of bridge i (used when concat_bridges).
- * weights: host arrays in the reference's layouts, in this order (cae_seg_weight_count of them); [..] only with
- * batch_norm, {..} only with concat_bridges:
- *   bottleneck: _c1.weight [_bn1.weight _bn1.bias] _c2.weight [_bn2.weight _bn2.bias] _up_sample.weight _up_sample.bias
- *   level i:    {[_bn1.weight _bn1.bias] _c2.weight [_bn2.weight _bn2.bias]}  (bridges_projection.i)
- *               _c1.weight [_bn1.weight _bn1.bias] _c2.weight [_bn2.weight _bn2.bias]
- *               _up_sample.weight _up_sample.bias  (i < levels - 1)                       (synthesis_track.i)
- *   fc.weight fc.bias */
+ * The stages (one per convolution, in launch order) and the order of the weights are what cae_seg_plan returns: the
+ * weights are host arrays in the reference's layouts, stage after stage, n_weights per stage as
+ * [_bn1 gamma beta of the bridge's projection] weight [bias] [gamma beta of the GroupNorm behind it]. */
 typedef struct cae_seg cae_seg_t;
 typedef struct {
     int channels_bn, seg_channels_bn, levels, num_classes, concat_bridges, batch_norm;
     int bridge_channels[8], level_channels[8], up_channels[8];
 } cae_seg_config;
-/* Optional taps (tests): per stage s in launch order (cae_seg_stage_count: bottleneck _c1, _c2, _up_sample; per level
- * {projection _c2} _c1 _c2 [_up_sample]; fc) raw[s] receives the stage's raw output as NCHW fp32 and ab[s] the (a, b)
- * pairs computed from it, (n, 8 ceil(cout / 8), 2) floats (stages that feed no normalisation write none); bridge_ab[i]
- * receives the pairs of bridge i, (n, 8 ceil(c / 8), 2).  Any entry may be NULL. */
+/* One stage of the head.  up: the 2x2 stride-2 transposed convolution (ks 1).  norm: a GroupNorm + ReLU follows (applied
+ * by the consumer; it has weights only with batch_norm).  bridge: source A is bridge i through the projection's _bn1 and
+ * ReLU, -1 otherwise.  src_a_stage / src_b_stage: the stage whose output the source is (A is contracted first); -1: the
+ * latents or a bridge, -2: no such source.  src_a_transformed: A is read through its producer's (a, b) and ReLU; B never
+ * is.  n_weights: the arrays the stage owns, in the order above. */
+typedef struct {
+    int ks, cin_a, cin_b, cout, up, biased, norm, bridge, src_a_stage, src_b_stage, src_a_transformed, n_weights;
+} cae_seg_stage_info;
+/* Needs no device.  Returns the number of stages and fills up to `capacity` records (out may be NULL: just counts), or
+ * CAE_ERR_ARG for a config cae_seg_create refuses.  cae_seg_weight_count is the sum of n_weights. */
+int cae_seg_plan(const cae_seg_config *cfg, cae_seg_stage_info *out, int capacity);
+/* (tests) bytes of the handle's eight workspaces for one cae_seg_forward(n, lh, lw), before rounding; no device.  In
+ * order: latents as C8, the two running-feature buffers, the upsampled features, the bridge as C8, its projection, the
+ * four (a, b) slots, the statistics partials. */
+int cae_seg_workspace_bytes(const cae_seg_config *cfg, int n, int lh, int lw, size_t *out /* 8 */);
+/* Optional taps (tests): per stage s of cae_seg_plan raw[s] receives the stage's raw output as NCHW fp32 and ab[s] the
+ * (a, b) pairs computed from it, (n, 8 ceil(cout / 8), 2) floats (stages without norm write none); bridge_ab[i] receives
+ * the pairs of bridge i, (n, 8 ceil(c / 8), 2).  Any entry may be NULL. */
 typedef struct {
     float **raw, **ab, **bridge_ab;
 } cae_seg_taps;

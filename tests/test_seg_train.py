@@ -85,9 +85,10 @@ def _head(name, cls=None, **kw):
     return m.to(DEV), cfg, sd, y_q.to(DEV), [b.to(DEV) for b in brg]
 
 
-def test_set_weights_gives_the_logits_of_a_fresh_handle():
+@pytest.mark.parametrize('name', sorted(SR.GOLDEN_CONFIGS))
+def test_set_weights_gives_the_logits_of_a_fresh_handle(name):
     from cnn_autoencoder_amd import segmenters
-    m, cfg, sd, y_q, brg = _head('a')
+    m, cfg, sd, y_q, brg = _head(name)
     with torch.no_grad():
         m(y_q, brg)  # creates the handle from the host
         for i, p in enumerate(m.parameters()):

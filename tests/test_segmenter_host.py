@@ -1,6 +1,7 @@
 """Host side of the segmentation head (cnn_autoencoder_amd/segmenters.py): the restatement against the reference's
-golden stages, the module surface (state dict keys, kwargs, errors), the weight packers with hand-worked answers, the
-judge of the GPU tests' bounds, and the packers under AddressSanitizer + UBSan."""
+golden stages, the module surface (state dict keys, kwargs, errors), the library's stage plan against the module's (stages,
+weight order, workspace sizes, refused configs), the weight packers with hand-worked answers, the judge of the GPU tests'
+bounds, and the packers under AddressSanitizer + UBSan."""
 import ctypes
 import math
 import os
@@ -116,6 +117,158 @@ def test_value_errors_and_not_implemented():
         criteria.setup_forward_func(('class_model',))
     out = criteria.setup_forward_func(())(y, {})
     assert out['s_pred'] is None and out['s_aux_pred'] is None
+
+
+# ----------------------------------------------------------------------------------------------- the stage plan
+class _StageInfo(ctypes.Structure):  # cae_seg_stage_info
+    _fields_ = [(k, ctypes.c_int) for k in ('ks', 'cin_a', 'cin_b', 'cout', 'up', 'biased', 'norm', 'bridge', 'src_a_stage',
+                                            'src_b_stage', 'src_a_transformed', 'n_weights')]
+
+
+CAE_ERR_ARG = -1
+_SMALL = dict(channels_bn=12, channels_net=10, seg_channels_net=3, seg_channels_bn=20, num_classes=2)
+PLAN_CONFIGS = dict({name: c[0] for name, c in SR.GOLDEN_CONFIGS.items()}, defaults={},
+                    **{f'L{L}-concat{int(cat)}-bn{int(bn)}': dict(_SMALL, compression_level=L, concat_bridges=cat, batch_norm=bn)
+                       for L in (1, 8) for cat in (False, True) for bn in (False, True)})
+_PLANNED = {}
+
+
+def _planned(name):
+    """-> (the JNet of PLAN_CONFIGS[name], its cae_seg_config, the library's stage records), built once"""
+    if name not in _PLANNED:
+        from cnn_autoencoder_amd import _lib
+        m = _seg().JNet(**PLAN_CONFIGS[name])
+        cfg = m._config()
+        L = _lib.lib()
+        n = L.cae_seg_plan(ctypes.byref(cfg), None, 0)
+        assert n > 0
+        out = (_StageInfo * n)()
+        assert L.cae_seg_plan(ctypes.byref(cfg), out, n) == n
+        short = (_StageInfo * 2)()  # a smaller capacity: the count all the same, the first records only
+        assert L.cae_seg_plan(ctypes.byref(cfg), short, 2) == n and bytes(short) == bytes(out)[:ctypes.sizeof(short)]
+        _PLANNED[name] = (m, cfg, list(out))
+    return _PLANNED[name]
+
+
+def _weight_shape(r):
+    return (r.cin_a, r.cout, 2, 2) if r.up else (r.cout, r.cin_a + r.cin_b, r.ks, r.ks)
+
+
+@pytest.mark.parametrize('name', sorted(PLAN_CONFIGS))
+def test_library_plan_is_the_modules_stage_plan(name):
+    """cae_seg_plan (csrc/cae_seg.hip, no device) against JNet.stage_plan(), stage by stage"""
+    m, cfg, recs = _planned(name)
+    plan = m.stage_plan()
+    assert len(recs) == len(plan)
+    for s, (r, st) in enumerate(zip(recs, plan)):
+        what = (name, s, st['name'])
+        assert r.ks == st['ks'] and bool(r.up) == st['up'] and (r.cin_b == 0 or not r.up), what
+        assert _weight_shape(r) == tuple(st['weight'].shape), what
+        assert bool(r.biased) == (st['bias'] is not None), what
+        assert bool(r.norm) == st['has_ab'] and (bool(r.norm) and bool(cfg.batch_norm)) == (st['norm'] is not None), what
+        srcs = []
+        if r.src_a_stage != -2:
+            srcs.append(('bridge', r.bridge) if r.bridge >= 0 else ('latent',) if r.src_a_stage == -1 else
+                        ('raw', r.src_a_stage, bool(r.src_a_transformed)))
+        if r.src_b_stage != -2:
+            srcs.append(('raw', r.src_b_stage, False))
+        assert srcs == [tuple(sr) for sr in st['srcs']], what
+        assert (r.src_a_stage == -2) == (r.cin_a == 0) and (r.src_b_stage == -2) == (r.cin_b == 0), what
+        assert r.bridge == (st['srcs'][0][1] if st['srcs'][0][0] == 'bridge' else -1), what
+        assert r.bridge < 0 or (r.src_a_stage == -1 and r.src_a_transformed == 1), what
+        for stage, cin in ((r.src_a_stage, r.cin_a), (r.src_b_stage, r.cin_b)):
+            assert not 0 <= stage < s or recs[stage].cout == cin, what  # a source has its producer's channels
+            assert stage < s, what
+
+
+@pytest.mark.parametrize('name', sorted(PLAN_CONFIGS))
+def test_weight_order_follows_the_plan(name):
+    """each stage owns n_weights consecutive entries of _weight_list(): [bn1 gamma beta] weight [bias] [gamma beta]"""
+    from cnn_autoencoder_amd import _lib
+    m, cfg, recs = _planned(name)
+    weights, plan, bn, pos = m._weight_list(), m.stage_plan(), bool(cfg.batch_norm), 0
+    for r, st in zip(recs, plan):
+        mine = weights[pos:pos + r.n_weights]
+        pos += r.n_weights
+        want = [(r.cin_a,)] * 2 if (r.bridge >= 0 and bn) else []
+        want += [_weight_shape(r)] + [(r.cout,)] * int(r.biased) + [(r.cout,)] * (2 if (r.norm and bn) else 0)
+        assert [tuple(w.shape) for w in mine] == want, (name, st['name'])
+        assert mine[2 if (r.bridge >= 0 and bn) else 0] is st['weight'], (name, st['name'])
+        if r.bridge >= 0 and bn:
+            bn1 = m.bridges_projection[r.bridge]._bn1
+            assert mine[0] is bn1.weight and mine[1] is bn1.bias
+        if r.biased:
+            assert mine[-1] is st['bias']
+        if r.norm and bn:
+            assert mine[-2] is st['norm'].weight and mine[-1] is st['norm'].bias
+    assert pos == len(weights) == _lib.lib().cae_seg_weight_count(ctypes.byref(cfg))
+
+
+def _workspace_before_the_plan(c, n, lh, lw, tx, ty):
+    """cae_seg_forward's own pass over the levels as it stood before it read the plan: bytes of X0 T1 T2 U BC RP AB STATS"""
+    X0, T1, T2, U, BC, RP, AB, STATS = range(8)
+    c8 = lambda ch, hw: n * ((ch + 7) // 8) * hw * 32
+    tiles_of = lambda hh, ww: ((hh + ty - 1) // ty) * ((ww + tx - 1) // tx)
+    need, cpmax, hw0 = [0] * 8, (c.seg_channels_bn + 7) // 8 * 8, lh * lw
+    need[X0] = c8(c.channels_bn, hw0)
+    need[T1] = need[T2] = c8(c.seg_channels_bn, hw0)
+    need[STATS] = tiles_of(lh, lw) * n * cpmax * 12
+    for i in range(c.levels):
+        hw, ch = hw0 << (2 * (i + 1)), c.level_channels[i]
+        for b in (U, T1, T2):
+            need[b] = max(need[b], c8(ch, hw))
+        cpl = (ch + 7) // 8 * 8
+        if c.concat_bridges:
+            need[BC] = max(need[BC], c8(c.bridge_channels[i], hw))
+            need[RP] = max(need[RP], c8(ch, hw))
+            cpmax = max(cpmax, (c.bridge_channels[i] + 7) // 8 * 8)
+        cpmax = max(cpmax, cpl)
+        need[STATS] = max(need[STATS], tiles_of(lh << (i + 1), lw << (i + 1)) * n * cpl * 12)
+    need[AB] = 4 * (n * cpmax * 2) * 4
+    return need
+
+
+@pytest.mark.parametrize('name', sorted(PLAN_CONFIGS))
+def test_workspace_sizes_are_those_before_the_plan(name):
+    """(1, 9, 17) straddles the 8 x 16 output tile"""
+    from cnn_autoencoder_amd import _lib
+    _, cfg, _ = _planned(name)
+    L = _lib.lib()
+    tx, ty = ctypes.c_int(), ctypes.c_int()
+    L.cae_seg_tile(ctypes.byref(tx), ctypes.byref(ty))
+    for n, lh, lw in ((1, 1, 1), (2, 3, 5), (1, 9, 17)):
+        out = (ctypes.c_size_t * 8)()
+        _lib.check(L.cae_seg_workspace_bytes(ctypes.byref(cfg), n, lh, lw, out))
+        assert list(out) == _workspace_before_the_plan(cfg, n, lh, lw, tx.value, ty.value), (name, n, lh, lw)
+    assert L.cae_seg_workspace_bytes(ctypes.byref(cfg), 0, 1, 1, out) == CAE_ERR_ARG
+
+
+def test_refused_configs():
+    """levels 0 or 9, a zero channel count, a level that hands the next one other channels than it takes"""
+    from cnn_autoencoder_amd import _lib
+    L = _lib.lib()
+
+    def refused(**change):
+        cfg = _seg().JNet(**SR.GOLDEN_CONFIGS['a'][0])._config()
+        for k, v in change.items():
+            if isinstance(v, tuple):
+                getattr(cfg, k)[v[0]] = v[1]
+            else:
+                setattr(cfg, k, v)
+        n = 64
+        host = [np.zeros(1 << 16, np.float32)] * n
+        ptrs, handle = (ctypes.c_void_p * n)(*[w.ctypes.data for w in host]), ctypes.c_void_p()
+        got = (L.cae_seg_plan(ctypes.byref(cfg), None, 0), L.cae_seg_weight_count(ctypes.byref(cfg)),
+               L.cae_seg_create(ctypes.byref(cfg), ptrs, n, ctypes.byref(handle)))
+        assert not handle
+        return got
+
+    assert refused()[:2] == (15, 47)  # (the unchanged config is accepted: 3 + 3 * 4 - 1 + 1 stages, 47 arrays)
+    for change in (dict(levels=0), dict(levels=9), dict(channels_bn=0), dict(seg_channels_bn=0), dict(num_classes=0),
+                   dict(level_channels=(1, 0)), dict(bridge_channels=(2, 0)), dict(up_channels=(0, 17))):
+        assert refused(**change) == (CAE_ERR_ARG,) * 3, change
+    with pytest.raises(ValueError):
+        _lib.check(L.cae_seg_plan(None, None, 0))
 
 
 # ----------------------------------------------------------------------------------------------- packers
