@@ -1,8 +1,9 @@
 """Training the compressed-domain segmentation head: the reference trains ``seg_model`` with the codec frozen
 (``_taskutils.py:46-110``) under the ``BCEWithLogits`` / ``CrossEntropy`` losses of ``criteria/_classification.py``.
 
-``JNetTrain`` is ``segmenters.JNet`` with a backward pass.  The forward is the inference head's one library call
-(``cae_seg_forward`` with taps: every stage's raw output and (a, b) pair is kept); the backward walks ``stage_plan()`` in
+``JNetTrain`` is ``segmenters.JNet`` with a backward pass.  Without autograd the forward is the inference head's one
+library call; under autograd it walks ``stage_plan()`` over ``cae_seg_conv2d`` with every weight scaled by a power of two
+before the f16 split (``_forward_taps``) and keeps every stage's raw output and (a, b) pair; the backward walks the plan in
 reverse over per-operation entry points on NCHW fp32 tensors (csrc/cae_seg_train.hip, csrc/cae_kernels_seg_train.hpp):
 
     cae_seg_wgrad               weight gradients, f16x3 on the MFMA with the contraction over pixels
@@ -15,12 +16,15 @@ device.  ``y_q`` and the bridges are constants: joint training of codec and head
 
 Gradient scale.  The f16x3 kernels need |v| <= 65504 and lose relative precision below about 6e-5, and the logit
 gradients of a mean-reduced loss are far smaller.  The backward is linear in g_logits, so it reads m = max|g_logits| once
-(the step's one synchronisation, together with the forward's range ticket) and propagates s g with s = 2^-floor(log2 m).
+(the step's one synchronisation) and propagates s g with s = 2^-floor(log2 m).
 One scale per step does not suffice: without normalisation the gradients shrink stage by stage until their small entries
 fall into the f16 subnormals (the 'nobn' golden configuration missed its bound by 1.8 on the first projection's weight).
 So every stage's gradient is brought back to max|G| in [1, 2) by a further power of two, computed and applied on the
 device with no further synchronisation, and every parameter gradient is multiplied by the inverse of the scale it was
-computed under; all these multiplications are exact.  A staged value of the backward outside
+computed under; all these multiplications are exact.  The weight of every data gradient is scaled the same way, to
+max|w| in [2^14, 2^15): the low half of an f16 split below 2^-14 is subnormal, so a weight near 0.01 (the canonical
+widths) kept 2^-18 of itself instead of 2^-22, and the canonical head missed its bound by 1.41 until this was done here and in the training forward.
+A staged value of the backward outside
 the f16 range raises a device word that ``JNetTrain.check_backward()`` / ``train_step`` read (FloatingPointError).
 """
 from __future__ import annotations
@@ -146,6 +150,9 @@ def channel_sums(g: torch.Tensor) -> torch.Tensor:
 
 
 # ---- the head's autograd function ----------------------------------------------------------------------------------
+WEIGHT_EXP = 15  # the data gradient reads its weight scaled to max|w| in [2^14, 2^15), below the f16 maximum 65504
+
+
 def grad_scale(m: float) -> float:
     """s = 2^-floor(log2 m): s m lies in [1, 2)"""
     return math.ldexp(1.0, -(math.frexp(m)[1] - 1))
@@ -230,10 +237,62 @@ class JNetTrain(JNet):
             raise ValueError('training the head needs its parameters as contiguous fp32 tensors on the device (.cuda())')
         return _HeadFunction.apply(self, x, len(brg), *brg, *params), None
 
+    def _pairs(self, t: torch.Tensor, norm) -> torch.Tensor:
+        """(a, b) of relu(GroupNorm_C(t)) in the taps' layout, from two-pass double statistics of the planes: a = gamma
+        rstd, b = fma(-mean, a, beta); norm None (no normalisation): (1, 0).  Padding channels (0, 0)."""
+        n, c = t.shape[:2]
+        ab = torch.zeros((n, (c + 7) // 8 * 8, 2), dtype=torch.float32, device=t.device)
+        if norm is None:
+            ab[:, :c, 0] = 1.0
+            return ab
+        mean = t.mean(dim=(2, 3), dtype=torch.float64)  # (the reductions convert as they read: no double copy of t)
+        var = (t - mean.float()[:, :, None, None]).square_().mean(dim=(2, 3), dtype=torch.float64)
+        a = (norm.weight.detach().double()[None] * torch.rsqrt(var + segmenters.EPS)).float()
+        ab[:, :c, 0] = a
+        ab[:, :c, 1] = (norm.bias.detach().double()[None] - mean * a.double()).float()
+        return ab
+
     def _forward_taps(self, x, brg):
-        """cae_seg_forward with every tap, asynchronous: the range ticket is checked by the backward"""
-        logits, saved, ticket = self._launch(x, brg, taps=True)
-        return logits, dict(saved, ticket=ticket)
+        """The training forward, stage by stage over ``cae_seg_conv2d`` (the forward kernel on freshly packed weights) with
+        every weight scaled to max|w| in [2^14, 2^15) before the split and the output scaled back: the fused
+        ``cae_seg_forward`` packs the weights as they are, and weights below 2^-3 (every canonical layer) then keep 2^-25
+        absolute instead of 2^-22 relative, which the gradients of the canonical head do not tolerate.  A
+        stage over two concatenated sources is the sum of two convolutions.  -> (logits, taps as JNet._taps lays them
+        out); asynchronous, the range word joins the backward's."""
+        plan, bn = self.stage_plan(), self._batch_norm
+        flag = new_flag(x.device)
+        one = torch.ones((), dtype=torch.float32, device=x.device)
+        raw: List[torch.Tensor] = []
+        ab: List[Optional[torch.Tensor]] = []
+        bab = [self._pairs(b, self.bridges_projection[i]._bn1 if bn else None) for i, b in enumerate(brg)]
+        for st in plan:
+            w, bias = st['weight'].detach(), st['bias']
+            if st['up']:  # four pointwise matrices, row 4 co + 2 dy + dx, then the pixel shuffle
+                cin, cout = w.shape[:2]
+                w = w.permute(1, 2, 3, 0).reshape(4 * cout, cin, 1, 1)
+                bias = None if bias is None else bias.detach().repeat_interleave(4)
+            elif bias is not None:
+                bias = bias.detach()
+            sw = torch.ldexp(one, WEIGHT_EXP - torch.frexp(w.abs().max())[1])
+            out, c0 = None, 0
+            for src in st['srcs']:
+                if src[0] == 'latent':
+                    t, t_ab = x, None
+                elif src[0] == 'bridge':
+                    t, t_ab = brg[src[1]], bab[src[1]]
+                else:
+                    t, t_ab = raw[src[1]], (ab[src[1]] if src[2] else None)
+                part = conv2d(t, (w[:, c0:c0 + t.size(1)] * sw).contiguous(), None if (bias is None or c0) else bias * sw,
+                              flag, t_ab)
+                out = part if out is None else out.add_(part)
+                c0 += t.size(1)
+            out.mul_(1.0 / sw)
+            raw.append(F.pixel_shuffle(out, 2) if st['up'] else out)
+            ab.append(self._pairs(raw[-1], st['norm']) if st['has_ab'] else None)
+        self._bwd_flags.append(flag)
+        # (a copy: the function's output must not be the tensor its own context keeps, or every step's taps wait for the
+        # cycle collector)
+        return raw[-1].clone(), dict(plan=plan, raw=raw, ab=ab, bridge_ab=bab, ticket=None)
 
     def _backward(self, x, brg, saved, g_logits) -> List[Optional[torch.Tensor]]:
         plan, raw, ab, bab = saved['plan'], saved['raw'], saved['ab'], saved['bridge_ab']
@@ -241,7 +300,8 @@ class JNetTrain(JNet):
         g = g_logits.detach().to(torch.float32).contiguous()
         m = float(g.abs().max()) if g.numel() else 0.0  # the step's one synchronisation
         self._check_weights()
-        _lib.check(_lib.lib().cae_seg_range_check(self._handle.ptr, saved['ticket']))  # FloatingPointError
+        if saved['ticket'] is not None:
+            _lib.check(_lib.lib().cae_seg_range_check(self._handle.ptr, saved['ticket']))  # FloatingPointError
         if not math.isfinite(m):
             raise FloatingPointError('segmentation head: the gradient of the logits is not finite')
         if m == 0.0:
@@ -284,7 +344,10 @@ class JNetTrain(JNet):
                 wd = w.detach().flip(2, 3).transpose(0, 1).contiguous()
             if not any(sr[2] for sr in srcs):
                 continue
-            gv, c0 = conv2d(G, wd, None, flag), 0
+            # the data gradient's weight is brought to max|w| in [2^14, 2^15) like G to [1, 2): at |w| < 2^-3 the low half of
+            # the f16 split is subnormal and keeps 2^-25 absolute, not 2^-22 relative (canonical weights are near 0.01)
+            sw = torch.ldexp(one, WEIGHT_EXP - torch.frexp(wd.abs().max())[1])
+            gv, c0, cum = conv2d(G, wd * sw, None, flag), 0, cum * sw
             for sr, (t, t_ab, want) in zip(st['srcs'], srcs):
                 piece = gv if len(srcs) == 1 else gv[:, c0:c0 + t.size(1)].contiguous()
                 c0 += t.size(1)

@@ -155,6 +155,11 @@ def emu_wgrad(g, srcs, ks, defect=None, border=None):
     double and rounded once.  (Inside a segment the sum is wide: the fp32 accumulation is what C_CONV allows for.)"""
     g = _f32(g)
     n, cout, h, w = g.shape
+    if defect == 'group_of_four_clipped' and w % 8 == 4:
+        # a vectorised row whose second 16-byte group is taken only where the whole 8-pixel half lies inside: the row's last
+        # four pixels of g read as zero (v's are then multiplied by nothing; its halo pixels are read one by one)
+        g = g.copy()
+        g[..., -4:] = 0
     (gh, gl), (vh, vl) = wgrad_operands(g, srcs, ks, defect)
     if defect == 'padding_counted':  # the pixels right of a ragged last step taken from the row's last pixel
         gh, gl = (np.concatenate([t, t[..., -1:]], axis=3) for t in (gh, gl))
@@ -163,7 +168,7 @@ def emu_wgrad(g, srcs, ks, defect=None, border=None):
     segs, per, xs = wgrad_splits(n, h, w, vh.shape[1], cout, ks)
     step = (np.arange(n)[:, None, None] * h + np.arange(h)[None, :, None]) * xs + (np.arange(w) // 16)[None, None, :]
     total = np.zeros((cout, vh.shape[1], ks, ks))
-    for s in range(segs):
+    for s in range(segs - 1 if defect == 'last_segment_dropped' else segs):
         mask = (step // per == s)[:, None].astype(np.float64)
         bh, bl = (None, None) if border is None else SR._split(border)
         part = _corr(gh * mask, vh, ks, bh) + _corr(gh * mask, vl, ks, bl) + _corr(gl * mask, vh, ks, bh)
@@ -205,9 +210,29 @@ def emu_norm_relu_backward(x, a, b, gamma, gv, defect=None):
     mg = np.zeros_like(sg, dtype=np.float32) if defect == 'no_mean_g' else (sg / hw).astype(np.float32)
     mgx = np.zeros_like(sgx, dtype=np.float32) if defect == 'no_mean_gx' else (sgx / hw).astype(np.float32)
     coef = (_f32(gamma)[None, :, None, None] * rstd).astype(np.float32)
+    if defect == 'stale_tail':  # a plane's elements from index 1024 on (its later blocks) see zero plane means
+        tail = (np.arange(hw) >= 1024).reshape(1, 1, h, w)
+        mg, mgx = np.where(tail, np.float32(0), mg), np.where(tail, np.float32(0), mgx)
     inner = ((gu - mg).astype(np.float32).astype(np.float64) - xh.astype(np.float64) * mgx).astype(np.float32)
     gx = (coef * inner).astype(np.float32)
     return gx, sgx.sum(axis=0).ravel().astype(np.float32), sg.sum(axis=0).ravel().astype(np.float32)
+
+
+def emu_channel_sums(g, defect=None):
+    """cae_seg_channel_sums: plane sums in double, the samples added in order, rounded once; 'one_block': the channels of
+    the second and later 256-thread blocks of seg_channel_sums_kernel are left at zero"""
+    g = _f32(g)
+    out = g.reshape(g.shape[0], g.shape[1], -1).astype(np.float64).sum(axis=2).sum(axis=0).astype(np.float32)
+    if defect == 'one_block':
+        out[256:] = 0
+    return out
+
+
+def mask_margin(x, a, b):
+    """the elements whose |a x + b| < 2^-20 (|a x| + |b|): there the mask of the fp32 fma may differ from float64's"""
+    ax = torch.as_tensor(a).double()[:, :, None, None] * torch.as_tensor(x).double()
+    bb = torch.as_tensor(b).double()[:, :, None, None]
+    return (ax + bb).abs() < 2.0 ** -20 * (ax.abs() + bb.abs())
 
 
 def norm_relu_backward_ref(x, a, b, gamma, beta, gv):
@@ -218,9 +243,7 @@ def norm_relu_backward_ref(x, a, b, gamma, beta, gv):
     bd = None if gamma is None else torch.as_tensor(beta).double().requires_grad_(True)
     v = torch.relu(xd if gamma is None else group_norm(xd, gd, bd))
     v.backward(torch.as_tensor(gv).double())
-    ad, bb = torch.as_tensor(a).double()[:, :, None, None], torch.as_tensor(b).double()[:, :, None, None]
-    ax = ad * torch.as_tensor(x).double()
-    margin = (ax + bb).abs() < 2.0 ** -20 * (ax.abs() + bb.abs())
+    margin = mask_margin(x, a, b)
     return xd.grad, None if gamma is None else gd.grad, None if gamma is None else bd.grad, margin
 
 
@@ -235,6 +258,11 @@ def norm_relu_backward_ref32(x, gamma, beta, gv):
 
 # ---------------------------------------------------------------------------------------------------------------------
 # the whole backward in the kernels' order
+# JNetTrain._backward brings every stage's gradient to max|G| in [2^(G_EXP - 1), 2^G_EXP) and the weight of every data
+# gradient to max|w| in [2^(W_EXP - 1), 2^W_EXP) (seg_train.WEIGHT_EXP; None: the weight as it is, a planted defect)
+G_EXP, W_EXP = 1, 15
+
+
 def plan_of(cfg):
     """JNet.stage_plan() from the constructor keys: dict(name, ks, up, norm (prefix or None), srcs)"""
     L, concat = cfg['compression_level'], cfg.get('concat_bridges', False)
@@ -279,9 +307,9 @@ def _unshuffle(g, defect=None):
     return np.ascontiguousarray(g.reshape(n, c * 4, h // 2, w // 2))
 
 
-def emu_backward(cfg, sd, y_q, bridges, target, defect=None):
+def emu_backward(cfg, sd, y_q, bridges, target, defect=None, g_exp=G_EXP, w_exp=W_EXP):
     """-> (loss, {key: gradient}): forward by the float32 restatement, backward through the emulated operations in the
-    order of JNetTrain._backward, every stage's gradient renormalised by a power of two"""
+    order of JNetTrain._backward, every stage's gradient and every data gradient's weight renormalised by a power of two"""
     bn = cfg.get('batch_norm', True)
     logits, stages = SR.jnet(sd, cfg, y_q, bridges, torch.float32)
     lg = logits.clone().requires_grad_(True)
@@ -307,7 +335,7 @@ def emu_backward(cfg, sd, y_q, bridges, target, defect=None):
     for k in reversed(range(len(plan))):
         st, (G, cum) = plan[k], graw.pop(k)
         mx = float(np.abs(G).max())
-        sk = 2.0 ** -(np.frexp(mx)[1] - 1) if mx > 0 else 2.0
+        sk = 2.0 ** (g_exp - np.frexp(mx)[1])
         G, cum = (G * np.float32(sk)).astype(np.float32), cum * sk
         keep = 1.0 if defect == 'scale_kept' else 1.0 / cum
         name, w = st['name'], par[st['name'] + '.weight']
@@ -316,21 +344,25 @@ def emu_backward(cfg, sd, y_q, bridges, target, defect=None):
         if name + '.bias' in par:
             taps = (4 if st['up'] else st['ks'] ** 2) if defect == 'bias_per_tap' else 1
             out[name + '.bias'] = (G.astype(np.float64).sum(axis=(0, 2, 3)) * taps).astype(np.float32) * np.float32(keep)
+        wmax = float(np.abs(w).max())
+        sw = 1.0 if w_exp is None else 2.0 ** (w_exp - np.frexp(wmax)[1])  # the data gradient's weight, scaled likewise
         if st['up']:
             G = _unshuffle(G, defect)
             cin, cout = w.shape[:2]
             gw = emu_wgrad(G, vs, 1).reshape(cout, 2, 2, cin).transpose(3, 0, 1, 2)
             wd = w.reshape(cin, 4 * cout, 1, 1)
-            gv = SR.emu_conv([G], wd)
+            gv = SR.emu_conv([G], wd * np.float32(sw))
         else:
             gw = emu_wgrad(G, vs, st['ks'], defect)
             if gw.shape != w.shape:  # (the swapped defect on a non-square layer)
                 gw = np.zeros_like(w)
-            gv = emu_data_grad(G, w, defect)
+            gv = emu_data_grad(G, w * np.float32(sw), defect)
         out[name + '.weight'] = np.ascontiguousarray(gw) * np.float32(keep)
         if not any(sr[2] for sr in srcs):
             continue
         gv, c0 = gv.astype(np.float32), 0
+        cum = cum * sw
+        keep = 1.0 if defect == 'scale_kept' else 1.0 / cum
         for sr, (x, t, want, norm) in zip(st['srcs'], srcs):
             piece = gv[:, c0:c0 + x.shape[1]]
             c0 += x.shape[1]
