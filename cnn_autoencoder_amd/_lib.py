@@ -171,6 +171,17 @@ SYMBOLS = {
                                  c_size_t, c_void_p]),
     'cae_seg_roc_workspace': (c_size_t, [c_int, c_int, c_int, c_int]),
     'cae_seg_roc_blocks': (c_int, [c_int, c_int, c_int, c_int]),
+    'cae_seg_components': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t,
+                                   c_void_p]),
+    'cae_seg_components_workspace': (c_size_t, [c_int, c_int, c_int]),
+    'cae_seg_object_cover': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    'cae_seg_object_cover_workspace': (c_size_t, [c_int, c_int, c_int]),
+    'cae_seg_object_counts': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_size_t, c_float, c_int, c_void_p,
+                                      c_void_p, c_size_t, c_void_p]),
+    'cae_seg_object_counts_workspace': (c_size_t, [c_int, c_int, c_size_t]),
+    'cae_seg_object_roc_hist': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
+                                        c_void_p, c_void_p, c_size_t, c_void_p]),
+    'cae_seg_object_roc_workspace': (c_size_t, [c_int, c_int, c_int, c_int]),
     'cae_seg_set_weights': (c_int, [c_void_p, c_void_p, c_int, c_void_p]),
     'cae_seg_pack_dev': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p]),
     'cae_seg_conv2d_workspace': (c_size_t, [c_int] * 6),

@@ -15,6 +15,7 @@
 #include <cstdint>
 
 #include "cae_launch.hpp"
+#include "cae_seg_roc_key.hpp"
 
 namespace cae {
 namespace {
@@ -35,15 +36,6 @@ struct RocArgs {
     uint32_t *partial;      // [n][bx][2][B]
     int h, w, bits, bx;
 };
-
-// order-preserving key of an fp32 logit, cut to its top `bits` bits.  -0 counts as +0 and NaN as key 0; in integers, so
-// that no floating-point mode (denormals) has a say: x + 0.0f changes no other value
-__device__ __forceinline__ uint32_t roc_bin(float x, int shift) {
-    uint32_t u = __float_as_uint(x);
-    if (u == 0x80000000u) u = 0;
-    const uint32_t key = (u >> 31) ? ~u : (u | 0x80000000u);
-    return (u & 0x7fffffffu) > 0x7f800000u ? 0u : key >> shift;
-}
 
 // one pixel per lane into the block's histogram; `word` = positive * B + bin
 __device__ __forceinline__ void roc_add(uint32_t *hist, bool on, uint32_t word) {

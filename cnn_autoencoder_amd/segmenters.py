@@ -17,6 +17,8 @@ The head's structure is stated once, in the library (``cae_seg_plan``); ``JNet.s
 metrics; ``cae_seg_predict``, csrc/cae_seg_predict.hip); ``slide.SlideCoder.segment_batches`` and ``zarrio.segment_image``
 run whole slides through codec, head and prediction.  ``roc_histogram`` / ``roc_from_histogram`` give the threshold-free
 results of a one-class head, ROC curve and AUC, from exact logit histograms (``cae_seg_roc_hist``, csrc/cae_seg_roc.hip).
+``components`` / ``object_cover`` / ``object_counts`` / ``object_roc_histogram`` give the object-level half of the harness:
+connected objects of the target, their boxes, and counts and histogram over the pixels of all boxes (csrc/cae_seg_objects.hip).
 
 Unlike the reference (whose in-place ReLU overwrites the caller's bridges when ``batch_norm=False``) the head never
 writes its inputs.
@@ -528,13 +530,7 @@ def roc_histogram(logits: torch.Tensor, target: torch.Tensor, extent=None, bits:
     logits = logits.contiguous()  # (a view of a larger buffer at any element offset is read in place)
     dev = logits.device
     tgt = target.to(dev).contiguous()
-    ext = None
-    if extent is not None:
-        ext = extent if isinstance(extent, torch.Tensor) else torch.as_tensor(np.asarray(extent))
-        if ext.is_floating_point() or ext.dtype == torch.bool or tuple(ext.shape) != (n, 2):
-            raise ValueError(f'expected an extent of {n} x 2 integers (rows, cols), got {ext.dtype} {tuple(ext.shape)}')
-        i32 = torch.iinfo(torch.int32)
-        ext = ext.clamp(i32.min, i32.max).to(device=dev, dtype=torch.int32).contiguous()
+    ext = _extent_arg(extent, n, dev)
     m = n if per_image else 1
     with torch.cuda.device(dev):
         if n == 0:
@@ -588,3 +584,159 @@ def roc_from_histogram(hist) -> Dict:
             ties += pb * nb
         auc, slack = area / (2 * P * N), ties / (2 * P * N)
     return dict(fpr=fpr, tpr=tpr, thresholds=thr, score_thresholds=score_thr, auc=auc, auc_slack=slack, p=P, n=N)
+
+
+# ---- object-level results: connected objects of the target, their boxes' cover, weighted counts (csrc/cae_seg_objects.hip)
+def _check_planes(n: int, h: int, w: int):
+    if n and (h < 1 or w < 1):
+        raise ValueError(f'empty planes: {n} x {h} x {w}')
+    if 3 * min(h, w) > 65535 or h * w > 2 ** 31 - 1:
+        raise ValueError(f'planes of {h} x {w} pixels are too large: the cover of a pixel is held in 16 bits '
+                         f'(3 min(H, W) <= 65535) and a label in 32')
+
+
+def _extent_arg(extent, n: int, dev):
+    """(N,2) integers (rows, cols), on the device as the int32 the library reads (clamped there to the plane), or None"""
+    if extent is None:
+        return None
+    ext = extent if isinstance(extent, torch.Tensor) else torch.as_tensor(np.asarray(extent))
+    if ext.is_floating_point() or ext.dtype == torch.bool or tuple(ext.shape) != (n, 2):
+        raise ValueError(f'expected an extent of {n} x 2 integers (rows, cols), got {ext.dtype} {tuple(ext.shape)}')
+    i32 = torch.iinfo(torch.int32)
+    return ext.clamp(i32.min, i32.max).to(device=dev, dtype=torch.int32).contiguous()
+
+
+def _workspace(nbytes: int, dev) -> torch.Tensor:
+    return torch.empty(max((int(nbytes) + 7) // 8, 1), dtype=torch.int64, device=dev)
+
+
+@torch.no_grad()
+def components(target: torch.Tensor, extent=None, by_value: bool = False):
+    """uint8 label planes (N,H,W) on the device, read as they stand -> (labels (N,H,W) int32, n_objects (N,) int64):
+    the 8-connected objects of every plane (cae_seg_components; asynchronous on the current stream).  Foreground is
+    ``target > 0`` inside ``extent`` ((N,2) integers (rows, cols), clamped to the plane; None: whole planes); with
+    ``by_value`` neighbours join only when their values are equal (skimage.measure.label of an integer image), otherwise
+    all foreground counts as one value (the reference's one-class case).  A label is 0 on background, else 1 + the
+    smallest row-major index of its object; objects never reach across planes."""
+    if not isinstance(target, torch.Tensor) or target.dim() != 3 or target.dtype != torch.uint8:
+        raise ValueError('expected uint8 label planes (N,H,W) on the device')
+    n, h, w = target.shape
+    _check_planes(n, h, w)
+    _lib.require_gpu()
+    if not target.is_cuda:
+        raise ValueError('expected uint8 label planes (N,H,W) on the device')
+    dev = target.device
+    ext = _extent_arg(extent, n, dev)
+    tgt = target.contiguous()  # (a view of a larger buffer at any byte offset is read in place)
+    with torch.cuda.device(dev):
+        labels = torch.empty((n, h, w), dtype=torch.int32, device=dev)
+        count = torch.empty((n,), dtype=torch.int64, device=dev)
+        if n:
+            L = _lib.lib()
+            ws = _workspace(L.cae_seg_components_workspace(n, h, w), dev)
+            _lib.check(L.cae_seg_components(tgt.data_ptr(), None if ext is None else ext.data_ptr(), n, h, w,
+                                            int(bool(by_value)), labels.data_ptr(), count.data_ptr(), ws.data_ptr(),
+                                            ws.numel() * 8, _lib.stream_ptr()))
+    return labels, count
+
+
+@torch.no_grad()
+def object_cover(labels: torch.Tensor, extent=None) -> torch.Tensor:
+    """labels (N,H,W) int32 of ``components`` (and its ``extent``) -> cover (N,H,W) uint16 on the device: the number of
+    objects whose box holds the pixel (cae_seg_object_cover; asynchronous on the current stream).  The box of an object
+    is its rows and columns widened by one pixel on every side, clipped to the extent (test_cae_classifier.py:101-109).
+    The reference concatenates the pixels of all boxes, so its object-level sums are the image-level sums weighted by
+    this cover."""
+    if not isinstance(labels, torch.Tensor) or labels.dim() != 3 or labels.dtype != torch.int32:
+        raise ValueError('expected int32 labels (N,H,W) on the device')
+    n, h, w = labels.shape
+    _check_planes(n, h, w)
+    _lib.require_gpu()
+    if not labels.is_cuda:
+        raise ValueError('expected int32 labels (N,H,W) on the device')
+    dev = labels.device
+    ext = _extent_arg(extent, n, dev)
+    lab = labels.contiguous()
+    with torch.cuda.device(dev):
+        cover = torch.empty((n, h, w), dtype=torch.uint16, device=dev)
+        if n:
+            L = _lib.lib()
+            ws = _workspace(L.cae_seg_object_cover_workspace(n, h, w), dev)
+            _lib.check(L.cae_seg_object_cover(lab.data_ptr(), None if ext is None else ext.data_ptr(), n, h, w,
+                                              cover.data_ptr(), ws.data_ptr(), ws.numel() * 8, _lib.stream_ptr()))
+    return cover
+
+
+def _check_cover(cover, n: int, hw: int, dev) -> torch.Tensor:
+    if not isinstance(cover, torch.Tensor) or cover.dtype != torch.uint16 or cover.numel() != n * hw:
+        raise ValueError(f'expected a uint16 cover of {n} x {hw} weights')
+    return cover.to(dev).contiguous()
+
+
+@torch.no_grad()
+def object_counts(logits: torch.Tensor, target: torch.Tensor, cover: torch.Tensor, threshold: float = 0.5,
+                  threshold_on: str = 'scores', top_k: int = 5) -> torch.Tensor:
+    """The counts of ``predict`` with every pixel counted ``cover`` times -> (N,6) int64 [tp, tn, fp, fn, p, tp_top] on
+    the device (cae_seg_object_counts; asynchronous on the current stream).  logits (N,C,...) fp32 on the device, target
+    and cover uint8 / uint16 of N x pixels entries; threshold, threshold_on and top_k as in ``predict``.  With the cover
+    of ``object_cover`` these are the reference's object-level counts; any uint16 weights are summed exactly."""
+    t = threshold_logit(threshold, threshold_on)  # ValueError before anything else
+    if int(top_k) != top_k or top_k < 1:
+        raise ValueError(f'top_k must be a positive integer, got {top_k!r}')
+    _lib.require_gpu()
+    if not isinstance(logits, torch.Tensor) or logits.dim() < 2 or logits.dtype != torch.float32 or not logits.is_cuda:
+        raise ValueError('expected fp32 logits (N,C,...) on the device')
+    if not 1 <= logits.size(1) <= 256:
+        raise ValueError(f'{logits.size(1)} classes outside 1..256')
+    logits = logits.contiguous()  # (a view of a larger buffer at any element offset is read in place)
+    n, c, space = logits.size(0), logits.size(1), tuple(logits.shape[2:])
+    hw = int(np.prod(space)) if space else 1
+    if n and hw < 1:
+        raise ValueError(f'empty planes: {tuple(logits.shape)}')
+    dev = logits.device
+    if not isinstance(target, torch.Tensor) or target.dtype != torch.uint8 or target.numel() != n * hw:
+        raise ValueError(f'expected a uint8 target of {n} x {hw} labels')
+    tgt, cov = target.to(dev).contiguous(), _check_cover(cover, n, hw, dev)
+    with torch.cuda.device(dev):
+        counts = torch.empty((n, len(COUNT_KEYS)), dtype=torch.int64, device=dev)
+        if n:
+            L = _lib.lib()
+            ws = _workspace(L.cae_seg_object_counts_workspace(n, c, hw), dev)
+            _lib.check(L.cae_seg_object_counts(logits.data_ptr(), tgt.data_ptr(), cov.data_ptr(), n, c, hw, t, int(top_k),
+                                               counts.data_ptr(), ws.data_ptr(), ws.numel() * 8, _lib.stream_ptr()))
+    return counts
+
+
+@torch.no_grad()
+def object_roc_histogram(logits: torch.Tensor, target: torch.Tensor, cover: torch.Tensor, extent=None,
+                         bits: int = ROC_BITS, per_image: bool = False) -> torch.Tensor:
+    """``roc_histogram`` with every pixel adding ``cover`` (uint16, N x H x W) instead of 1 (cae_seg_object_roc_hist;
+    asynchronous on the current stream): with the cover of ``object_cover`` the histogram of the pixels of all object
+    boxes.  Same arguments, layout and bins otherwise; ``roc_from_histogram`` takes it as it is."""
+    bits = _check_roc_bits(bits)
+    _lib.require_gpu()
+    if not isinstance(logits, torch.Tensor) or logits.dim() != 4 or logits.dtype != torch.float32 or not logits.is_cuda:
+        raise ValueError('expected fp32 logits (N,1,H,W) on the device')
+    if logits.size(1) != 1:
+        raise ValueError(f'the ROC histogram is built for a one-class head, got {logits.size(1)} classes')
+    n, _, h, w = logits.shape
+    if n and (h < 1 or w < 1):
+        raise ValueError(f'empty planes: {tuple(logits.shape)}')
+    if not isinstance(target, torch.Tensor) or target.dtype != torch.uint8 or target.numel() != n * h * w:
+        raise ValueError(f'expected a uint8 target of {n} x {h} x {w} labels')
+    logits = logits.contiguous()  # (a view of a larger buffer at any element offset is read in place)
+    dev = logits.device
+    tgt, cov = target.to(dev).contiguous(), _check_cover(cover, n, h * w, dev)
+    ext = _extent_arg(extent, n, dev)
+    m = n if per_image else 1
+    with torch.cuda.device(dev):
+        if n == 0:
+            return torch.zeros((m, 2, 1 << bits) if per_image else (2, 1 << bits), dtype=torch.int64, device=dev)
+        L = _lib.lib()
+        hist = torch.empty((m, 2, 1 << bits), dtype=torch.int64, device=dev)
+        ws = _workspace(L.cae_seg_object_roc_workspace(n, h, w, bits), dev)
+        _lib.check(L.cae_seg_object_roc_hist(logits.data_ptr(), tgt.data_ptr(), cov.data_ptr(),
+                                             None if ext is None else ext.data_ptr(), n, h, w, bits,
+                                             int(bool(per_image)), hist.data_ptr(), ws.data_ptr(), ws.numel() * 8,
+                                             _lib.stream_ptr()))
+    return hist if per_image else hist[0]

@@ -575,7 +575,7 @@ class SlideCoder:
     # ---- pipelined segmentation of compressed tiles ---------------------------------------------------------
     def segment_batches(self, payload_batches, h: int, w: int, seg_model, targets=None, threshold: float = 0.5,
                         threshold_on: str = 'scores', top_k: int = 5, scores: bool = False, keep_logits: bool = False,
-                        to_host: bool = False, roc_bits=None, extents=None):
+                        to_host: bool = False, roc_bits=None, extents=None, object_level: bool = False):
         """Generator: for every list of chunk byte strings (the 16-byte '>QQ' tile size in front of the rANS payload, as
         ZarrArray.read_chunk_bytes returns and segmenters.segment_compressed takes them; tiles of h x w pixels) the
         prediction of the segmentation head ``seg_model`` (a JNet in eval mode), in order:
@@ -587,6 +587,12 @@ class SlideCoder:
         batch's logit histograms of negatives and positives (segmenters.roc_histogram); ``extents``: an iterable beside
         the batches of (n, 2) integers (rows, cols), the part of each tile that the histogram counts.  A histogram is
         there to be summed over the slide (it adds exactly) and stays a CUDA tensor with ``to_host`` too.
+        ``object_level`` (needs ``targets``): each result gains 'n_objects' (n,) int64, the connected objects of every
+        label map (segmenters.components; by value for a head of several classes), and 'object_counts' (n,6) int64, the
+        counts over the pixels of all object boxes (segmenters.object_cover, object_counts); with ``roc_bits`` also
+        'object_roc_hist', the histogram over those pixels (segmenters.object_roc_histogram; stays on the device).
+        ``extents`` then bound objects and boxes too.  All of it runs behind cae_seg_predict on the main stream, on the
+        labels that are on the device already.
 
         The stages of decompress_batches: a worker range-decodes up to `depth` batches ahead (host or device coder), the
         symbols cross on the H2D side stream; then, on the main stream, dequantiser, synthesis track with its bridges
@@ -596,8 +602,8 @@ class SlideCoder:
 
         ValueError before any work: seg_model in training mode, a head built for other latent channels than the
         codec's, a bad threshold / threshold_on / top_k, roc_bits without targets, for a head of several classes or
-        outside 8..14, extents without roc_bits; and for every batch, before it is handed to the decoder: a chunk
-        whose header is not (h, w) -- chunks of mixed tile sizes."""
+        outside 8..14, object_level without targets, extents without roc_bits or object_level; and for every batch,
+        before it is handed to the decoder: a chunk whose header is not (h, w) -- chunks of mixed tile sizes."""
         from .codec import _module
         from . import segmenters
         seg = _module(seg_model)
@@ -617,15 +623,21 @@ class SlideCoder:
                 raise ValueError('roc_bits needs targets: the histograms are those of the labelled pixels')
             if seg._num_classes != 1:
                 raise ValueError(f'roc_bits needs a one-class head, this one has {seg._num_classes} classes')
-            roc = (segmenters._check_roc_bits(roc_bits), iter(extents) if extents is not None else None)
-        elif extents is not None:
-            raise ValueError('extents bound the ROC histograms: they need roc_bits')
+            roc = segmenters._check_roc_bits(roc_bits)
+        elif extents is not None and not object_level:
+            raise ValueError('extents bound the ROC histograms and the object boxes: they need roc_bits or object_level')
+        if object_level:
+            if targets is None:
+                raise ValueError('object_level needs targets: the objects are those of the label maps')
+            segmenters._check_planes(1, int(h), int(w))
         return self._segment_batches(payload_batches, int(h), int(w), seg, targets,
                                      dict(threshold=threshold, threshold_on=threshold_on, top_k=int(top_k), scores=scores),
-                                     keep_logits, to_host, roc)
+                                     keep_logits, to_host, roc, iter(extents) if extents is not None else None,
+                                     bool(object_level))
 
     @torch.no_grad()
-    def _segment_batches(self, payload_batches, h, w, seg, targets, how, keep_logits, to_host, roc=None):
+    def _segment_batches(self, payload_batches, h, w, seg, targets, how, keep_logits, to_host, roc=None, extents=None,
+                         object_level=False):
         import struct
         from concurrent.futures import ThreadPoolExecutor
         from . import _lib, segmenters
@@ -650,7 +662,8 @@ class SlideCoder:
             cls = res['cls']
             out = self._ring('c').take(k, tuple(cls.shape), torch.uint8)
             _lib.check(_lib.lib().cae_copy_to_host(out.data_ptr(), cls.data_ptr(), cls.numel()))
-            stay = {key: res[key] for key in ('roc_hist',) if key in res}  # there to be summed: left on the device
+            # there to be summed: left on the device
+            stay = {key: res[key] for key in ('roc_hist', 'object_roc_hist') if key in res}
             host = {key: None if v is None else v.cpu().numpy() for key, v in res.items() if key != 'cls' and key not in stay}
             _clock(tm, 'copy', t0)
             return dict(host, cls=out.numpy(), **stay)
@@ -681,8 +694,18 @@ class SlideCoder:
                 target = torch.as_tensor(np.ascontiguousarray(target)).to(main.device)
             res = segmenters.predict(logits, target, **how)
             res['logits'] = logits if keep_logits else None
+            if extent is not None:  # on the device once, for every call below
+                extent = segmenters._extent_arg(extent, n, main.device)
             if roc is not None:
-                res['roc_hist'] = segmenters.roc_histogram(logits, target, extent=extent, bits=roc[0])
+                res['roc_hist'] = segmenters.roc_histogram(logits, target, extent=extent, bits=roc)
+            if object_level:
+                labels, res['n_objects'] = segmenters.components(target.reshape(n, h, w), extent=extent,
+                                                                 by_value=seg._num_classes > 1)
+                cover = segmenters.object_cover(labels, extent=extent)
+                res['object_counts'] = segmenters.object_counts(logits, target, cover, threshold=how['threshold'],
+                                                                threshold_on=how['threshold_on'], top_k=how['top_k'])
+                if roc is not None:
+                    res['object_roc_hist'] = segmenters.object_roc_histogram(logits, target, cover, extent=extent, bits=roc)
             done = torch.cuda.Event(blocking=True)
             done.record(main)
             _clock(tm, 'predict', t0)
@@ -703,7 +726,7 @@ class SlideCoder:
 
                 for k, payloads in enumerate(payload_batches):
                     target = next(targets) if targets is not None else None
-                    extent = next(roc[1]) if roc is not None and roc[1] is not None else None
+                    extent = next(extents) if extents is not None else None
                     inflight.append((k, pool.submit(self._decode, k, strip(payloads), lh * lw, tm), target, extent))
                     if len(inflight) > depth:
                         yield from emit(*inflight.pop(0))

@@ -505,7 +505,7 @@ def decompress_image(input_filename: str, data_group: str = '0/0', checkpoint=No
 def segment_image(input_filename: str, seg_model, output_filename: str, data_group: str = '0/0', checkpoint=None,
                   target_group: Optional[str] = None, batch_tiles: int = 4, threshold: float = 0.5,
                   threshold_on: str = 'scores', top_k: int = 5, scores: bool = False, coder: str = 'host',
-                  roc_bits: Optional[int] = None) -> Dict:
+                  roc_bits: Optional[int] = None, object_level: bool = False) -> Dict:
     """The reference's segmentation harness on a compressed slide (test_cae_classifier.py:46-55 and its metrics), without
     decoding a pixel to the host: the chunk bytes of the 'cae'-coded array ``data_group`` of ``input_filename`` go through
     SlideCoder.segment_batches (range decoder on ``coder``, synthesis track, the head ``seg_model``, cae_seg_predict)
@@ -530,6 +530,15 @@ def segment_image(input_filename: str, seg_model, output_filename: str, data_gro
 
         image_level/fpr, image_level/tpr, image_level/thrsh (thresholds on the scores), image_level/thrsh_logit
 
+    ``object_level`` (needs a target): the second half of the reference's harness (--compute-components-metrics,
+    test_cae_classifier.py:97-157, 267-370) per tile: the connected objects of the tile's labels (by value for a head of
+    several classes), their boxes, and the counts -- with ``roc_bits`` the histogram too -- over the pixels of all boxes
+    (SlideCoder.segment_batches(object_level=True)).  Every tile's real size is its extent, so the padding of an edge
+    chunk is in no object and no box.  The result gains 'object_level': segmenters.class_metrics of the summed
+    object-level record plus 'n_objects' (the slide's sum), 'records' ((tiles, 6), all ranks) and, with ``roc_bits``,
+    'auc', 'auc_slack' and 'roc'; rank 0 then writes object_level/fpr, tpr, thrsh and thrsh_logit as above.  An object cut
+    by a tile border counts as two.
+
     -> segmenters.class_metrics of the slide's summed record, plus
     'records': the (tiles, 6) int64 per-tile records of all ranks in tile order (slide.gather_counts), 'tiles' and
     'head_fp32_repeats' (this rank's); without a target only the last two."""
@@ -539,6 +548,8 @@ def segment_image(input_filename: str, seg_model, output_filename: str, data_gro
     from .codec import ConvolutionalAutoencoder, _module
     from .entropy import check_coder
     check_coder(coder)
+    if object_level and target_group is None:
+        raise ValueError('object_level needs a target_group: the objects are those of the labels')
     codec = None
     if checkpoint is not None and not (isinstance(checkpoint, str) and not len(checkpoint)):
         codec = ConvolutionalAutoencoder(checkpoint=checkpoint)
@@ -591,12 +602,18 @@ def segment_image(input_filename: str, seg_model, output_filename: str, data_gro
     stream = sc.segment_batches((chunks(g) for g in groups), ph, pw, seg,
                                 targets=None if tz is None else (labels(g) for g in groups), threshold=threshold,
                                 threshold_on=threshold_on, top_k=top_k, scores=scores, to_host=True, roc_bits=roc_bits,
-                                extents=None if roc_bits is None else (extents(g) for g in groups))
-    records = []
-    roc_hist = None
+                                extents=(extents(g) for g in groups) if roc_bits is not None or object_level else None,
+                                object_level=bool(object_level))
+    records, obj_records, obj_numbers = [], [], []
+    roc_hist = obj_hist = None
     for group, res in zip(groups, stream):  # res['cls']: pinned ring buffer, written out before the generator advances
         if roc_bits is not None:
             roc_hist = res['roc_hist'] if roc_hist is None else roc_hist + res['roc_hist']
+            if object_level:
+                obj_hist = res['object_roc_hist'] if obj_hist is None else obj_hist + res['object_roc_hist']
+        if object_level:
+            obj_records.append(torch.from_numpy(np.array(res['object_counts'], dtype=np.int64)))
+            obj_numbers.append(torch.from_numpy(np.array(res['n_objects'], dtype=np.int64)))
         for t, (i, j, _) in enumerate(group):
             ch, cw = min(ph, H - i * ph), min(pw, W - j * pw)
             zc.write_chunk((i, j), res['cls'][t, :ch, :cw].astype(zc.dtype))
@@ -616,24 +633,45 @@ def segment_image(input_filename: str, seg_model, output_filename: str, data_gro
                     rec[t, 2] -= pad_on
             records.append(torch.from_numpy(rec))
     out = dict(tiles=hi - lo, head_fp32_repeats=sc.timers.get('head_fp32_repeats', 0))
-    if tz is not None:
-        local = torch.cat(records) if records else torch.zeros((0, slide.COUNTS_WIDTH), dtype=torch.int64)
+
+    def gathered(parts):  # this rank's (tiles, 6) records -> those of all ranks, in tile order
+        local = torch.cat(parts) if parts else torch.zeros((0, slide.COUNTS_WIDTH), dtype=torch.int64)
         try:
             import torch.distributed as dist
             if dist.is_available() and dist.is_initialized() and dist.get_backend() == 'nccl':
                 local = local.cuda()
         except ImportError:
             pass
-        allrec = slide.gather_counts(local).cpu().numpy()
+        return slide.gather_counts(local).cpu().numpy()
+
+    def write_curve(group, roc):
+        for name, key in (('fpr', 'fpr'), ('tpr', 'tpr'), ('thrsh', 'score_thresholds'), ('thrsh_logit', 'thresholds')):
+            v = roc[key].astype(np.float32)
+            ZarrArray.create(output_filename, f'{group}/{name}', v.shape, v.shape, np.float32, codec=Zlib(9))[:] = v
+
+    if tz is not None:
+        allrec = gathered(records)
         out.update(segmenters.class_metrics(allrec.sum(axis=0), multiclass=C > 1), records=allrec)
+    if object_level:
+        objrec = gathered(obj_records)
+        # this rank's number of objects, summed over the ranks as the histograms are (an int64 all_reduce)
+        numbers = torch.tensor([sum(int(v.sum()) for v in obj_numbers)], dtype=torch.int64, device='cuda')
+        obj = dict(segmenters.class_metrics(objrec.sum(axis=0), multiclass=C > 1), records=objrec,
+                   n_objects=int(slide.reduce_histogram(numbers)[0]))
+        if roc_bits is not None:
+            if obj_hist is None:  # a rank without tiles
+                obj_hist = torch.zeros((2, 1 << roc_bits), dtype=torch.int64, device='cuda')
+            roc = segmenters.roc_from_histogram(slide.reduce_histogram(obj_hist))
+            obj.update(auc=roc['auc'], auc_slack=roc['auc_slack'], roc=roc)
+            if rank == 0:
+                write_curve('object_level', roc)
+        out['object_level'] = obj
     if roc_bits is not None:
         if roc_hist is None:  # a rank without tiles
             roc_hist = torch.zeros((2, 1 << roc_bits), dtype=torch.int64, device='cuda')
         roc = segmenters.roc_from_histogram(slide.reduce_histogram(roc_hist))
         out.update(auc=roc['auc'], auc_slack=roc['auc_slack'], roc=roc)
         if rank == 0:
-            for name, key in (('fpr', 'fpr'), ('tpr', 'tpr'), ('thrsh', 'score_thresholds'), ('thrsh_logit', 'thresholds')):
-                v = roc[key].astype(np.float32)
-                ZarrArray.create(output_filename, f'image_level/{name}', v.shape, v.shape, np.float32, codec=Zlib(9))[:] = v
+            write_curve('image_level', roc)
     _barrier()
     return out

@@ -823,6 +823,62 @@ int cae_seg_roc_hist(const float *logits_dev, const uint8_t *target_dev, const i
 size_t cae_seg_roc_workspace(int n, int h, int w, int bits);
 int cae_seg_roc_blocks(int n, int h, int w, int bits);
 
+/* ---- Objects of a label plane (csrc/cae_seg_objects.hip) -----------------------------------------
+ * The object-level half of the reference's harness (--compute-components-metrics, test_cae_classifier.py:97-157 and
+ * 267-370): every connected object of the target gets a bounding box, and counts and ROC curve are taken over the pixels
+ * of all boxes.  Four entry points; all results are integers and bitwise repeatable.
+ *
+ * cae_seg_components: target_dev (n, h, w) uint8 at any byte address -> labels_dev (n, h, w) int32 and n_objects_dev
+ * int64 [n].  A pixel is foreground when target > 0 and it lies inside the extent (extent_dev int32 [n][2] = (rows,
+ * cols) on the device, clamped to 0..h / 0..w as in cae_seg_roc_hist, NULL = whole planes).  Foreground pixels that
+ * touch by an edge or a corner (8-connected) belong to one object; with by_value != 0 only when their values are equal
+ * (skimage.measure.label of an integer image).  The label of a pixel is 0 on background, else 1 + the smallest
+ * row-major index y w + x of its object: canonical, independent of launch shapes and execution order.  n_objects_dev[i]
+ * is the number of objects of plane i.  Objects never reach across planes.
+ *
+ * cae_seg_object_cover: labels_dev as cae_seg_components writes them (same extent) -> cover_dev (n, h, w) uint16, the
+ * number of objects of the plane whose box contains the pixel.  Box of an object with pixel rows ymin..ymax and columns
+ * xmin..xmax (test_cae_classifier.py:101-109): rows max(0, ymin - 1) .. min(rows, ymax + 2), columns max(0, xmin - 1) ..
+ * min(cols, xmax + 2), end exclusive, (rows, cols) the extent.  The reference concatenates the pixels of every box, so a
+ * pixel inside k boxes counts k times: every object-level sum is the image-level sum weighted by the cover.
+ * cover <= 3 min(h, w) (objects are disjoint, and one whose widened column range holds x has a pixel in columns
+ * x-1..x+1), which is why planes with 3 min(h, w) > 65535 are refused.  A label that does not name a root pixel of its
+ * plane, or whose root pixel lies outside the extent (labels made with another extent), is ignored, as is every pixel
+ * outside the extent; no label is used as an index before it is checked.
+ *
+ * cae_seg_object_counts: the [tp, tn, fp, fn, p, tp_top] record of cae_seg_predict with every pixel counted cover
+ * times, by cae_seg_predict's rules (logit > t; lowest-index argmax, the rank rule of tp_top, a target >= c is wrong);
+ * several classes: fp = fn = sum(cover) - tp, tn = 0, p = sum(cover).  logits_dev (n, c, hw) fp32 4-byte aligned,
+ * target_dev (n, hw) uint8, cover_dev (n, hw) uint16: any values, not only a cover's.
+ *
+ * cae_seg_object_roc_hist: the histogram of cae_seg_roc_hist (same key, bin, NaN rule, extent and layout) with every
+ * pixel adding its cover instead of 1.
+ *
+ * Weighted sums are exact for every uint16 weight: lane tallies, block partials and results are 64 bits wide; the one
+ * 32-bit accumulator, a block's LDS histogram, is added into the block's 64-bit partial and cleared after at most 65536
+ * pixels (65536 x 65535 < 2^32).  Integer global atomics (min / max / add) only: exact in any order.  No launch waits
+ * for another block; every walk of the union-find strictly descends (parent <= index at all times).  Neither outputs
+ * nor workspaces need initialising; workspaces (the _workspace queries; 8-byte aligned) hold nothing between calls.
+ * Launches are asynchronous on `stream`.  CAE_ERR_ARG before any launch: n < 0, h / w / hw < 1, 3 min(h, w) > 65535 or
+ * h w > 2^31 - 1 (components, cover), c outside 1..256, top_k < 1, bits outside 8..14, and for n >= 1 a NULL or
+ * misaligned pointer or a workspace that is too small.  n == 0: CAE_OK, nothing launched.  The queries return 0 for
+ * refused shapes and for n == 0. */
+int cae_seg_components(const uint8_t *target_dev, const int32_t *extent_dev, int n, int h, int w, int by_value,
+                       int32_t *labels_dev, int64_t *n_objects_dev, void *workspace_dev, size_t workspace_bytes,
+                       void *stream);
+size_t cae_seg_components_workspace(int n, int h, int w);
+int cae_seg_object_cover(const int32_t *labels_dev, const int32_t *extent_dev, int n, int h, int w, uint16_t *cover_dev,
+                         void *workspace_dev, size_t workspace_bytes, void *stream);
+size_t cae_seg_object_cover_workspace(int n, int h, int w);
+int cae_seg_object_counts(const float *logits_dev, const uint8_t *target_dev, const uint16_t *cover_dev, int n, int c,
+                          size_t hw, float t, int top_k, int64_t *counts_dev, void *workspace_dev,
+                          size_t workspace_bytes, void *stream);
+size_t cae_seg_object_counts_workspace(int n, int c, size_t hw);
+int cae_seg_object_roc_hist(const float *logits_dev, const uint8_t *target_dev, const uint16_t *cover_dev,
+                            const int32_t *extent_dev, int n, int h, int w, int bits, int per_image, int64_t *hist_dev,
+                            void *workspace_dev, size_t workspace_bytes, void *stream);
+size_t cae_seg_object_roc_workspace(int n, int h, int w, int bits);
+
 #ifdef __cplusplus
 }
 #endif

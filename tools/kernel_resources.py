@@ -9,7 +9,7 @@ out = subprocess.run(cmd, capture_output=True, text=True).stderr
 cur = None
 rows = []
 for line in out.splitlines():
-    m = re.search(r'remark: (?:\s*)([A-Za-z ]+): (.*?) \[-Rpass', line)
+    m = re.search(r'remark: (?:\s*)([A-Za-z ]+(?: \[[a-z/A-Z]+\])?): (.*?) \[-Rpass', line)
     if not m:
         continue
     k, v = m.group(1).strip(), m.group(2).strip()
@@ -20,6 +20,6 @@ for line in out.splitlines():
         cur[k] = v
 print('%-70s %5s %5s %6s %6s %8s %4s' % ('kernel', 'VGPR', 'AGPR', 'vspill', 'sspill', 'scratch', 'occ'))
 for r in rows:
-    name = r['name'].replace('cae::', '').split('(')[0][:70]
+    name = r['name'].replace('(anonymous namespace)::', '').replace('cae::', '').split('(')[0][:70]
     print('%-70s %5s %5s %6s %6s %8s %4s' % (name, r.get('VGPRs'), r.get('AGPRs'), r.get('VGPRs Spill', r.get('VGPR Spill')),
           r.get('SGPRs Spill', r.get('SGPR Spill')), r.get('ScratchSize [bytes/lane]'), r.get('Occupancy [waves/SIMD]')))
