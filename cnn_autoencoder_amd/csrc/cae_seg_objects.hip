@@ -16,21 +16,15 @@
 // cae_seg_object_counts / _roc_hist: the tallies of cae_seg_predict and the histogram of cae_seg_roc_hist with every
 // pixel counted cover times.  Tallies and partials are 64 bits wide throughout; the one 32-bit accumulator, the LDS
 // histogram, is added into the block's 64-bit partial and cleared every kChunk = 65536 pixels: 65536 * 65535 < 2^32.
-#include <hip/hip_runtime.h>
-
-#include <algorithm>
-#include <climits>
-#include <cstdint>
-
-#include "cae_launch.hpp"
+// The decisions, the block tally, the counted extent, the shape checks and the grid policy are those of the image-level
+// metrics (cae_seg_metrics.hpp), and so are the two merge kernels behind the partials (cae_seg_merge.hip).
+#include "cae_seg_metrics.hpp"
 #include "cae_seg_roc_key.hpp"
 
 namespace cae {
 namespace {
 
 constexpr int kThreads = 256;
-constexpr int kBlocksTarget = 4096;  // blocks of a grid-stride launch at which more would only add partials
-constexpr int kMinBits = 8, kMaxBits = 14;
 constexpr int kHistThreads = 1024;
 constexpr uint32_t kChunk = 65536;   // pixels a block adds into its 32-bit LDS words before it flushes them
 
@@ -38,15 +32,6 @@ struct Plane {
     int h, w, wseg;  // wseg: 64-column segments of a row
     int bx;          // blocks per image
 };
-
-// the counted part of image n: (rows, cols), clamped to the plane
-__device__ __forceinline__ void extent_of(const int32_t *extent, int n, int h, int w, int &rows, int &cols) {
-    rows = h, cols = w;
-    if (extent) {
-        rows = std::min(std::max(extent[2 * n], 0), h);
-        cols = std::min(std::max(extent[2 * n + 1], 0), w);
-    }
-}
 
 // block and lane -> image n, pixel (y, x); x may lie beyond the row (x >= w) and y beyond the plane: a wave holds 64
 // consecutive columns of one row
@@ -312,8 +297,6 @@ __global__ __launch_bounds__(kThreads) void obj_colscan_kernel(CoverArgs a, size
 }
 
 // ---- weighted counts -------------------------------------------------------------------------------------------
-constexpr int kPartial = 4;  // one class: tp tn fp fn; several: tp tp_top sum -
-
 struct TallyArgs {
     const float *logits;
     const uint8_t *target;
@@ -332,75 +315,19 @@ __global__ __launch_bounds__(kThreads) void obj_tally_kernel(TallyArgs a) {
     const float *lg = a.logits + (size_t)n * C * hw;
     const uint8_t *tg = a.target + (size_t)n * hw;
     const uint16_t *cv = a.cover + (size_t)n * hw;
-    unsigned long long ty[kPartial] = {0, 0, 0, 0};  // 64 bits: no count of pixels times 65535 leaves them
+    Tally<unsigned long long> ty = {{0, 0, 0, 0}};
     for (size_t p = (size_t)(blockIdx.x % a.bx) * kThreads + tid; p < hw; p += stride) {
         const unsigned long long wgt = cv[p];
         if (!wgt) continue;
-        const int tgt = tg[p];
         if constexpr (!MULTI) {
-            const bool on = lg[p] > a.t, pos = tgt > 0;  // false for NaN
-            ty[on ? (pos ? 0 : 2) : (pos ? 3 : 1)] += wgt;
+            float x = lg[p];
+            decide_binary(x, a.t, (int)tg[p], false, wgt, ty);
         } else {
-            float best = lg[p];
-            int idx = 0;
-            for (int c = 1; c < C; ++c) {
-                const float v = lg[(size_t)c * hw + p];
-                if (v > best) {  // strict: the lowest index of equal maxima; NaN never wins
-                    best = v;
-                    idx = c;
-                }
-            }
-            const bool ranked = tgt < C;  // the only use of the target as an index, behind its bound
-            const float lt = ranked ? lg[(size_t)tgt * hw + p] : 0.f;
-            int rank = 0;
-            for (int c = 0; c < C; ++c) {
-                const float v = lg[(size_t)c * hw + p];
-                rank += v > lt || (c < tgt && v == lt);
-            }
-            if (idx == tgt) ty[0] += wgt;
-            if (ranked && rank < a.top_k) ty[1] += wgt;
-            ty[2] += wgt;
+            decide_stream<false>(lg, nullptr, hw, p, C, (int)tg[p], a.top_k, wgt, ty);
+            ty.v[2] += wgt;
         }
     }
-    __shared__ unsigned long long wave_sum[kThreads / 64][kPartial];
-#pragma unroll
-    for (int j = 0; j < kPartial; ++j) {
-        unsigned long long s = ty[j];
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) s += __shfl_down(s, d, 64);
-        if ((tid & 63) == 0) wave_sum[tid >> 6][j] = s;
-    }
-    __syncthreads();
-    if (tid < kPartial) {
-        unsigned long long s = 0;
-#pragma unroll
-        for (int k = 0; k < kThreads / 64; ++k) s += wave_sum[k][tid];
-        a.partial[(size_t)blockIdx.x * kPartial + tid] = s;  // every (image, block) writes its partial, work or not
-    }
-}
-
-// one wave per image: the bx partials summed in a fixed order, the record written
-__global__ __launch_bounds__(64) void obj_record_kernel(const unsigned long long *partial, int bx, int c, long long *counts) {
-    const int n = blockIdx.x;
-    unsigned long long s[kPartial] = {0, 0, 0, 0};
-    for (int b = threadIdx.x; b < bx; b += 64) {
-#pragma unroll
-        for (int j = 0; j < kPartial; ++j) s[j] += partial[((size_t)n * bx + b) * kPartial + j];
-    }
-#pragma unroll
-    for (int j = 0; j < kPartial; ++j) {
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) s[j] += __shfl_down(s[j], d, 64);
-    }
-    if (threadIdx.x == 0) {
-        long long *out = counts + (size_t)n * 6;  // tp tn fp fn p tp_top
-        const long long v0 = (long long)s[0], v1 = (long long)s[1], v2 = (long long)s[2], v3 = (long long)s[3];
-        if (c == 1) {
-            out[0] = v0, out[1] = v1, out[2] = v2, out[3] = v3, out[4] = v0 + v3, out[5] = v0;
-        } else {
-            out[0] = v0, out[1] = 0, out[2] = v2 - v0, out[3] = v2 - v0, out[4] = v2, out[5] = v1;
-        }
-    }
+    block_tally_store<kThreads>(ty, a.partial);
 }
 
 // ---- weighted histograms ---------------------------------------------------------------------------------------
@@ -451,23 +378,7 @@ __global__ __launch_bounds__(kHistThreads) void obj_hist_kernel(HistArgs a) {
     }
 }
 
-// hist[m][e] = the sum over the `sources` partials of output m of word e, in a fixed order
-__global__ __launch_bounds__(kThreads) void obj_histsum_kernel(const unsigned long long *partial, int sources, uint32_t words,
-                                                               long long *out) {
-    const size_t id = (size_t)blockIdx.x * kThreads + threadIdx.x;  // < m words: words is a multiple of kThreads
-    const size_t m = id / words, e = id % words;
-    const unsigned long long *src = partial + m * sources * words + e;
-    unsigned long long s = 0;
-#pragma unroll 4
-    for (int b = 0; b < sources; ++b) s += src[(size_t)b * words];
-    out[id] = (long long)s;
-}
-
 // ---- shapes ----------------------------------------------------------------------------------------------------
-bool plane_ok(int n, int h, int w) {
-    return n >= 1 && h >= 1 && w >= 1 && 3 * (long long)std::min(h, w) <= 65535 && (long long)h * w <= INT_MAX;
-}
-
 // wave-per-row-segment placement of the labelling kernels; false if the grid would not fit
 bool plane_of(int n, int h, int w, Plane &p) {
     p.h = h, p.w = w, p.wseg = (w + 63) / 64;
@@ -479,22 +390,12 @@ bool plane_of(int n, int h, int w, Plane &p) {
 }
 
 // blocks per image of the grid-stride kernels
-int stride_blocks(int n, size_t hw) {
-    const size_t tiles = (hw + kThreads - 1) / kThreads;
-    const size_t cap = std::max<size_t>(1, (size_t)kBlocksTarget / (size_t)std::max(n, 1));
-    return (int)std::min(tiles, cap);
-}
+int stride_blocks(int n, size_t hw) { return blocks_for(n, hw, kThreads, kBlocksTarget); }
 
-// blocks per image of the histogram: one per kChunk pixels, fewer once the launch has 256 (a block fills a CU's LDS
-// above 12 bits) or 1024 blocks
+// blocks per image of the histogram: one per kChunk pixels
 int hist_blocks(int n, int h, int w, int bits) {
-    const size_t hw = (size_t)h * (size_t)w;
-    const size_t spans = (hw + kChunk - 1) / kChunk;
-    const size_t cap = std::max<size_t>(1, (size_t)(bits > 12 ? 256 : 1024) / (size_t)n);
-    return (int)std::min(spans, cap);
+    return blocks_for(n, (size_t)h * (size_t)w, kChunk, hist_blocks_target(bits));
 }
-
-bool misaligned(const void *p, unsigned mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; }
 
 }  // namespace
 }  // namespace cae
@@ -511,7 +412,7 @@ extern "C" int cae_seg_components(const uint8_t *target, const int32_t *extent, 
                                   int32_t *labels, int64_t *n_objects, void *workspace, size_t workspace_bytes,
                                   void *stream) {
     if (n < 0 || h < 1 || w < 1) return fail(CAE_ERR_ARG, "cae_seg_components: bad shape n=%d h=%d w=%d", n, h, w);
-    if (3 * (long long)std::min(h, w) > 65535 || (long long)h * w > INT_MAX)
+    if (!plane_fits(h, w))
         return fail(CAE_ERR_ARG, "cae_seg_components: planes of %d x %d pixels are too large", h, w);
     if (n == 0) return CAE_OK;
     if (!target || !labels || !n_objects) return fail(CAE_ERR_ARG, "cae_seg_components: NULL target, labels or n_objects");
@@ -545,7 +446,7 @@ extern "C" size_t cae_seg_object_cover_workspace(int n, int h, int w) {
 extern "C" int cae_seg_object_cover(const int32_t *labels, const int32_t *extent, int n, int h, int w, uint16_t *cover,
                                     void *workspace, size_t workspace_bytes, void *stream) {
     if (n < 0 || h < 1 || w < 1) return fail(CAE_ERR_ARG, "cae_seg_object_cover: bad shape n=%d h=%d w=%d", n, h, w);
-    if (3 * (long long)std::min(h, w) > 65535 || (long long)h * w > INT_MAX)
+    if (!plane_fits(h, w))
         return fail(CAE_ERR_ARG, "cae_seg_object_cover: planes of %d x %d pixels are too large", h, w);
     if (n == 0) return CAE_OK;
     if (!labels || !cover) return fail(CAE_ERR_ARG, "cae_seg_object_cover: NULL labels or cover");
@@ -607,21 +508,18 @@ extern "C" int cae_seg_object_counts(const float *logits, const uint8_t *target,
     else
         hipLaunchKernelGGL(obj_tally_kernel<true>, grid, block, 0, st, a);
     HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(obj_record_kernel, dim3(n), dim3(64), 0, st, a.partial, a.bx, c, reinterpret_cast<long long *>(counts));
-    HIP_TRY(hipGetLastError());
-    return CAE_OK;
+    return launch_seg_record(a.partial, n, a.bx, c, -1, reinterpret_cast<long long *>(counts), st);  // -1: total in tally 2
 }
 
 extern "C" size_t cae_seg_object_roc_workspace(int n, int h, int w, int bits) {
-    if (n < 1 || h < 1 || w < 1 || bits < kMinBits || bits > kMaxBits) return 0;
+    if (n < 1 || h < 1 || w < 1 || !bits_ok(bits)) return 0;
     return (size_t)n * hist_blocks(n, h, w, bits) * (sizeof(unsigned long long) << (bits + 1));
 }
 
 extern "C" int cae_seg_object_roc_hist(const float *logits, const uint8_t *target, const uint16_t *cover,
                                        const int32_t *extent, int n, int h, int w, int bits, int per_image,
                                        int64_t *hist, void *workspace, size_t workspace_bytes, void *stream) {
-    if (bits < kMinBits || bits > kMaxBits)
-        return fail(CAE_ERR_ARG, "cae_seg_object_roc_hist: %d bits outside %d..%d", bits, kMinBits, kMaxBits);
+    if (!bits_ok(bits)) return refuse_bits("cae_seg_object_roc_hist", bits);
     if (n < 0 || h < 1 || w < 1) return fail(CAE_ERR_ARG, "cae_seg_object_roc_hist: bad shape n=%d h=%d w=%d", n, h, w);
     if (n == 0) return CAE_OK;
     if (!logits || !target || !cover || !hist)
@@ -640,10 +538,5 @@ extern "C" int cae_seg_object_roc_hist(const float *logits, const uint8_t *targe
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(obj_hist_kernel, dim3((unsigned)((size_t)n * a.bx)), dim3(kHistThreads), lds, st, a);
     HIP_TRY(hipGetLastError());
-    const uint32_t words = 2u << bits;
-    const int m = per_image ? n : 1, sources = per_image ? a.bx : n * a.bx;
-    hipLaunchKernelGGL(obj_histsum_kernel, dim3((unsigned)((size_t)m * words / kThreads)), dim3(kThreads), 0, st, a.partial,
-                       sources, words, reinterpret_cast<long long *>(hist));
-    HIP_TRY(hipGetLastError());
-    return CAE_OK;
+    return launch_seg_histsum(a.partial, n, a.bx, per_image, bits, reinterpret_cast<long long *>(hist), st);
 }

@@ -8,21 +8,15 @@
 // each) -- and every pixel otherwise -- go one pixel per lane.  Up to kRegC classes the logits of a pixel live in
 // registers and are read from HBM once; above it the planes are streamed three times (maximum, sum, scores), the second
 // and third time out of the cache.  Counts are integers: lane tallies, summed over the wave by shuffles, over the block
-// through LDS, one partial per (image, block) in the workspace, merged by seg_counts_kernel; no atomics, exact.
-#include <hip/hip_runtime.h>
-
-#include <algorithm>
-#include <cstdint>
-
-#include "cae_launch.hpp"
+// through LDS, one partial per (image, block) in the workspace, merged by seg_record_kernel; no atomics, exact.  The
+// decisions of one class and of streamed planes, the block tally, the grid policy and the merge: cae_seg_metrics.hpp.
+#include "cae_seg_metrics.hpp"
 
 namespace cae {
 namespace {
 
 constexpr int kThreads = 256;
-constexpr int kRegC = 16;         // classes held in registers (four pixels each: 64 VGPRs of logits)
-constexpr int kBlocksTarget = 4096;  // blocks of a launch at which more would only add partials
-constexpr int kPartial = 4;       // tallies per (image, block): binary tp tn fp fn; several classes tp tp_top - -
+constexpr int kRegC = 16;  // classes held in registers (four pixels each: 64 VGPRs of logits)
 
 struct PredictArgs {
     const float *logits;
@@ -35,37 +29,14 @@ struct PredictArgs {
     float t;
 };
 
-// a lane's tallies; 32 bits hold them: a lane sees hw / (256 bx) + 7 pixels and hw floats fit the device's memory
-struct Tally {
-    unsigned v[kPartial];
-};
-
-__device__ __forceinline__ uint8_t decide_binary(float &x, float t, int tgt, bool want, Tally &ty) {
-    const bool on = x > t;  // false for NaN
-    if (tgt >= 0) {
-        const bool pos = tgt > 0;
-        ty.v[0] += on && pos;
-        ty.v[1] += !on && !pos;
-        ty.v[2] += on && !pos;
-        ty.v[3] += !on && pos;
-    }
-    if (want) {
-        // e in (0, 1]: no overflow, and the rounding of the argument costs |x| e^-|x| 2^-24 absolute at most
-        const float e = __expf(-fabsf(x));
-        const float r = 1.0f / (1.0f + e);
-        x = x >= 0.f ? r : e * r;
-    }
-    return on;
-}
-
 // l[0..C): the pixel's logits, overwritten by its scores if `want`.  -> class index
 template <int CMAX>
-__device__ __forceinline__ uint8_t decide_multi(float (&l)[CMAX], int C, int tgt, int k, bool want, Tally &ty) {
+__device__ __forceinline__ uint8_t decide_multi(float (&l)[CMAX], int C, int tgt, int k, bool want, Tally<unsigned> &ty) {
     float best = l[0];
     int idx = 0;
 #pragma unroll
     for (int c = 1; c < CMAX; ++c)
-        if (c < C && l[c] > best) {  // strict: the lowest index of equal maxima; NaN never wins, idx stays in 0..C-1
+        if (c < C && above(l[c], best)) {  // strict: idx stays in 0..C-1
             best = l[c];
             idx = c;
         }
@@ -76,7 +47,7 @@ __device__ __forceinline__ uint8_t decide_multi(float (&l)[CMAX], int C, int tgt
         for (int c = 0; c < CMAX; ++c) lt = c == tgt ? l[c] : lt;
         int rank = 0;
 #pragma unroll
-        for (int c = 0; c < CMAX; ++c) rank += c < C && (l[c] > lt || (c < tgt && l[c] == lt));
+        for (int c = 0; c < CMAX; ++c) rank += c < C && before(l[c], c, lt, tgt);
         ty.v[1] += tgt < C && rank < k;
     }
     if (want) {
@@ -94,43 +65,11 @@ __device__ __forceinline__ uint8_t decide_multi(float (&l)[CMAX], int C, int tgt
     return (uint8_t)idx;
 }
 
-// one pixel of more than kRegC classes, its planes streamed
-__device__ __forceinline__ uint8_t decide_stream(const float *lg, float *sc, size_t hw, size_t p, int C, int tgt, int k,
-                                                 Tally &ty) {
-    float best = lg[p];
-    int idx = 0;
-    for (int c = 1; c < C; ++c) {
-        const float v = lg[(size_t)c * hw + p];
-        if (v > best) {
-            best = v;
-            idx = c;
-        }
-    }
-    if (tgt < 0 && !sc) return (uint8_t)idx;
-    const bool ranked = tgt >= 0 && tgt < C;  // the only use of the target as an index, behind its bound
-    const float lt = ranked ? lg[(size_t)tgt * hw + p] : 0.f;
-    float s = 0.f;
-    int rank = 0;
-    for (int c = 0; c < C; ++c) {
-        const float v = lg[(size_t)c * hw + p];
-        s += __expf(v - best);
-        rank += v > lt || (c < tgt && v == lt);
-    }
-    if (tgt >= 0) {
-        ty.v[0] += idx == tgt;
-        ty.v[1] += ranked && rank < k;
-    }
-    if (sc) {
-        const float r = 1.0f / s;
-        for (int c = 0; c < C; ++c) sc[(size_t)c * hw + p] = __expf(lg[(size_t)c * hw + p] - best) * r;
-    }
-    return (uint8_t)idx;
-}
-
 template <int CMAX>
-__device__ __forceinline__ uint8_t decide_pixel(float (&l)[CMAX], const PredictArgs &a, int tgt, bool want, Tally &ty) {
+__device__ __forceinline__ uint8_t decide_pixel(float (&l)[CMAX], const PredictArgs &a, int tgt, bool want,
+                                                Tally<unsigned> &ty) {
     if constexpr (CMAX == 1)
-        return decide_binary(l[0], a.t, tgt, want, ty);
+        return decide_binary(l[0], a.t, tgt, want, 1u, ty);
     else
         return decide_multi<CMAX>(l, a.c, tgt, a.top_k, want, ty);
 }
@@ -146,14 +85,14 @@ __global__ __launch_bounds__(kThreads) void seg_predict_kernel(PredictArgs a) {
     const uint8_t *tg = a.target ? a.target + (size_t)n * hw : nullptr;
     uint8_t *cl = a.cls + (size_t)n * hw;
     const size_t stride = (size_t)a.bx * kThreads, first = (size_t)x * kThreads + tid;
-    Tally ty = {{0, 0, 0, 0}};
+    Tally<unsigned> ty = {{0, 0, 0, 0}};
 
     // pixels [head, tail) in groups of four behind 16-byte aligned addresses; the rest one by one
     size_t head = hw, groups = 0;
     if constexpr (CMAX != 0) {
         constexpr int R = CMAX;
         if (C == 1 || hw % 4 == 0) {
-            head = std::min<size_t>(hw, (size_t)((0 - (reinterpret_cast<uintptr_t>(lg) >> 2)) & 3));
+            head = std::min(hw, aligned_head(lg));
             groups = (hw - head) / 4;
         }
         // scores share the 16-byte path if they sit at the logits' offset within 16 bytes; class and target bytes go
@@ -217,7 +156,8 @@ __global__ __launch_bounds__(kThreads) void seg_predict_kernel(PredictArgs a) {
         const size_t p = q < head ? q : tail + (q - head);  // < hw
         const int tgt = tg ? (int)tg[p] : -1;
         if constexpr (CMAX == 0) {
-            cl[p] = decide_stream(lg, sc, hw, p, C, tgt, a.top_k, ty);
+            cl[p] = sc ? decide_stream<true>(lg, sc, hw, p, C, tgt, a.top_k, 1u, ty)
+                       : decide_stream<false>(lg, sc, hw, p, C, tgt, a.top_k, 1u, ty);
         } else {
             constexpr int R = CMAX;
             float l[R];
@@ -232,64 +172,11 @@ __global__ __launch_bounds__(kThreads) void seg_predict_kernel(PredictArgs a) {
         }
     }
 
-    if (!a.partial) return;
-    __shared__ unsigned long long wave_sum[kThreads / 64][kPartial];
-#pragma unroll
-    for (int j = 0; j < kPartial; ++j) {
-        unsigned long long s = ty.v[j];
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) s += __shfl_down(s, d, 64);
-        if ((tid & 63) == 0) wave_sum[tid >> 6][j] = s;
-    }
-    __syncthreads();
-    if (tid < kPartial) {
-        unsigned long long s = 0;
-#pragma unroll
-        for (int w = 0; w < kThreads / 64; ++w) s += wave_sum[w][tid];
-        a.partial[((size_t)n * a.bx + x) * kPartial + tid] = s;  // every (image, block) writes its partial, work or not
-    }
+    if (a.partial) block_tally_store<kThreads>(ty, a.partial);
 }
 
-// one block per image: the bx partials summed (integers: any order is exact; this one is fixed), the record written
-__global__ __launch_bounds__(kThreads) void seg_counts_kernel(const unsigned long long *partial, int bx, int c, size_t hw,
-                                                              long long *counts) {
-    const int n = blockIdx.x, tid = threadIdx.x;
-    unsigned long long s[kPartial] = {0, 0, 0, 0};
-    for (int b = tid; b < bx; b += kThreads) {
-#pragma unroll
-        for (int j = 0; j < kPartial; ++j) s[j] += partial[((size_t)n * bx + b) * kPartial + j];
-    }
-    __shared__ unsigned long long wave_sum[kThreads / 64][kPartial];
-#pragma unroll
-    for (int j = 0; j < kPartial; ++j) {
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) s[j] += __shfl_down(s[j], d, 64);
-        if ((tid & 63) == 0) wave_sum[tid >> 6][j] = s[j];
-    }
-    __syncthreads();
-    if (tid == 0) {
-        long long v[kPartial];
-        for (int j = 0; j < kPartial; ++j) {
-            unsigned long long t = 0;
-            for (int w = 0; w < kThreads / 64; ++w) t += wave_sum[w][j];
-            v[j] = (long long)t;
-        }
-        long long *out = counts + (size_t)n * 6;  // tp tn fp fn p tp_top
-        if (c == 1) {
-            out[0] = v[0], out[1] = v[1], out[2] = v[2], out[3] = v[3], out[4] = v[0] + v[3], out[5] = v[0];
-        } else {
-            const long long wrong = (long long)hw - v[0];
-            out[0] = v[0], out[1] = 0, out[2] = wrong, out[3] = wrong, out[4] = (long long)hw, out[5] = v[1];
-        }
-    }
-}
-
-// blocks per image: one per 256 groups of four pixels, fewer once the launch has kBlocksTarget blocks
-int blocks_per_image(int n, size_t hw) {
-    const size_t tiles = (hw + 4 * kThreads - 1) / (4 * kThreads);
-    const size_t cap = std::max<size_t>(1, (size_t)kBlocksTarget / (size_t)std::max(n, 1));
-    return (int)std::min(tiles, cap);
-}
+// blocks per image: one per 256 groups of four pixels
+int blocks_per_image(int n, size_t hw) { return blocks_for(n, hw, 4 * kThreads, kBlocksTarget); }
 
 }  // namespace
 }  // namespace cae
@@ -313,7 +200,7 @@ extern "C" int cae_seg_predict(const float *logits, const uint8_t *target, int n
     const size_t need = cae_seg_predict_workspace(n, c, hw);
     if (counts && (!workspace || workspace_bytes < need))
         return fail(CAE_ERR_ARG, "cae_seg_predict: workspace too small: %zu bytes needed", need);
-    if (counts && (reinterpret_cast<uintptr_t>(workspace) & 7))
+    if (counts && misaligned(workspace, 7))
         return fail(CAE_ERR_ARG, "cae_seg_predict: workspace not 8-byte aligned");
     PredictArgs a;
     a.logits = logits, a.target = target, a.cls = cls, a.scores = scores;
@@ -334,10 +221,6 @@ extern "C" int cae_seg_predict(const float *logits, const uint8_t *target, int n
     else
         hipLaunchKernelGGL(seg_predict_kernel<0>, grid, block, 0, st, a);
     HIP_TRY(hipGetLastError());
-    if (counts) {
-        hipLaunchKernelGGL(seg_counts_kernel, dim3(n), dim3(kThreads), 0, st, a.partial, a.bx, c, hw,
-                           reinterpret_cast<long long *>(counts));
-        HIP_TRY(hipGetLastError());
-    }
-    return CAE_OK;
+    if (!counts) return CAE_OK;
+    return launch_seg_record(a.partial, n, a.bx, c, (long long)hw, reinterpret_cast<long long *>(counts), st);
 }

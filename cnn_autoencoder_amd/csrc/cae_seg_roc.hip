@@ -7,27 +7,17 @@
 // logit loads and 4-byte target loads behind the image's first aligned address, the pixels in front of it and behind the
 // last whole group one per lane (block 0 of the image).  Lanes of a wave that hit the first active lane's word add
 // once, by their number: a slide's background puts most of a wave on one or two words, and 64 adds to one LDS word
-// take 64 turns.  Second launch: the partials of an image, or of all images, summed into int64 in a fixed order.
-// No global atomics, no float atomics, nothing to initialise.
-#include <hip/hip_runtime.h>
-
-#include <algorithm>
-#include <cstdint>
-
-#include "cae_launch.hpp"
+// take 64 turns.  Second launch: the partials of an image, or of all images, summed into int64 in a fixed order
+// (seg_histsum_kernel, cae_seg_merge.hip).  No global atomics, no float atomics, nothing to initialise.  The counted
+// extent, the aligned head, the bits range and the grid policy: cae_seg_metrics.hpp.
+#include "cae_seg_metrics.hpp"
 #include "cae_seg_roc_key.hpp"
 
 namespace cae {
 namespace {
 
 constexpr int kThreads = 1024;      // 16 waves: the one block a CU holds at 14 bits keeps its four SIMDs loading
-constexpr int kSumThreads = 512;    // roc_sum_kernel: 64 lanes x 4 entries, 8 waves that share the partials out
 constexpr size_t kSpanMin = 8192;   // pixels below which a block of its own only adds a partial
-constexpr int kMinBits = 8, kMaxBits = 14;
-
-// blocks of a launch at which more would only add partials: a partial is 2^(bits+3) bytes written and read again, as
-// much as 2^(bits+3) / 5 pixels of input; above 12 bits one block per CU of the 256 is all that runs at a time
-int blocks_target(int bits) { return bits > 12 ? 256 : 1024; }
 
 struct RocArgs {
     const float *logits;
@@ -58,18 +48,15 @@ __global__ __launch_bounds__(kThreads) void roc_hist_kernel(RocArgs a) {
     __syncthreads();
 
     const size_t w = (size_t)a.w, hw = (size_t)a.h * w;
-    int rows = a.h, cols = a.w;
-    if (a.extent) {
-        rows = std::min(std::max(a.extent[2 * n], 0), a.h);
-        cols = std::min(std::max(a.extent[2 * n + 1], 0), a.w);
-    }
+    int rows, cols;
+    extent_of(a.extent, n, a.h, a.w, rows, cols);
     const size_t lim = cols > 0 ? (size_t)rows * w : 0;  // whole rows beyond `rows` are never loaded
     const bool ragged = cols < a.w;                      // columns beyond `cols` are loaded and left out
     const float *lg = a.logits + (size_t)n * hw;
     const uint8_t *tg = a.target + (size_t)n * hw;
 
     // pixels [head, tail) in groups of four behind 16-byte aligned addresses; the (at most six) others one per lane
-    const size_t head = std::min<size_t>(lim, (size_t)((0 - (reinterpret_cast<uintptr_t>(lg) >> 2)) & 3));
+    const size_t head = std::min(lim, aligned_head(lg));
     const size_t groups = (lim - head) / 4;
     const size_t per_block = (groups + a.bx - 1) / a.bx;
     const size_t g0 = std::min(groups, (size_t)x * per_block), g1 = std::min(groups, g0 + per_block);
@@ -110,41 +97,11 @@ __global__ __launch_bounds__(kThreads) void roc_hist_kernel(RocArgs a) {
     for (uint32_t i = tid; i < B / 2; i += kThreads) dst[i] = src[i];
 }
 
-// hist[m][e] = the sum over the `sources` partials of output m of word e, e in 0 .. 2B: a block owns 256 words (four per
-// lane), its waves take the partials in turn, and the eight wave sums are added in wave order
-__global__ __launch_bounds__(kSumThreads) void roc_sum_kernel(const uint32_t *partial, int sources, uint32_t words,
-                                                              long long *out) {
-    constexpr int kWaves = kSumThreads / 64;
-    const uint32_t per_m = words / 256, m = blockIdx.x / per_m, first = (blockIdx.x % per_m) * 256u;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const uint32_t e = first + 4u * lane;  // < words: words is a multiple of 256
-    const uint32_t *src = partial + (size_t)m * sources * words + e;
-    unsigned long long s[4] = {0, 0, 0, 0};
-#pragma unroll 4
-    for (int b = wave; b < sources; b += kWaves) {
-        const uint4 v = *reinterpret_cast<const uint4 *>(src + (size_t)b * words);
-        s[0] += v.x, s[1] += v.y, s[2] += v.z, s[3] += v.w;
-    }
-    __shared__ unsigned long long wave_sum[kWaves][256];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) wave_sum[wave][4 * lane + j] = s[j];
-    __syncthreads();
-    if (threadIdx.x < 256) {
-        unsigned long long t = 0;
-#pragma unroll
-        for (int k = 0; k < kWaves; ++k) t += wave_sum[k][threadIdx.x];
-        out[(size_t)m * words + first + threadIdx.x] = (long long)t;
-    }
-}
+bool shape_ok(int n, int h, int w, int bits) { return n >= 1 && h >= 1 && w >= 1 && bits_ok(bits); }
 
-bool shape_ok(int n, int h, int w, int bits) { return n >= 1 && h >= 1 && w >= 1 && bits >= kMinBits && bits <= kMaxBits; }
-
-// blocks per image: one per kSpanMin pixels, fewer once the launch has blocks_target blocks
+// blocks per image: one per kSpanMin pixels
 int blocks_per_image(int n, int h, int w, int bits) {
-    const size_t hw = (size_t)h * (size_t)w;
-    const size_t spans = (hw + kSpanMin - 1) / kSpanMin;
-    const size_t cap = std::max<size_t>(1, (size_t)blocks_target(bits) / (size_t)n);
-    return (int)std::min(spans, cap);
+    return blocks_for(n, (size_t)h * (size_t)w, kSpanMin, hist_blocks_target(bits));
 }
 
 }  // namespace
@@ -164,16 +121,15 @@ extern "C" size_t cae_seg_roc_workspace(int n, int h, int w, int bits) {
 extern "C" int cae_seg_roc_hist(const float *logits, const uint8_t *target, const int32_t *extent, int n, int h, int w,
                                 int bits, int per_image, int64_t *hist, void *workspace, size_t workspace_bytes,
                                 void *stream) {
-    if (bits < kMinBits || bits > kMaxBits)
-        return fail(CAE_ERR_ARG, "cae_seg_roc_hist: %d bits outside %d..%d", bits, kMinBits, kMaxBits);
+    if (!bits_ok(bits)) return refuse_bits("cae_seg_roc_hist", bits);
     if (n < 0 || h < 1 || w < 1) return fail(CAE_ERR_ARG, "cae_seg_roc_hist: bad shape n=%d h=%d w=%d", n, h, w);
     if (n == 0) return CAE_OK;
     if (!logits || !target || !hist) return fail(CAE_ERR_ARG, "cae_seg_roc_hist: NULL logits, target or histogram");
-    if (reinterpret_cast<uintptr_t>(logits) & 3) return fail(CAE_ERR_ARG, "cae_seg_roc_hist: logits not 4-byte aligned");
+    if (misaligned(logits, 3)) return fail(CAE_ERR_ARG, "cae_seg_roc_hist: logits not 4-byte aligned");
     const size_t need = cae_seg_roc_workspace(n, h, w, bits);
     if (!workspace || workspace_bytes < need)
         return fail(CAE_ERR_ARG, "cae_seg_roc_hist: workspace too small: %zu bytes needed", need);
-    if ((reinterpret_cast<uintptr_t>(workspace) & 15) || (reinterpret_cast<uintptr_t>(hist) & 7))
+    if (misaligned(workspace, 15) || misaligned(hist, 7))
         return fail(CAE_ERR_ARG, "cae_seg_roc_hist: workspace not 16-byte or histogram not 8-byte aligned");
     RocArgs a;
     a.logits = logits, a.target = target, a.extent = extent, a.partial = static_cast<uint32_t *>(workspace);
@@ -186,10 +142,5 @@ extern "C" int cae_seg_roc_hist(const float *logits, const uint8_t *target, cons
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(roc_hist_kernel, dim3((unsigned)((size_t)n * a.bx)), dim3(kThreads), lds, st, a);
     HIP_TRY(hipGetLastError());
-    const uint32_t words = 2u << bits;
-    const int m = per_image ? n : 1, sources = per_image ? a.bx : n * a.bx;
-    hipLaunchKernelGGL(roc_sum_kernel, dim3((unsigned)((size_t)m * (words / 256))), dim3(kSumThreads), 0, st, a.partial, sources, words,
-                       reinterpret_cast<long long *>(hist));
-    HIP_TRY(hipGetLastError());
-    return CAE_OK;
+    return launch_seg_histsum(a.partial, n, a.bx, per_image, bits, reinterpret_cast<long long *>(hist), st);
 }

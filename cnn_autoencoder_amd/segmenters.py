@@ -415,6 +415,54 @@ def threshold_logit(threshold: float, threshold_on: str = 'scores') -> float:
     return float(np.float32(np.log(np.float64(thr) / (1.0 - np.float64(thr)))))
 
 
+def _check_top_k(top_k) -> int:
+    if int(top_k) != top_k or top_k < 1:
+        raise ValueError(f'top_k must be a positive integer, got {top_k!r}')
+    return int(top_k)
+
+
+def _logits_arg(logits):
+    """fp32 logits (N,C,...) on the device, 1..256 classes, non-empty planes -> (contiguous, n, c, space, pixels)"""
+    _lib.require_gpu()
+    if not isinstance(logits, torch.Tensor) or logits.dim() < 2 or logits.dtype != torch.float32 or not logits.is_cuda:
+        raise ValueError('expected fp32 logits (N,C,...) on the device')
+    if not 1 <= logits.size(1) <= 256:
+        raise ValueError(f'{logits.size(1)} classes outside 1..256')
+    n, c, space = logits.size(0), logits.size(1), tuple(logits.shape[2:])
+    hw = int(np.prod(space)) if space else 1
+    if n and hw < 1:
+        raise ValueError(f'empty planes: {tuple(logits.shape)}')
+    return logits.contiguous(), n, c, space, hw  # (a view of a larger buffer at any element offset is read in place)
+
+
+def _one_class_logits_arg(logits):
+    """fp32 logits (N,1,H,W) of a one-class head on the device, non-empty planes -> (contiguous, n, h, w)"""
+    _lib.require_gpu()
+    if not isinstance(logits, torch.Tensor) or logits.dim() != 4 or logits.dtype != torch.float32 or not logits.is_cuda:
+        raise ValueError('expected fp32 logits (N,1,H,W) on the device')
+    if logits.size(1) != 1:
+        raise ValueError(f'the ROC histogram is built for a one-class head, got {logits.size(1)} classes')
+    n, _, h, w = logits.shape
+    if n and (h < 1 or w < 1):
+        raise ValueError(f'empty planes: {tuple(logits.shape)}')
+    return logits.contiguous(), n, h, w  # (a view of a larger buffer at any element offset is read in place)
+
+
+def _target_arg(target, dev, *dims) -> torch.Tensor:
+    """a uint8 target of dims[0] x dims[1] ... labels -> on the device, contiguous"""
+    if not isinstance(target, torch.Tensor) or target.dtype != torch.uint8 or target.numel() != int(np.prod(dims)):
+        raise ValueError(f"expected a uint8 target of {' x '.join(str(d) for d in dims)} labels")
+    return target.to(dev).contiguous()
+
+
+def _workspace(nbytes: int, dev) -> torch.Tensor:
+    return torch.empty(max((int(nbytes) + 7) // 8, 1), dtype=torch.int64, device=dev)
+
+
+def _ptr(v):
+    return None if v is None else v.data_ptr()
+
+
 @torch.no_grad()
 def predict(logits: torch.Tensor, target: Optional[torch.Tensor] = None, threshold: float = 0.5,
             threshold_on: str = 'scores', top_k: int = 5, scores: bool = False) -> Dict:
@@ -426,24 +474,10 @@ def predict(logits: torch.Tensor, target: Optional[torch.Tensor] = None, thresho
     cls against target > 0; several -- tp = #{cls == target}, fp = fn = pixels - tp, tp_top = #{target among the
     min(top_k, C) largest logits}."""
     t = threshold_logit(threshold, threshold_on)  # ValueError before anything else
-    if int(top_k) != top_k or top_k < 1:
-        raise ValueError(f'top_k must be a positive integer, got {top_k!r}')
-    _lib.require_gpu()
-    if not isinstance(logits, torch.Tensor) or logits.dim() < 2 or logits.dtype != torch.float32 or not logits.is_cuda:
-        raise ValueError('expected fp32 logits (N,C,...) on the device')
-    if not 1 <= logits.size(1) <= 256:
-        raise ValueError(f'{logits.size(1)} classes outside 1..256')
-    logits = logits.contiguous()  # (a view of a larger buffer at any element offset is read in place)
-    n, c, space = logits.size(0), logits.size(1), tuple(logits.shape[2:])
-    hw = int(np.prod(space)) if space else 1
-    if n and hw < 1:
-        raise ValueError(f'empty planes: {tuple(logits.shape)}')
+    top_k = _check_top_k(top_k)
+    logits, n, c, space, hw = _logits_arg(logits)
     dev = logits.device
-    tgt = None
-    if target is not None:
-        if not isinstance(target, torch.Tensor) or target.dtype != torch.uint8 or target.numel() != n * hw:
-            raise ValueError(f'expected a uint8 target of {n} x {hw} labels')
-        tgt = target.to(dev).contiguous()
+    tgt = None if target is None else _target_arg(target, dev, n, hw)
     with torch.cuda.device(dev):
         cls = torch.empty((n,) + space, dtype=torch.uint8, device=dev)
         sc = torch.empty_like(logits) if scores else None
@@ -451,11 +485,9 @@ def predict(logits: torch.Tensor, target: Optional[torch.Tensor] = None, thresho
         L = _lib.lib()
         if tgt is not None:
             counts = torch.empty((n, len(COUNT_KEYS)), dtype=torch.int64, device=dev)
-            ws = torch.empty(max(int(L.cae_seg_predict_workspace(n, c, hw)) // 8, 1), dtype=torch.int64, device=dev)
-        ptr = lambda v: None if v is None else v.data_ptr()
-        _lib.check(L.cae_seg_predict(logits.data_ptr(), ptr(tgt), n, c, max(hw, 1), t, int(top_k), cls.data_ptr(),
-                                     ptr(sc), ptr(counts), ptr(ws), 0 if ws is None else ws.numel() * 8,
-                                     _lib.stream_ptr()))
+            ws = _workspace(L.cae_seg_predict_workspace(n, c, hw), dev)
+        _lib.check(L.cae_seg_predict(logits.data_ptr(), _ptr(tgt), n, c, max(hw, 1), t, top_k, cls.data_ptr(), _ptr(sc),
+                                     _ptr(counts), _ptr(ws), 0 if ws is None else ws.numel() * 8, _lib.stream_ptr()))
     return dict(cls=cls, scores=sc, counts=counts)
 
 
@@ -508,6 +540,33 @@ def roc_bin_edges(bits: int = ROC_BITS) -> np.ndarray:
     return edges
 
 
+def _roc_histogram(logits, target, cover, extent, bits, per_image) -> torch.Tensor:
+    """roc_histogram, or with a ``cover`` object_roc_histogram"""
+    bits = _check_roc_bits(bits)
+    logits, n, h, w = _one_class_logits_arg(logits)
+    dev = logits.device
+    tgt = _target_arg(target, dev, n, h, w)
+    cov = None if cover is None else _check_cover(cover, n, h * w, dev)
+    ext = _extent_arg(extent, n, dev)
+    m = n if per_image else 1
+    with torch.cuda.device(dev):
+        if n == 0:
+            return torch.zeros((m, 2, 1 << bits) if per_image else (2, 1 << bits), dtype=torch.int64, device=dev)
+        L = _lib.lib()
+        hist = torch.empty((m, 2, 1 << bits), dtype=torch.int64, device=dev)
+        tail = (_ptr(ext), n, h, w, bits, int(bool(per_image)), hist.data_ptr())
+        if cov is None:
+            ws = _workspace(L.cae_seg_roc_workspace(n, h, w, bits), dev)
+            rc = L.cae_seg_roc_hist(logits.data_ptr(), tgt.data_ptr(), *tail, ws.data_ptr(), ws.numel() * 8,
+                                    _lib.stream_ptr())
+        else:
+            ws = _workspace(L.cae_seg_object_roc_workspace(n, h, w, bits), dev)
+            rc = L.cae_seg_object_roc_hist(logits.data_ptr(), tgt.data_ptr(), cov.data_ptr(), *tail, ws.data_ptr(),
+                                           ws.numel() * 8, _lib.stream_ptr())
+        _lib.check(rc)
+    return hist if per_image else hist[0]
+
+
 @torch.no_grad()
 def roc_histogram(logits: torch.Tensor, target: torch.Tensor, extent=None, bits: int = ROC_BITS,
                   per_image: bool = False) -> torch.Tensor:
@@ -516,32 +575,7 @@ def roc_histogram(logits: torch.Tensor, target: torch.Tensor, extent=None, bits:
     over the batch -- or (N, 2, 2^bits) with ``per_image`` (cae_seg_roc_hist; asynchronous on the current stream).
     ``extent``: (N,2) integers (rows, cols): only the pixels y < rows, x < cols of each image are counted (values are
     clamped to the plane).  Histograms are exact and add; ``roc_from_histogram`` makes curve and AUC of them."""
-    bits = _check_roc_bits(bits)
-    _lib.require_gpu()
-    if not isinstance(logits, torch.Tensor) or logits.dim() != 4 or logits.dtype != torch.float32 or not logits.is_cuda:
-        raise ValueError('expected fp32 logits (N,1,H,W) on the device')
-    if logits.size(1) != 1:
-        raise ValueError(f'the ROC histogram is built for a one-class head, got {logits.size(1)} classes')
-    n, _, h, w = logits.shape
-    if n and (h < 1 or w < 1):
-        raise ValueError(f'empty planes: {tuple(logits.shape)}')
-    if not isinstance(target, torch.Tensor) or target.dtype != torch.uint8 or target.numel() != n * h * w:
-        raise ValueError(f'expected a uint8 target of {n} x {h} x {w} labels')
-    logits = logits.contiguous()  # (a view of a larger buffer at any element offset is read in place)
-    dev = logits.device
-    tgt = target.to(dev).contiguous()
-    ext = _extent_arg(extent, n, dev)
-    m = n if per_image else 1
-    with torch.cuda.device(dev):
-        if n == 0:
-            return torch.zeros((m, 2, 1 << bits) if per_image else (2, 1 << bits), dtype=torch.int64, device=dev)
-        L = _lib.lib()
-        hist = torch.empty((m, 2, 1 << bits), dtype=torch.int64, device=dev)
-        ws = torch.empty(int(L.cae_seg_roc_workspace(n, h, w, bits)) // 8, dtype=torch.int64, device=dev)
-        _lib.check(L.cae_seg_roc_hist(logits.data_ptr(), tgt.data_ptr(), None if ext is None else ext.data_ptr(), n, h, w,
-                                      bits, int(bool(per_image)), hist.data_ptr(), ws.data_ptr(), ws.numel() * 8,
-                                      _lib.stream_ptr()))
-    return hist if per_image else hist[0]
+    return _roc_histogram(logits, target, None, extent, bits, per_image)
 
 
 def roc_from_histogram(hist) -> Dict:
@@ -606,10 +640,6 @@ def _extent_arg(extent, n: int, dev):
     return ext.clamp(i32.min, i32.max).to(device=dev, dtype=torch.int32).contiguous()
 
 
-def _workspace(nbytes: int, dev) -> torch.Tensor:
-    return torch.empty(max((int(nbytes) + 7) // 8, 1), dtype=torch.int64, device=dev)
-
-
 @torch.no_grad()
 def components(target: torch.Tensor, extent=None, by_value: bool = False):
     """uint8 label planes (N,H,W) on the device, read as they stand -> (labels (N,H,W) int32, n_objects (N,) int64):
@@ -634,9 +664,8 @@ def components(target: torch.Tensor, extent=None, by_value: bool = False):
         if n:
             L = _lib.lib()
             ws = _workspace(L.cae_seg_components_workspace(n, h, w), dev)
-            _lib.check(L.cae_seg_components(tgt.data_ptr(), None if ext is None else ext.data_ptr(), n, h, w,
-                                            int(bool(by_value)), labels.data_ptr(), count.data_ptr(), ws.data_ptr(),
-                                            ws.numel() * 8, _lib.stream_ptr()))
+            _lib.check(L.cae_seg_components(tgt.data_ptr(), _ptr(ext), n, h, w, int(bool(by_value)), labels.data_ptr(),
+                                            count.data_ptr(), ws.data_ptr(), ws.numel() * 8, _lib.stream_ptr()))
     return labels, count
 
 
@@ -662,8 +691,8 @@ def object_cover(labels: torch.Tensor, extent=None) -> torch.Tensor:
         if n:
             L = _lib.lib()
             ws = _workspace(L.cae_seg_object_cover_workspace(n, h, w), dev)
-            _lib.check(L.cae_seg_object_cover(lab.data_ptr(), None if ext is None else ext.data_ptr(), n, h, w,
-                                              cover.data_ptr(), ws.data_ptr(), ws.numel() * 8, _lib.stream_ptr()))
+            _lib.check(L.cae_seg_object_cover(lab.data_ptr(), _ptr(ext), n, h, w, cover.data_ptr(), ws.data_ptr(),
+                                              ws.numel() * 8, _lib.stream_ptr()))
     return cover
 
 
@@ -681,28 +710,16 @@ def object_counts(logits: torch.Tensor, target: torch.Tensor, cover: torch.Tenso
     and cover uint8 / uint16 of N x pixels entries; threshold, threshold_on and top_k as in ``predict``.  With the cover
     of ``object_cover`` these are the reference's object-level counts; any uint16 weights are summed exactly."""
     t = threshold_logit(threshold, threshold_on)  # ValueError before anything else
-    if int(top_k) != top_k or top_k < 1:
-        raise ValueError(f'top_k must be a positive integer, got {top_k!r}')
-    _lib.require_gpu()
-    if not isinstance(logits, torch.Tensor) or logits.dim() < 2 or logits.dtype != torch.float32 or not logits.is_cuda:
-        raise ValueError('expected fp32 logits (N,C,...) on the device')
-    if not 1 <= logits.size(1) <= 256:
-        raise ValueError(f'{logits.size(1)} classes outside 1..256')
-    logits = logits.contiguous()  # (a view of a larger buffer at any element offset is read in place)
-    n, c, space = logits.size(0), logits.size(1), tuple(logits.shape[2:])
-    hw = int(np.prod(space)) if space else 1
-    if n and hw < 1:
-        raise ValueError(f'empty planes: {tuple(logits.shape)}')
+    top_k = _check_top_k(top_k)
+    logits, n, c, _, hw = _logits_arg(logits)
     dev = logits.device
-    if not isinstance(target, torch.Tensor) or target.dtype != torch.uint8 or target.numel() != n * hw:
-        raise ValueError(f'expected a uint8 target of {n} x {hw} labels')
-    tgt, cov = target.to(dev).contiguous(), _check_cover(cover, n, hw, dev)
+    tgt, cov = _target_arg(target, dev, n, hw), _check_cover(cover, n, hw, dev)
     with torch.cuda.device(dev):
         counts = torch.empty((n, len(COUNT_KEYS)), dtype=torch.int64, device=dev)
         if n:
             L = _lib.lib()
             ws = _workspace(L.cae_seg_object_counts_workspace(n, c, hw), dev)
-            _lib.check(L.cae_seg_object_counts(logits.data_ptr(), tgt.data_ptr(), cov.data_ptr(), n, c, hw, t, int(top_k),
+            _lib.check(L.cae_seg_object_counts(logits.data_ptr(), tgt.data_ptr(), cov.data_ptr(), n, c, hw, t, top_k,
                                                counts.data_ptr(), ws.data_ptr(), ws.numel() * 8, _lib.stream_ptr()))
     return counts
 
@@ -713,30 +730,4 @@ def object_roc_histogram(logits: torch.Tensor, target: torch.Tensor, cover: torc
     """``roc_histogram`` with every pixel adding ``cover`` (uint16, N x H x W) instead of 1 (cae_seg_object_roc_hist;
     asynchronous on the current stream): with the cover of ``object_cover`` the histogram of the pixels of all object
     boxes.  Same arguments, layout and bins otherwise; ``roc_from_histogram`` takes it as it is."""
-    bits = _check_roc_bits(bits)
-    _lib.require_gpu()
-    if not isinstance(logits, torch.Tensor) or logits.dim() != 4 or logits.dtype != torch.float32 or not logits.is_cuda:
-        raise ValueError('expected fp32 logits (N,1,H,W) on the device')
-    if logits.size(1) != 1:
-        raise ValueError(f'the ROC histogram is built for a one-class head, got {logits.size(1)} classes')
-    n, _, h, w = logits.shape
-    if n and (h < 1 or w < 1):
-        raise ValueError(f'empty planes: {tuple(logits.shape)}')
-    if not isinstance(target, torch.Tensor) or target.dtype != torch.uint8 or target.numel() != n * h * w:
-        raise ValueError(f'expected a uint8 target of {n} x {h} x {w} labels')
-    logits = logits.contiguous()  # (a view of a larger buffer at any element offset is read in place)
-    dev = logits.device
-    tgt, cov = target.to(dev).contiguous(), _check_cover(cover, n, h * w, dev)
-    ext = _extent_arg(extent, n, dev)
-    m = n if per_image else 1
-    with torch.cuda.device(dev):
-        if n == 0:
-            return torch.zeros((m, 2, 1 << bits) if per_image else (2, 1 << bits), dtype=torch.int64, device=dev)
-        L = _lib.lib()
-        hist = torch.empty((m, 2, 1 << bits), dtype=torch.int64, device=dev)
-        ws = _workspace(L.cae_seg_object_roc_workspace(n, h, w, bits), dev)
-        _lib.check(L.cae_seg_object_roc_hist(logits.data_ptr(), tgt.data_ptr(), cov.data_ptr(),
-                                             None if ext is None else ext.data_ptr(), n, h, w, bits,
-                                             int(bool(per_image)), hist.data_ptr(), ws.data_ptr(), ws.numel() * 8,
-                                             _lib.stream_ptr()))
-    return hist if per_image else hist[0]
+    return _roc_histogram(logits, target, cover, extent, bits, per_image)

@@ -613,8 +613,7 @@ class SlideCoder:
             raise ValueError(f'the head expects {seg._channels_bn} latent channels (channels_bn), the codec has '
                              f'{self.eb.channels}')
         segmenters.threshold_logit(threshold, threshold_on)
-        if int(top_k) != top_k or top_k < 1:
-            raise ValueError(f'top_k must be a positive integer, got {top_k!r}')
+        top_k = segmenters._check_top_k(top_k)
         if h % 2 ** self.level or w % 2 ** self.level:
             raise ValueError(f'tiles of {h} x {w} pixels are no multiple of 2^{self.level}')
         roc = None
@@ -631,7 +630,7 @@ class SlideCoder:
                 raise ValueError('object_level needs targets: the objects are those of the label maps')
             segmenters._check_planes(1, int(h), int(w))
         return self._segment_batches(payload_batches, int(h), int(w), seg, targets,
-                                     dict(threshold=threshold, threshold_on=threshold_on, top_k=int(top_k), scores=scores),
+                                     dict(threshold=threshold, threshold_on=threshold_on, top_k=top_k, scores=scores),
                                      keep_logits, to_host, roc, iter(extents) if extents is not None else None,
                                      bool(object_level))
 

@@ -581,6 +581,8 @@ def segment_image(input_filename: str, seg_model, output_filename: str, data_gro
     tiles = z.chunk_indices()
     lo, hi = slide.tile_range(rank, world, len(tiles))
     groups = list(_batches(tiles[lo:hi], batch_tiles))
+    # the real pixels (rows, cols) of every tile: an edge chunk is padded beyond them, and the padding is in no histogram
+    sizes = [[(min(ph, H - i * ph), min(pw, W - j * pw)) for i, j, _ in g] for g in groups]
 
     def chunks(group):
         bufs = [z.read_chunk_bytes(i) for i in group]
@@ -596,33 +598,29 @@ def segment_image(input_filename: str, seg_model, output_filename: str, data_gro
             out[t, :part.shape[0], :part.shape[1]] = part
         return out
 
-    def extents(group):  # the real pixels of every tile: the padding of the edge chunks is in no histogram
-        return np.array([(min(ph, H - i * ph), min(pw, W - j * pw)) for i, j, _ in group], dtype=np.int32).reshape(-1, 2)
-
     stream = sc.segment_batches((chunks(g) for g in groups), ph, pw, seg,
                                 targets=None if tz is None else (labels(g) for g in groups), threshold=threshold,
                                 threshold_on=threshold_on, top_k=top_k, scores=scores, to_host=True, roc_bits=roc_bits,
-                                extents=(extents(g) for g in groups) if roc_bits is not None or object_level else None,
+                                extents=(np.array(s, dtype=np.int32).reshape(-1, 2) for s in sizes)
+                                if roc_bits is not None or object_level else None,
                                 object_level=bool(object_level))
     records, obj_records, obj_numbers = [], [], []
-    roc_hist = obj_hist = None
-    for group, res in zip(groups, stream):  # res['cls']: pinned ring buffer, written out before the generator advances
-        if roc_bits is not None:
-            roc_hist = res['roc_hist'] if roc_hist is None else roc_hist + res['roc_hist']
-            if object_level:
-                obj_hist = res['object_roc_hist'] if obj_hist is None else obj_hist + res['object_roc_hist']
+    hists = {}  # 'roc_hist', 'object_roc_hist' -> this rank's sum, on the device
+    # res['cls']: pinned ring buffer, written out before the generator advances
+    for group, real, res in zip(groups, sizes, stream):
+        for key in ('roc_hist', 'object_roc_hist'):
+            if key in res:
+                hists[key] = res[key] + hists.get(key, 0)
         if object_level:
             obj_records.append(torch.from_numpy(np.array(res['object_counts'], dtype=np.int64)))
             obj_numbers.append(torch.from_numpy(np.array(res['n_objects'], dtype=np.int64)))
-        for t, (i, j, _) in enumerate(group):
-            ch, cw = min(ph, H - i * ph), min(pw, W - j * pw)
+        for t, ((i, j, _), (ch, cw)) in enumerate(zip(group, real)):
             zc.write_chunk((i, j), res['cls'][t, :ch, :cw].astype(zc.dtype))
             if zs is not None:
                 zs.write_chunk((0, i, j), res['scores'][t, :, :ch, :cw])
         if res['counts'] is not None:
             rec = np.array(res['counts'], dtype=np.int64)
-            for t, (i, j, _) in enumerate(group):
-                ch, cw = min(ph, H - i * ph), min(pw, W - j * pw)
+            for t, (ch, cw) in enumerate(real):
                 if ch * cw == ph * pw:
                     continue
                 if C > 1:  # the padding (label 255) is in neither tp nor tp_top
@@ -644,10 +642,15 @@ def segment_image(input_filename: str, seg_model, output_filename: str, data_gro
             pass
         return slide.gather_counts(local).cpu().numpy()
 
-    def write_curve(group, roc):
+    def curve(group, hist, into):  # this rank's histogram (None: a rank without tiles) -> the slide's curve and AUC
+        if hist is None:
+            hist = torch.zeros((2, 1 << roc_bits), dtype=torch.int64, device='cuda')
+        roc = segmenters.roc_from_histogram(slide.reduce_histogram(hist))
+        into.update(auc=roc['auc'], auc_slack=roc['auc_slack'], roc=roc)
         for name, key in (('fpr', 'fpr'), ('tpr', 'tpr'), ('thrsh', 'score_thresholds'), ('thrsh_logit', 'thresholds')):
             v = roc[key].astype(np.float32)
-            ZarrArray.create(output_filename, f'{group}/{name}', v.shape, v.shape, np.float32, codec=Zlib(9))[:] = v
+            if rank == 0:
+                ZarrArray.create(output_filename, f'{group}/{name}', v.shape, v.shape, np.float32, codec=Zlib(9))[:] = v
 
     if tz is not None:
         allrec = gathered(records)
@@ -659,19 +662,9 @@ def segment_image(input_filename: str, seg_model, output_filename: str, data_gro
         obj = dict(segmenters.class_metrics(objrec.sum(axis=0), multiclass=C > 1), records=objrec,
                    n_objects=int(slide.reduce_histogram(numbers)[0]))
         if roc_bits is not None:
-            if obj_hist is None:  # a rank without tiles
-                obj_hist = torch.zeros((2, 1 << roc_bits), dtype=torch.int64, device='cuda')
-            roc = segmenters.roc_from_histogram(slide.reduce_histogram(obj_hist))
-            obj.update(auc=roc['auc'], auc_slack=roc['auc_slack'], roc=roc)
-            if rank == 0:
-                write_curve('object_level', roc)
+            curve('object_level', hists.get('object_roc_hist'), obj)
         out['object_level'] = obj
     if roc_bits is not None:
-        if roc_hist is None:  # a rank without tiles
-            roc_hist = torch.zeros((2, 1 << roc_bits), dtype=torch.int64, device='cuda')
-        roc = segmenters.roc_from_histogram(slide.reduce_histogram(roc_hist))
-        out.update(auc=roc['auc'], auc_slack=roc['auc_slack'], roc=roc)
-        if rank == 0:
-            write_curve('image_level', roc)
+        curve('image_level', hists.get('roc_hist'), out)
     _barrier()
     return out

@@ -310,6 +310,24 @@ def test_object_histograms_are_those_of_the_concatenated_boxes(bits, offset):
         assert torch.equal(plain, same)
 
 
+def test_object_histograms_merge_more_partials_than_the_merge_kernel_has_waves():
+    """5 planes of 264 x 265 are two blocks each: 10 sources of 64-bit words when summed over the batch (the merge
+    kernel has 8 waves, so two of them take a second source) and 2 per image"""
+    S = _seg()
+    names, h, w, bits = ['b10', 'rows', 'rings', 'b40', 'grid'], 264, 265, 8
+    n = len(names)
+    from cnn_autoencoder_amd import _lib
+    assert _lib.lib().cae_seg_object_roc_workspace(n, h, w, bits) == n * 2 * (2 << bits) * 8  # two partials a plane
+    target = np.stack([plane(k, h, w) for k in names])
+    logits = _logits(n, 1, h, w, bits + h, target, target)
+    _, _, boxes = OO.components(target)
+    cover = OO.cover(boxes, h, w).astype(np.uint16)
+    for per_image in (False, True):
+        got = S.object_roc_histogram(dev(logits), dev(target), dev(cover), bits=bits, per_image=per_image)
+        torch.cuda.synchronize()
+        assert np.array_equal(got.cpu().numpy(), OO.object_histogram(logits, target, boxes, bits, per_image=per_image))
+
+
 def test_sums_beyond_32_bits_are_exact():
     """cover 65535 on every pixel of a (264, 265) plane whose logits are one value: 69 960 x 65 535 > 2^32 in one bin"""
     S = _seg()
