@@ -182,6 +182,10 @@ SYMBOLS = {
     'cae_seg_object_roc_hist': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
                                         c_void_p, c_void_p, c_size_t, c_void_p]),
     'cae_seg_object_roc_workspace': (c_size_t, [c_int, c_int, c_int, c_int]),
+    'cae_seg_object_distances': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    'cae_seg_object_distances_workspace': (c_size_t, [c_int, c_int, c_int]),
+    'cae_seg_weight_map': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_float, c_float, c_int, c_size_t,
+                                   c_void_p, c_void_p, c_void_p]),
     'cae_seg_set_weights': (c_int, [c_void_p, c_void_p, c_int, c_void_p]),
     'cae_seg_pack_dev': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p]),
     'cae_seg_conv2d_workspace': (c_size_t, [c_int] * 6),

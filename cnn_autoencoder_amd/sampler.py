@@ -319,6 +319,96 @@ def _reflect(idx: np.ndarray, n: int) -> np.ndarray:
     return np.where(m >= n, 2 * n - 1 - m, m)
 
 
+class WeightsDistances:
+    """The reference's ``WeightsDistances`` (_augs.py:102-136) for a batch on the device: the U-Net border weight
+    ``class_weights[t] + w_0 exp(-(d1 + d2)^2 / (2 sigma^2))``, d1 and d2 the distances to the nearest and second-nearest
+    object of the plane (one object: ``exp(-d1^2 / (2 sigma^2))``; none: the class weight alone).
+
+    Called on label planes ``t`` ``[n, 1, h, w]`` (fp32 or int64, integer values) on the device, returns fp32
+    ``[n, 2, h, w]``: the weights, then the labels -- what ``SegLoss('WeightedBCELoss')`` takes.  The steps are
+    ``segmenters.components(t != 0)``, ``segmenters.object_distances`` and ``cae_seg_weight_map`` (contract in
+    include/cae_hip.h), then one read of the kernel's flag: a label outside ``class_weights`` raises IndexError, as
+    ``numpy.take`` does.  ``force_torch=True`` runs the reference's own procedure on the host (``scipy.ndimage.label``
+    and one ``distance_transform_edt`` per object) and uploads the result: a comparison path that nothing but this flag
+    selects.
+    """
+
+    def __init__(self, class_weights, sigma=5, w_0=10, force_torch: bool = False):
+        cw = np.asarray(class_weights, dtype=np.float32).reshape(-1)
+        if cw.size < 1:
+            raise ValueError('class_weights is empty')
+        sigma_2 = float(np.float32(2 * float(sigma) ** 2))
+        if not (math.isfinite(sigma_2) and sigma_2 > 0.0):
+            raise ValueError(f'sigma {sigma}')
+        self.class_weights = class_weights
+        self.sigma_2 = 2 * sigma ** 2
+        self.w_0 = w_0
+        self.force_torch = bool(force_torch)
+        self._cw, self._sigma_2 = cw, sigma_2
+        self._cw_dev = None
+
+    @staticmethod
+    def _planes(t):
+        if not isinstance(t, torch.Tensor) or t.dim() != 4 or t.dtype not in (torch.float32, torch.int64):
+            raise ValueError('expected label planes [n, 1, h, w], fp32 or int64')
+        if t.shape[1] != 1:
+            raise ValueError(f'the weight map is built for one target channel, got {t.shape[1]}')
+        return t.to(torch.float32).contiguous()
+
+    def __call__(self, t: torch.Tensor) -> torch.Tensor:
+        return self.apply(t, check=True)
+
+    @torch.no_grad()
+    def apply(self, t: torch.Tensor, check: bool = True) -> torch.Tensor:
+        """``__call__``; with ``check=False`` the flag is not read back (a caller that has checked its labels against
+        the table before: the call then stays asynchronous)."""
+        t = self._planes(t)
+        if self.force_torch:
+            return self._host(t)
+        from . import segmenters
+        _lib.require_gpu()
+        if not t.is_cuda:
+            raise ValueError('expected label planes on the device')
+        n, _, h, w = t.shape
+        dev = t.device
+        with torch.cuda.device(dev):
+            labels, count = segmenters.components((t[:, 0] != 0).to(torch.uint8))
+            d2 = segmenters.object_distances(labels)
+            if self._cw_dev is None or self._cw_dev.device != dev:
+                self._cw_dev = torch.from_numpy(self._cw).to(dev)
+            out = torch.empty((n, 2, h, w), dtype=torch.float32, device=dev)
+            flag = torch.zeros(1, dtype=torch.int32, device=dev)
+            if n:
+                _lib.check(_lib.lib().cae_seg_weight_map(
+                    t.data_ptr(), d2.data_ptr(), count.data_ptr(), self._cw_dev.data_ptr(), self._cw.size, self._sigma_2,
+                    float(self.w_0), n, h * w, out.data_ptr(), flag.data_ptr(), _lib.stream_ptr()))
+            if check and n and int(flag.item()):
+                raise IndexError(f'a label lies outside the {self._cw.size} class weights')
+        return out
+
+    def _host(self, t: torch.Tensor) -> torch.Tensor:
+        """the reference's ``__call__`` per plane, in numpy on the host"""
+        from scipy.ndimage import distance_transform_edt, label
+        planes = t.cpu().numpy()
+        out = []
+        for target in planes:  # [1, h, w]
+            w_x = np.take(self._cw, target.astype(np.int32)).astype(np.float32)
+            if target.sum() > 0:
+                target_labels, num_objects = label(target[0], structure=np.ones((3, 3)))
+                dist = []
+                for obj in range(1, num_objects + 1):
+                    remaining = np.ones_like(target[0])
+                    remaining[target_labels == obj] = 0
+                    dist.append(distance_transform_edt(remaining).astype(np.float32))
+                dist = np.sort(np.stack(dist), axis=0)
+                s = dist[0] + dist[1] if num_objects > 1 else dist[0]
+                w_x = w_x + np.float32(self.w_0) * np.exp(-s ** 2 / np.float32(self._sigma_2))
+            out.append(np.concatenate((w_x.astype(np.float32), target), axis=0))
+        if not out:
+            return torch.empty((0, 2) + tuple(t.shape[2:]), dtype=torch.float32, device=t.device)
+        return torch.from_numpy(np.stack(out)).to(t.device)
+
+
 class LabeledPatchSampler(PatchSampler):
     """Pairs of an image patch and its pixel labels: ``PatchSampler`` over ``pool`` plus ``labels``, uint8 ``[T, H, W, K]``
     (``[T, H, W]``: one channel), 1 <= K <= 4, of the pool's ``T, H, W``.  Image and mask share tile, crop window, ragged
@@ -335,12 +425,22 @@ class LabeledPatchSampler(PatchSampler):
     Iterating yields ``steps_per_epoch`` batches ``(x, t)``: ``x`` fp32 ``[n, C, ps, ps]`` and ``t`` ``[n, Kt, ps, ps]``
     (``Kt`` = 1 with ``map_labels``, else K), what ``seg_train.train_step`` and ``SegLoss('BCELoss')`` take; an int64 ``t``
     with ``Kt`` = 1 is yielded as ``[n, ps, ps]``, the class map ``SegLoss('CELoss')`` takes.
+
+    ``class_weights``, ``weights_map_sigma`` and ``weights_map_w`` (all three, as in ``get_zarr_transform``, or none) add
+    the reference's border weight map: ``t`` becomes fp32 ``[n, 2, ps, ps]``, ``WeightsDistances(class_weights,
+    weights_map_sigma, weights_map_w)`` of the labels and then the labels, what ``SegLoss('WeightedBCELoss')`` takes.  It
+    needs ``Kt`` = 1.  The map is computed on the final target, after crop and rotation, so the weights belong to the
+    labels the loss sees (objects cut by the crop window count as the pieces that are left); the order of the reference's
+    own pipeline lies in ``zarrdataset`` and is not pinned here.  The pool's largest label value (with ``map_labels`` the
+    largest channel sum) is checked against ``class_weights`` once at construction -- IndexError -- so no batch reads the
+    kernel's flag back.
     """
 
     def __init__(self, pool, labels, patch_size: int, data_mode: str = 'train', add_noise: bool = False,
                  noise_std: float = 0.001, normalize: bool = False, rotation: bool = False, degrees: float = 30.0,
                  seed: int = 0, force_torch: bool = False, tile_hw=None, batch_size: int = 16,
-                 steps_per_epoch: Optional[int] = None, map_labels: bool = False, target_data_type=torch.float32):
+                 steps_per_epoch: Optional[int] = None, map_labels: bool = False, target_data_type=torch.float32,
+                 class_weights=None, weights_map_sigma=None, weights_map_w=None):
         if target_data_type not in (torch.float32, torch.int64):
             raise ValueError('Convertion to data type {} not supported'.format(target_data_type))
         super().__init__(pool, patch_size, data_mode=data_mode, add_noise=add_noise, noise_std=noise_std, normalize=normalize,
@@ -361,6 +461,18 @@ class LabeledPatchSampler(PatchSampler):
         self.Kt = 1 if self.map_labels else self.K
         self.target_data_type = target_data_type
         self._labels_dev = None
+        self.weights = None
+        given = [v is not None for v in (class_weights, weights_map_sigma, weights_map_w)]
+        if any(given):
+            if not all(given):
+                raise ValueError('class_weights, weights_map_sigma and weights_map_w are given together or not at all')
+            if self.Kt != 1:
+                raise ValueError(f'the weight map needs one target channel, got {self.Kt} (map_labels sums them into one)')
+            self.weights = WeightsDistances(class_weights, sigma=weights_map_sigma, w_0=weights_map_w,
+                                            force_torch=self.force_torch)
+            top = int(self.labels.sum(dim=3, dtype=torch.int64).max()) if self.map_labels else int(self.labels.max())
+            if top >= self.weights._cw.size:
+                raise IndexError(f'the largest label value {top} lies outside the {self.weights._cw.size} class weights')
 
     @classmethod
     def from_zarr(cls, stores: Sequence[str], data_group: str = '0/0', labels_data_group: str = 'labels/0/0',
@@ -395,7 +507,7 @@ class LabeledPatchSampler(PatchSampler):
         if self.force_torch:
             g = self.torch_normals(n, seed, int(sample_base)) if std != 0.0 else None
             x, t = self._gather_host(tile, y0, x0, cs, std, g)
-            return x, t.to(self.target_data_type)
+            return x, self._target(t)
         pool, tile_hw = self._device_pool()
         if self._labels_dev is None:
             self._labels_dev = self.labels.to(pool.device)
@@ -413,7 +525,13 @@ class LabeledPatchSampler(PatchSampler):
                 cs_dev[1].data_ptr() if cs is not None else None, seed, int(sample_base) & 0xFFFFFFFF, std,
                 int(self.normalize), int(self.map_labels), n, ps, ws.data_ptr() if ws is not None else None, ws_bytes,
                 x.data_ptr(), t.data_ptr(), _lib.stream_ptr()))
-        return x, t.to(self.target_data_type)
+        return x, self._target(t)
+
+    def _target(self, t: torch.Tensor) -> torch.Tensor:
+        """the fp32 labels ``[n, Kt, ps, ps]`` as the sampler hands them out: cast, or with their weight map in front"""
+        if self.weights is None:
+            return t.to(self.target_data_type)
+        return self.weights.apply(t, check=False)  # the pool's labels were checked against the table at construction
 
     def _gather_host(self, tile, y0, x0, cs, std, g):
         """The contract in float64 numpy on the host, uploaded as float32 to the pool's device.  The patch ``p`` is
@@ -461,4 +579,4 @@ class LabeledPatchSampler(PatchSampler):
             self._next_tile = 0
         for _ in range(self.steps_per_epoch):
             x, t = self.sample(self.batch_size)
-            yield x, (t[:, 0] if self.Kt == 1 and self.target_data_type == torch.int64 else t)
+            yield x, (t[:, 0] if self.Kt == 1 and self.target_data_type == torch.int64 and self.weights is None else t)

@@ -696,6 +696,39 @@ def object_cover(labels: torch.Tensor, extent=None) -> torch.Tensor:
     return cover
 
 
+MAX_DISTANCE_EDGE = 32768  # cae_seg_object_distances: 2 (edge - 1)^2 stays below 2^31 - 1
+
+
+@torch.no_grad()
+def object_distances(labels: torch.Tensor) -> torch.Tensor:
+    """labels (N,H,W) int32 of ``components`` (0 is background; only that the labels of two objects differ matters) ->
+    d2 (N,2,H,W) int32 on the device (cae_seg_object_distances; asynchronous on the current stream): plane 0 the squared
+    Euclidean distance to the nearest foreground pixel (0 on foreground), plane 1 the smallest squared distance to a
+    pixel of another object than the one that gives plane 0; -1 where there is no such object.  Exact integers, the
+    distances of the reference's ``WeightsDistances`` (one distance transform per object there, two passes here)."""
+    if not isinstance(labels, torch.Tensor) or labels.dim() != 3 or labels.dtype != torch.int32:
+        raise ValueError('expected int32 labels (N,H,W) on the device')
+    n, h, w = labels.shape
+    if n and (h < 1 or w < 1):
+        raise ValueError(f'empty planes: {n} x {h} x {w}')
+    if max(h, w) > MAX_DISTANCE_EDGE or h * w > 2 ** 31 - 1:
+        raise ValueError(f'planes of {h} x {w} pixels are too large: a squared distance is held in 32 bits '
+                         f'(H, W <= {MAX_DISTANCE_EDGE}, H W <= 2^31 - 1)')
+    _lib.require_gpu()
+    if not labels.is_cuda:
+        raise ValueError('expected int32 labels (N,H,W) on the device')
+    dev = labels.device
+    lab = labels.contiguous()
+    with torch.cuda.device(dev):
+        d2 = torch.empty((n, 2, h, w), dtype=torch.int32, device=dev)
+        if n:
+            L = _lib.lib()
+            ws = _workspace(L.cae_seg_object_distances_workspace(n, h, w), dev)
+            _lib.check(L.cae_seg_object_distances(lab.data_ptr(), n, h, w, d2.data_ptr(), ws.data_ptr(), ws.numel() * 8,
+                                                  _lib.stream_ptr()))
+    return d2
+
+
 def _check_cover(cover, n: int, hw: int, dev) -> torch.Tensor:
     if not isinstance(cover, torch.Tensor) or cover.dtype != torch.uint16 or cover.numel() != n * hw:
         raise ValueError(f'expected a uint16 cover of {n} x {hw} weights')

@@ -879,6 +879,53 @@ int cae_seg_object_roc_hist(const float *logits_dev, const uint8_t *target_dev, 
                             void *workspace_dev, size_t workspace_bytes, void *stream);
 size_t cae_seg_object_roc_workspace(int n, int h, int w, int bits);
 
+/* ---- Weight map of a label plane (csrc/cae_seg_distances.hip) -------------------------------------
+ * The reference's WeightsDistances (utils/datasets/_augs.py:102-136), the U-Net border weight
+ *   w = class_weights[target] + w_0 exp(-(d1 + d2)^2 / (2 sigma^2)),
+ * d1 and d2 the Euclidean distances of the pixel to the nearest and to the second-nearest object of its plane.  The
+ * reference runs one full-plane distance transform per object; here the two distances of every pixel come out of two
+ * passes whatever the number of objects.
+ *
+ * cae_seg_object_distances: labels_dev (n, h, w) int32 as cae_seg_components writes them (0 is background, any other
+ * value names an object; only that labels differ matters) -> d2_dev (n, 2, h, w) int32.  Plane 0: the squared Euclidean
+ * distance to the nearest foreground pixel, 0 on foreground.  Plane 1: the smallest squared distance to a pixel of an
+ * object other than the one that gives plane 0 (with equal distances to two objects both planes hold that value).  -1
+ * where no such object exists: plane 1 of a plane with one object, both planes of an empty plane.  Exact integers,
+ * bitwise repeatable: both are minima over sets that do not depend on the order of evaluation.
+ *   Column pass (one lane per column): for every pixel the two nearest foreground pixels of its column that carry
+ * distinct labels, as (squared row distance, label) records, from one downward and one upward scan that each keep the
+ * latest label and the latest different label.  Two labels per (row, column) are enough: a pixel hidden behind two
+ * other labels of its column is farther than both, and one of the two differs from the nearest object.
+ *   Row pass (one lane per pixel): the smallest (x - x')^2 + record over both records of all columns x' of the pixel's
+ * row, and the smallest of a label other than the best one's; the records pass through LDS in chunks of 256 columns, so
+ * w is not bounded by LDS.  w times 2 candidates per pixel.
+ *   workspace_dev: cae_seg_object_distances_workspace bytes (16 per pixel), 16-byte aligned.  Neither the output nor
+ * the workspace needs initialising.  No atomics; no block waits for another.  Two launches, asynchronous on `stream`.
+ * CAE_ERR_ARG before any launch: n < 0, h or w outside 1..32768 (so that every squared distance is below 2^31 - 1),
+ * h w > 2^31 - 1, and for n >= 1 a NULL or misaligned pointer or a workspace that is too small.  n == 0: CAE_OK, nothing
+ * launched.  The query returns 0 for refused shapes and for n == 0.
+ *
+ * cae_seg_weight_map: target_dev (n, hw) fp32 holding integer label values (what cae_t_sample_labeled_patches writes),
+ * d2_dev as above, n_objects_dev int64 [n] of cae_seg_components, class_weights_dev fp32 [n_class_weights] -> out_dev
+ * (n, 2, hw) fp32: plane 0 the weight, plane 1 the target, copied -- the concatenation the reference's weighted loss
+ * (BCEWeightedClassLoss) takes.  With k = (int)target, cw = class_weights[k] and d_i = (float)sqrt((double)d2_i), the correctly
+ * rounded double root rounded once to fp32 (scipy's float64 distance cast to float32):
+ *   n_objects == 0: w = cw
+ *   n_objects == 1: w = cw + w_0 expf(-(d_0 d_0) / sigma_2)
+ *   n_objects >= 2: w = cw + w_0 expf(-((d_0 + d_1) (d_0 + d_1)) / sigma_2)
+ * every operation rounded to fp32 on its own (no fused multiply-add); sigma_2 = 2 sigma^2 is formed by the caller.  An
+ * exponential below 2^-126 may be flushed to zero.  A target that is NaN, negative or >= n_class_weights writes NaN as
+ * its weight and sets *flag_dev to 1; flag_dev is a device int the caller zeroed, as in the head-training entry points.
+ * No target is used as an index before it is checked.  One launch, asynchronous on `stream`.  CAE_ERR_ARG before any
+ * launch: n < 0, hw < 1, n_class_weights < 1, sigma_2 not finite and positive, and for n >= 1 a NULL pointer.  n == 0:
+ * CAE_OK, nothing launched. */
+int cae_seg_object_distances(const int32_t *labels_dev, int n, int h, int w, int32_t *d2_dev, void *workspace_dev,
+                             size_t workspace_bytes, void *stream);
+size_t cae_seg_object_distances_workspace(int n, int h, int w);
+int cae_seg_weight_map(const float *target_dev, const int32_t *d2_dev, const int64_t *n_objects_dev,
+                       const float *class_weights_dev, int n_class_weights, float sigma_2, float w_0, int n, size_t hw,
+                       float *out_dev, int *flag_dev, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
