@@ -132,6 +132,9 @@ SYMBOLS = {
                                              c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_uint64,
                                              ctypes.c_uint32, c_float, c_int, c_int, c_int, c_int, c_void_p, c_size_t,
                                              c_void_p, c_void_p, c_void_p]),
+    'cae_t_elastic_deform': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p,
+                                     c_void_p, c_void_p]),
+    'cae_t_elastic_deform_workspace': (c_size_t, [c_int, c_int, c_int]),
     'cae_cpu_budget': (c_int, []),
     'cae_coder_lockstep': (c_int, []),
     'cae_coder_threads': (c_int, [c_int, c_int]),

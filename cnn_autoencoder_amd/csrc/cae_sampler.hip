@@ -28,6 +28,7 @@
 #include "cae_hip.h"
 #include "cae_internal.hpp"
 #include "cae_launch.hpp"
+#include "cae_spline.hpp"
 
 #include <hip/hip_runtime.h>
 
@@ -257,42 +258,10 @@ constexpr float SPLINE_GAIN = 384.0f;
 // float32 sum, and z^n is below 2^-93 from n = 64 on (the line's other end reaches the start with that weight).
 constexpr int START_TERMS = 28, POWER_TERMS = 64;
 
-// one pole over the line c[0], c[stride], ..., n values, in place; `gain` scales the line on the way in
-__device__ __forceinline__ void filter_pole(float *c, int n, int stride, float z, float gain) {
-    float zn = 1.0f;
-    for (int i = 0; i < min(n, POWER_TERMS); ++i) zn *= z;
-    if (n > POWER_TERMS) zn = 0.0f;
-    const float c0 = gain * c[0];
-    float acc = c0 + zn * (gain * c[(n - 1) * stride]), zi = z;
-    const int terms = min(n, START_TERMS);
-    for (int i = 1; i < terms; ++i) {
-        acc += zi * (gain * (c[i * stride] + zn * c[(n - 1 - i) * stride]));
-        zi *= z;
-    }
-    float v = c0 + z / (1.0f - zn * zn) * acc;
-    c[0] = v;
-    for (int i = 1; i < n; ++i) {
-        v = gain * c[i * stride] + z * v;
-        c[i * stride] = v;
-    }
-    v *= z / (z - 1.0f);
-    c[(n - 1) * stride] = v;
-    for (int i = n - 2; i >= 0; --i) {
-        v = z * (v - c[i * stride]);
-        c[i * stride] = v;
-    }
-}
-
+// (the recursion over one pole and `reflect` live in cae_spline.hpp, shared with the cubic spline of cae_elastic.hip)
 __device__ __forceinline__ void filter_line(float *c, int n, int stride) {
-    filter_pole(c, n, stride, POLE1, SPLINE_GAIN);
-    filter_pole(c, n, stride, POLE2, 1.0f);
-}
-
-// d c b a | a b c d | d c b a, as often as needed (|idx| is at most a few ps: see taps_of)
-__device__ __forceinline__ int reflect(int idx, int n) {
-    int m = idx % (2 * n);
-    if (m < 0) m += 2 * n;
-    return m >= n ? 2 * n - 1 - m : m;
+    filter_pole<START_TERMS, POWER_TERMS>(c, n, stride, POLE1, SPLINE_GAIN);
+    filter_pole<START_TERMS, POWER_TERMS>(c, n, stride, POLE2, 1.0f);
 }
 
 // the quartic B-spline at distance d; 0 from 2.5 on

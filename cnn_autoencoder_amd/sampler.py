@@ -12,6 +12,11 @@ image and pixel labels under one crop and one rotation, ``scipy.ndimage.rotate``
 the image, nearest neighbour on the mask), in ``cae_t_sample_labeled_patches``; its batches ``(x, t)`` are what
 ``seg_train.train_step`` takes.
 
+``elastic_deform`` stands where ``RandomElasticDeformationInput`` / ``RandomElasticDeformationInputTarget`` stand
+(_augs.py:26-49, 85-99; ``elastic_deformation=True``): a 3 x 3 grid of random displacements bent into a per-pixel field,
+the image resampled through the cubic B-spline and the mask by its nearest neighbour (``cae_t_elastic_deform``).  Both
+samplers apply it after their rotation with ``elastic_deformation=True``.
+
 Under several ranks every rank builds its own sampler and passes ``draw`` / ``sample`` a generator seeded per rank (and
 a per-rank ``seed`` for the noise): the sampler itself shares nothing between ranks.
 """
@@ -92,13 +97,16 @@ class PatchSampler:
     ``tile_hw`` (``[T, 2]``) gives the valid rows and columns of each tile where the pool pads ragged tiles; padding is
     never sampled as image.  ``seed`` keys the noise.  ``force_torch=True`` computes the same contract with torch ops on
     the pool's device (the comparison of tools/bench_sampler.py; it is not a fallback: nothing selects it but this flag).
+    ``elastic_deformation`` bends every patch after its rotation by ``elastic_deform`` with displacements drawn from
+    N(0, ``elastic_sigma``^2) (``RandomElasticDeformationInput(sigma=10)``).
 
     Iterating yields ``steps_per_epoch`` batches ``(x, x)`` of ``batch_size`` patches.
     """
 
     def __init__(self, pool, patch_size: int, data_mode: str = 'train', add_noise: bool = False, noise_std: float = 0.001,
                  normalize: bool = False, rotation: bool = False, degrees: float = 30.0, seed: int = 0,
-                 force_torch: bool = False, tile_hw=None, batch_size: int = 16, steps_per_epoch: Optional[int] = None):
+                 force_torch: bool = False, tile_hw=None, batch_size: int = 16, steps_per_epoch: Optional[int] = None,
+                 elastic_deformation: bool = False, elastic_sigma: float = 10.0):
         pool = torch.as_tensor(pool)
         if pool.dim() == 3:
             pool = pool[..., None]
@@ -116,6 +124,9 @@ class PatchSampler:
             raise ValueError(f'patch_size {patch_size}')
         if not (noise_std >= 0.0 and math.isfinite(noise_std)):
             raise ValueError(f'noise_std {noise_std}')
+        if not (elastic_sigma >= 0.0 and math.isfinite(elastic_sigma)):
+            raise ValueError(f'elastic_sigma {elastic_sigma}')
+        self.elastic_deformation, self.elastic_sigma = bool(elastic_deformation), float(elastic_sigma)
         self.pool = pool.contiguous()
         self.T, self.H, self.W, self.C = (int(v) for v in self.pool.shape)
         self.patch_size = int(patch_size)
@@ -177,6 +188,11 @@ class PatchSampler:
         """torchvision's RandomRotation: uniform in [-degrees, degrees]"""
         return (torch.rand(n, generator=generator, dtype=torch.float64) * 2.0 - 1.0) * self.degrees
 
+    def draw_displacement(self, n: int, generator: Optional[torch.Generator] = None) -> torch.Tensor:
+        """The displacement grids of ``n`` patches, float64 ``[n, 2, 3, 3]``: ``np.random.randn(2, 3, 3) * sigma`` per
+        patch.  Host code; ``sample`` calls it after ``draw``, and only with ``elastic_deformation``."""
+        return torch.randn(int(n), 2, 3, 3, generator=generator, dtype=torch.float64) * self.elastic_sigma
+
     # ---- device: the batch -------------------------------------------------------------------------------------------
     def _device_pool(self):
         if self._dev is None:
@@ -201,11 +217,18 @@ class PatchSampler:
         std = self.noise_std if self.add_noise else 0.0
         return tile, y0, x0, n, cs, seed, std
 
-    def gather(self, tile, y0, x0, angle=None, noise_seed: Optional[int] = None, sample_base: int = 0) -> torch.Tensor:
+    def gather(self, tile, y0, x0, angle=None, noise_seed: Optional[int] = None, sample_base: int = 0,
+               displacement=None) -> torch.Tensor:
         """The ``[n, C, ps, ps]`` fp32 batch of the given draw on the device.  ``angle`` in degrees (None: no rotation).
+        ``displacement`` (``[n, 2, 3, 3]``, None: no deformation) bends the rotated batch by ``elastic_deform``.
         ``noise_seed`` keys the noise of this batch (None: the sampler's ``seed``); it is used with ``add_noise`` only.
         ``sample_base`` is the index of the batch's first sample in the noise stream, so a batch can be gathered in
         parts.  A tile index outside the pool raises ValueError before anything is launched."""
+        x = self._gather_plain(tile, y0, x0, angle, noise_seed, sample_base)
+        return x if displacement is None else elastic_deform(x, displacement, force_torch=self.force_torch)
+
+    def _gather_plain(self, tile, y0, x0, angle, noise_seed, sample_base) -> torch.Tensor:
+        """``gather`` up to and including the rotation"""
         tile, y0, x0, n, cs, seed, std = self._gather_args(tile, y0, x0, angle, noise_seed)
         if self.force_torch:
             g = self.torch_normals(n, seed, int(sample_base)) if std != 0.0 else None
@@ -262,9 +285,11 @@ class PatchSampler:
         return _splitmix64(_splitmix64(self.seed) ^ (int(batch) & _M64))
 
     def sample(self, n: int, generator: Optional[torch.Generator] = None) -> torch.Tensor:
-        """``draw`` then ``gather``; every call takes the next per-batch noise seed."""
+        """``draw`` (then ``draw_displacement`` with ``elastic_deformation``) then ``gather``; every call takes the next
+        per-batch noise seed."""
         tile, y0, x0, angle = self.draw(n, generator)
-        x = self.gather(tile, y0, x0, angle, noise_seed=self.batch_seed(self._batch))
+        displacement = self.draw_displacement(n, generator) if self.elastic_deformation else None
+        x = self.gather(tile, y0, x0, angle, noise_seed=self.batch_seed(self._batch), displacement=displacement)
         self._batch += 1
         return x
 
@@ -288,11 +313,12 @@ _SPLINE_GAIN = math.prod((1.0 - z) * (1.0 - 1.0 / z) for z in _SPLINE_POLES)
 _LDS_PATCH = 128  # the entry point needs a workspace for rotated patches larger than this
 
 
-def _spline_prefilter(c: np.ndarray) -> np.ndarray:
-    """force_torch: the interpolation coefficients along the last axis of float64 ``c``, every line at once"""
-    c = c * _SPLINE_GAIN
+def _spline_prefilter(c: np.ndarray, poles=_SPLINE_POLES, gain=_SPLINE_GAIN) -> np.ndarray:
+    """force_torch: the interpolation coefficients along the last axis of float64 ``c``, every line at once (the quartic
+    spline's poles and gain unless others are given)"""
+    c = c * gain
     n = c.shape[-1]
-    for z in _SPLINE_POLES:
+    for z in poles:
         zn = z ** n
         mirrored = c[..., ::-1]
         acc = c[..., 0] + zn * mirrored[..., 0]
@@ -317,6 +343,103 @@ def _spline_weight(d: np.ndarray) -> np.ndarray:
 def _reflect(idx: np.ndarray, n: int) -> np.ndarray:
     m = np.mod(idx, 2 * n)
     return np.where(m >= n, 2 * n - 1 - m, m)
+
+
+# ---- elastic deformation: a 3 x 3 displacement grid bent into a per-pixel field (contract: include/cae_hip.h) ------------
+# the samples of the cubic B-spline at the three control points: displacement = M coefficient M^T
+_ELASTIC_M = np.array([[2.0 / 3.0, 1.0 / 3.0, 0.0], [1.0 / 6.0, 2.0 / 3.0, 1.0 / 6.0], [0.0, 1.0 / 3.0, 2.0 / 3.0]])
+_CUBIC_POLE, _CUBIC_GAIN = math.sqrt(3.0) - 2.0, 6.0
+
+
+def elastic_coefficients(displacement: np.ndarray) -> np.ndarray:
+    """``coef[k] = M^-1 d[k] M^-T`` of float64 displacement grids ``[n, 2, 3, 3]``, in float64"""
+    inv = np.linalg.inv(_ELASTIC_M)
+    return np.einsum('pa,nkab,qb->nkpq', inv, np.asarray(displacement, dtype=np.float64), inv)
+
+
+def _cubic_weight(d: np.ndarray) -> np.ndarray:
+    d = np.abs(d)
+    return np.where(d < 1.0, 2.0 / 3.0 - d * d + d * d * d / 2.0, np.where(d < 2.0, (2.0 - d) ** 3 / 6.0, 0.0))
+
+
+def _elastic_host(x: np.ndarray, t: Optional[np.ndarray], coef: np.ndarray):
+    """The contract of ``cae_t_elastic_deform`` in float64 numpy: ``x`` ``[n, c, ps, ps]``, ``t`` ``[n, kt, ps, ps]`` or
+    None, ``coef`` the float32 coefficients the kernel would get.  Returns float64 ``x'`` and ``t'`` (or None)."""
+    n, ch, ps, _ = x.shape
+    cf = _spline_prefilter(x.astype(np.float64), (_CUBIC_POLE,), _CUBIC_GAIN)                                  # rows
+    cf = _spline_prefilter(cf.swapaxes(-1, -2).copy(), (_CUBIC_POLE,), _CUBIC_GAIN).swapaxes(-1, -2)         # columns
+    u = 2.0 * np.arange(ps, dtype=np.float64) / (ps - 1) if ps > 1 else np.zeros(1)
+    w = np.stack([_cubic_weight(u), _cubic_weight(u - 1.0) + _cubic_weight(u + 1.0) + _cubic_weight(u - 3.0),
+                  _cubic_weight(u - 2.0)])
+    with np.errstate(invalid='ignore', over='ignore'):
+        field = np.einsum('ai,bj,nkab->nkij', w, w, coef.astype(np.float64))
+    i, j = np.meshgrid(np.arange(ps, dtype=np.float64), np.arange(ps, dtype=np.float64), indexing='ij')
+    x_out = np.zeros((n, ch, ps, ps))
+    t_out = None if t is None else np.empty_like(t)
+    for s in range(n):
+        y = np.fmin(np.fmax(i + field[s, 0], -float(ps)), 2.0 * ps)  # fmax / fmin: a NaN becomes -ps
+        xx = np.fmin(np.fmax(j + field[s, 1], -float(ps)), 2.0 * ps)
+        if t is not None:
+            t_out[s] = t[s][:, _reflect(np.floor(y + 0.5).astype(np.int64), ps), _reflect(np.floor(xx + 0.5).astype(np.int64), ps)]
+        ys, xs = np.floor(y).astype(np.int64) - 1, np.floor(xx).astype(np.int64) - 1
+        for a in range(4):
+            wy, ry = _cubic_weight(y - (ys + a)), _reflect(ys + a, ps)
+            for b in range(4):
+                x_out[s] += wy * _cubic_weight(xx - (xs + b)) * cf[s][:, ry, _reflect(xs + b, ps)]
+    return x_out, t_out
+
+
+def elastic_workspace_bytes(n: int, c: int, ps: int) -> int:
+    """the scratch ``cae_t_elastic_deform`` needs (its contract's formula)"""
+    return int(n) * int(c) * int(ps) * int(ps) * 4 if ps > _LDS_PATCH else 0
+
+
+def elastic_deform(x: torch.Tensor, displacement, t: Optional[torch.Tensor] = None, force_torch: bool = False):
+    """The reference's elastic deformation of a batch on the device (``cae_t_elastic_deform``, contract in
+    include/cae_hip.h): ``x`` fp32 ``[n, c, ps, ps]`` and optionally its masks ``t`` fp32 ``[n, kt, ps, ps]``, bent by the
+    per-pixel field of the displacement grids ``displacement`` ``[n, 2, 3, 3]`` (float64 or float32, host or device; row
+    displacements first).  The image goes through the interpolating cubic B-spline, the mask through its nearest
+    neighbour, edges reflected.  Returns ``x'``, or ``(x', t')`` with ``t``.
+
+    The spline coefficients of the grids are solved for in float64 on the host and rounded once.  There is no CPU
+    fallback: without a HIP device the call raises RuntimeError.  ``force_torch=True`` evaluates the same contract in
+    float64 on the host and uploads it to ``x``'s device: a comparison path that nothing but this flag selects."""
+    if not isinstance(x, torch.Tensor) or x.dim() != 4 or x.dtype != torch.float32 or x.shape[2] != x.shape[3]:
+        raise ValueError('expected an fp32 batch [n, c, ps, ps]')
+    n, c, ps, _ = (int(v) for v in x.shape)
+    if not 1 <= c <= 4 or ps < 1:
+        raise ValueError(f'1 to 4 channels of at least one pixel, got {tuple(x.shape)}')
+    d = torch.as_tensor(displacement)
+    if d.dtype not in (torch.float64, torch.float32) or tuple(d.shape) != (n, 2, 3, 3):
+        raise ValueError(f'the displacement is float64 or float32 [{n}, 2, 3, 3], got {d.dtype} {tuple(d.shape)}')
+    kt = 0
+    if t is not None:
+        if not isinstance(t, torch.Tensor) or t.dim() != 4 or t.dtype != torch.float32:
+            raise ValueError('expected fp32 masks [n, kt, ps, ps]')
+        kt = int(t.shape[1])
+        if (int(t.shape[0]), int(t.shape[2]), int(t.shape[3])) != (n, ps, ps) or not 1 <= kt <= 4 or t.device != x.device:
+            raise ValueError(f'the masks {tuple(t.shape)} on {t.device} do not match the batch {tuple(x.shape)} on {x.device}')
+    coef = elastic_coefficients(d.detach().cpu().to(torch.float64).numpy()).astype(np.float32)
+    if force_torch:
+        xo, to = _elastic_host(x.detach().cpu().numpy(), None if t is None else t.detach().cpu().numpy(), coef)
+        xo = torch.from_numpy(xo.astype(np.float32)).to(x.device)
+        return xo if t is None else (xo, torch.from_numpy(to).to(x.device))
+    _lib.require_gpu()
+    if not x.is_cuda:
+        raise ValueError('expected the batch on the device')
+    x = x.contiguous()
+    t = t.contiguous() if t is not None else None
+    coef_dev = torch.from_numpy(coef).to(x.device)
+    x_out = torch.empty((n, c, ps, ps), dtype=torch.float32, device=x.device)
+    t_out = torch.empty((n, kt, ps, ps), dtype=torch.float32, device=x.device) if t is not None else None
+    ws_bytes = elastic_workspace_bytes(n, c, ps)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device) if ws_bytes else None
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.lib().cae_t_elastic_deform(
+            x.data_ptr(), t.data_ptr() if t is not None else None, coef_dev.data_ptr(), n, c, kt, ps,
+            ws.data_ptr() if ws is not None else None, ws_bytes, x_out.data_ptr(),
+            t_out.data_ptr() if t is not None else None, _lib.stream_ptr()))
+    return x_out if t is None else (x_out, t_out)
 
 
 class WeightsDistances:
@@ -434,18 +557,24 @@ class LabeledPatchSampler(PatchSampler):
     own pipeline lies in ``zarrdataset`` and is not pinned here.  The pool's largest label value (with ``map_labels`` the
     largest channel sum) is checked against ``class_weights`` once at construction -- IndexError -- so no batch reads the
     kernel's flag back.
+
+    ``elastic_deformation`` bends image and labels after the pair's rotation by one field per sample
+    (``RandomElasticDeformationInputTarget(sigma=10)``; ``elastic_deform``): the weight map is then taken on the deformed
+    labels, and the cast to ``target_data_type`` comes last.
     """
 
     def __init__(self, pool, labels, patch_size: int, data_mode: str = 'train', add_noise: bool = False,
                  noise_std: float = 0.001, normalize: bool = False, rotation: bool = False, degrees: float = 30.0,
                  seed: int = 0, force_torch: bool = False, tile_hw=None, batch_size: int = 16,
                  steps_per_epoch: Optional[int] = None, map_labels: bool = False, target_data_type=torch.float32,
-                 class_weights=None, weights_map_sigma=None, weights_map_w=None):
+                 class_weights=None, weights_map_sigma=None, weights_map_w=None, elastic_deformation: bool = False,
+                 elastic_sigma: float = 10.0):
         if target_data_type not in (torch.float32, torch.int64):
             raise ValueError('Convertion to data type {} not supported'.format(target_data_type))
         super().__init__(pool, patch_size, data_mode=data_mode, add_noise=add_noise, noise_std=noise_std, normalize=normalize,
                          rotation=rotation, degrees=degrees, seed=seed, force_torch=force_torch, tile_hw=tile_hw,
-                         batch_size=batch_size, steps_per_epoch=steps_per_epoch)
+                         batch_size=batch_size, steps_per_epoch=steps_per_epoch, elastic_deformation=elastic_deformation,
+                         elastic_sigma=elastic_sigma)
         labels = torch.as_tensor(labels)
         if labels.dim() == 3:
             labels = labels[..., None]
@@ -499,15 +628,22 @@ class LabeledPatchSampler(PatchSampler):
         ps = self.patch_size
         return int(n) * self.C * ps * ps * 4 if rotated and ps > _LDS_PATCH else 0
 
-    def gather(self, tile, y0, x0, angle=None, noise_seed: Optional[int] = None, sample_base: int = 0):
+    def gather(self, tile, y0, x0, angle=None, noise_seed: Optional[int] = None, sample_base: int = 0, displacement=None):
         """``(x, t)`` of the given draw on the device: ``x`` fp32 ``[n, C, ps, ps]``, ``t`` ``[n, Kt, ps, ps]`` in
-        ``target_data_type``.  The arguments are those of ``PatchSampler.gather``; one ``angle`` turns image and mask."""
+        ``target_data_type``.  The arguments are those of ``PatchSampler.gather``; one ``angle`` turns image and mask, and
+        one ``displacement`` grid per sample bends both."""
+        x, t = self._gather_pair(tile, y0, x0, angle, noise_seed, sample_base)
+        if displacement is not None:
+            x, t = elastic_deform(x, displacement, t, force_torch=self.force_torch)
+        return x, self._target(t)
+
+    def _gather_pair(self, tile, y0, x0, angle, noise_seed, sample_base):
+        """``gather`` up to and including the rotation: ``x`` and the fp32 labels"""
         tile, y0, x0, n, cs, seed, std = self._gather_args(tile, y0, x0, angle, noise_seed)
         ps = self.patch_size
         if self.force_torch:
             g = self.torch_normals(n, seed, int(sample_base)) if std != 0.0 else None
-            x, t = self._gather_host(tile, y0, x0, cs, std, g)
-            return x, self._target(t)
+            return self._gather_host(tile, y0, x0, cs, std, g)
         pool, tile_hw = self._device_pool()
         if self._labels_dev is None:
             self._labels_dev = self.labels.to(pool.device)
@@ -525,7 +661,7 @@ class LabeledPatchSampler(PatchSampler):
                 cs_dev[1].data_ptr() if cs is not None else None, seed, int(sample_base) & 0xFFFFFFFF, std,
                 int(self.normalize), int(self.map_labels), n, ps, ws.data_ptr() if ws is not None else None, ws_bytes,
                 x.data_ptr(), t.data_ptr(), _lib.stream_ptr()))
-        return x, self._target(t)
+        return x, t
 
     def _target(self, t: torch.Tensor) -> torch.Tensor:
         """the fp32 labels ``[n, Kt, ps, ps]`` as the sampler hands them out: cast, or with their weight map in front"""
@@ -568,9 +704,11 @@ class LabeledPatchSampler(PatchSampler):
         return torch.from_numpy(x_out.astype(np.float32)).to(dev), torch.from_numpy(t_out).to(dev)
 
     def sample(self, n: int, generator: Optional[torch.Generator] = None):
-        """``draw`` then ``gather`` -> ``(x, t)``; every call takes the next per-batch noise seed."""
+        """``draw`` (then ``draw_displacement`` with ``elastic_deformation``) then ``gather`` -> ``(x, t)``; every call
+        takes the next per-batch noise seed."""
         tile, y0, x0, angle = self.draw(n, generator)
-        pair = self.gather(tile, y0, x0, angle, noise_seed=self.batch_seed(self._batch))
+        displacement = self.draw_displacement(n, generator) if self.elastic_deformation else None
+        pair = self.gather(tile, y0, x0, angle, noise_seed=self.batch_seed(self._batch), displacement=displacement)
         self._batch += 1
         return pair
 

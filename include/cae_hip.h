@@ -534,6 +534,67 @@ int cae_t_sample_labeled_patches(const uint8_t *pool_dev, const uint8_t *labels_
                                  int ps, void *workspace_dev, size_t workspace_bytes, float *x_dev, float *t_dev,
                                  void *stream);
 
+/* ---- training input: elastic deformation of image and mask patches (csrc/cae_elastic.hip) ---------------------------------
+ * Stands where RandomElasticDeformationInput / RandomElasticDeformationInputTarget(sigma) of utils/datasets/_augs.py:26-49,
+ * 85-99 stand (get_zarr_transform with elastic_deformation=True): a 3 x 3 grid of random displacements is interpolated to a
+ * per-pixel field; the image is resampled through the cubic B-spline, the mask by its nearest neighbour, edges reflected.
+ * The contract below is the form of that operation that scipy.ndimage expresses (map_coordinates(order=3, mode='mirror')
+ * for the field, spline_filter + map_coordinates(order=3 / 0, mode='reflect') for the planes); parity with the
+ * `elasticdeform` package itself is not pinned.  The call works on a batch that already lies in device memory, after
+ * either sampler entry point above or on any tensor the caller brings.
+ *
+ * Inputs.
+ *   x_in, x_out     float [n][c][ps][ps], 1 <= c <= 4.
+ *   t_in, t_out     float [n][kt][ps][ps], 0 <= kt <= 4; both NULL with kt == 0 (the image-only transform).
+ *   coef_dev        float [n][2][3][3] on the device: the spline coefficients of each sample's displacement grid (below).
+ *   workspace_dev, workspace_bytes   device scratch of at least cae_t_elastic_deform_workspace(n, c, ps) =
+ *                       ps > 128 ? n * c * ps * ps * sizeof(float) : 0
+ *                   bytes (NULL / 0 where that is 0).  What it holds before the call does not matter.
+ *
+ * Displacement field.  The caller draws d[k][a][b], k = 0 for rows and 1 for columns, a, b = 0..2, as N(0, sigma^2) in
+ * float64 (np.random.randn(2, 3, 3) * sigma).  Control point (a, b) sits at pixel (a (ps - 1) / 2, b (ps - 1) / 2).  The field
+ * is the interpolating cubic B-spline through the nine values with whole-sample mirror extension of the grid
+ * (... 2 1 | 0 1 2 | 1 0 ...).  The caller solves for its coefficients in float64 and rounds once to float32 (as cos / sin
+ * are handled above): with M = [[2/3, 1/3, 0], [1/6, 2/3, 1/6], [0, 1/3, 2/3]],
+ *     coef[k] = M^-1 d[k] M^-T.
+ * With the cubic B-spline
+ *     beta(r) = 2/3 - r^2 + |r|^3 / 2   |r| < 1
+ *               (2 - |r|)^3 / 6         |r| < 2,  else 0,
+ * the grid coordinate u_i = 2 i / (ps - 1) of row or column i (0 with ps == 1) and the folded weights
+ *     W_0(u) = beta(u),   W_1(u) = beta(u - 1) + beta(u + 1) + beta(u - 3),   W_2(u) = beta(u - 2),
+ * the kernels evaluate
+ *     D_k(i, j) = sum over a, b = 0..2 of W_a(u_i) W_b(u_j) coef[k][a][b],
+ * which equals scipy.ndimage.map_coordinates(d[k], [u_i, u_j], order=3, mode='mirror').
+ * Source point.  Output pixel (i, j) (row, column) reads y = i + D_0(i, j), x = j + D_1(i, j), both clamped to [-ps, 2 ps]
+ * before any integer cast (a NaN becomes -ps).  Every row or column index q that follows is reflected half-sample
+ * symmetrically, as often as needed: refl(q) of the labelled contract above.
+ *   Mask.   t_out = t_in[refl(floor(y + 0.5))][refl(floor(x + 0.5))] per channel, an exact copy of a value.
+ *   Image.  x_out = sum over a, b = 0..3 of beta(y - (ys + a)) beta(x - (xs + b)) cf[refl(ys + a)][refl(xs + b)], with
+ *           ys = floor(y) - 1 and xs = floor(x) - 1.  There is no clipping afterwards.
+ *   cf.     The cubic interpolation coefficients of each plane of x_in: every row is filtered, then every column.  A line
+ *           c[0..n-1] (n = ps) is scaled by 6 = (1 - z)(1 - 1 / z) and run through the recursion of the labelled contract
+ *           above with the single pole z = sqrt(3) - 2:
+ *               c[0]   = c0 + z / (1 - z^(2n)) * (c0 + z^n c[n-1] + sum_{i=1..n-1} z^i (c[i] + z^n c[n-1-i])),  c0 = c[0]
+ *               c[i]  += z c[i-1]                 i = 1 .. n-1
+ *               c[n-1] *= z / (z - 1)
+ *               c[i]   = z (c[i+1] - c[i])        i = n-2 .. 0.
+ *           This start is the exact one for the reflected line.  scipy's spline_filter1d(order=3, mode='reflect') parts
+ *           from it by up to 6e-4 at n = 2, 1e-6 at 5 and 4e-10 at 8 (lines in [-1, 1]) and equals it to rounding from n = 16; the contract is the
+ *           exact form.  The filter's l1 gain per axis is 3.  The kernels work in float32 and drop terms of the start that
+ *           are below float32 resolution (z^i from i = 22, z^n from n = 64).
+ * Zero displacement.  t_out == t_in exactly and x_out == x_in up to rounding, for every ps >= 1.
+ * Results are bitwise repeatable and independent of the launch shape and of what x_out, t_out and the workspace held.
+ *
+ * CAE_ERR_ARG before any launch, with a message in cae_last_error: c outside 1..4, kt outside 0..4, ps outside 1..16384,
+ * n < 0, a NULL x_in, x_out or coef_dev, kt > 0 with a NULL t_in or t_out, kt == 0 with a non-NULL t_in or t_out, an output
+ * that is also an input, a workspace that is NULL or smaller than the query where that size is not 0 (the message names
+ * the bytes), more than 2^31 - 1 blocks.  n == 0 returns CAE_OK with nothing launched.  No device-side value faults:
+ * coefficients that are NaN or huge only move clamped coordinates.  The workspace query returns 0 for arguments the call
+ * refuses. */
+int cae_t_elastic_deform(const float *x_in, const float *t_in, const float *coef_dev, int n, int c, int kt, int ps,
+                         void *workspace_dev, size_t workspace_bytes, float *x_out, float *t_out, void *stream);
+size_t cae_t_elastic_deform_workspace(int n, int c, int ps);
+
 /* compressai NonNegativeParametrizer (GDN beta / gamma; layers/gdn.py via _autoencoders.py GDN units) under autograd:
  * out = max(x, bound)^2 - pedestal;  g_x = g 2 max(x, bound) where x >= bound or that value is negative (LowerBound rule). */
 int cae_t_reparam_forward(const float *x, long n, float bound, float pedestal, float *out, void *stream);
