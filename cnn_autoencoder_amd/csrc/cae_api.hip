@@ -154,7 +154,14 @@ static int upload_channels(DevBuf &d, const float *v, int c, int ct, float fill)
         d.reset();
         return CAE_OK;
     }
-    return d.upload(pad_channels(v, c, ct, fill));
+    // The kernels read these vectors as 16-byte pieces, whole channel tiles at a time (load_acc_tile, cae_kernels.hpp):
+    // the host vector `v` may lie anywhere, its padded copy is an allocation of its own -- ct * 32 floats at an address
+    // hipMalloc aligns to 256 bytes.  Checked, not assumed: a buffer that broke this would fault in the kernel.
+    CAE_TRY(d.upload(pad_channels(v, c, ct, fill)));
+    if ((uintptr_t)d.p % 16 != 0 || d.bytes != (size_t)ct * 32 * sizeof(float))
+        return fail(CAE_ERR_HIP, "per-channel vector: device buffer %p (%zu bytes) is not a 16-byte aligned run of %d floats",
+                    d.p, d.bytes, ct * 32);
+    return CAE_OK;
 }
 
 // What every launch site fills the same way; the site adds its weights and whatever else is special about it.  (Tile

@@ -99,12 +99,30 @@ __device__ __forceinline__ void wait_vm0() { asm volatile("s_waitcnt vmcnt(0)" :
 // row of a 32x32 accumulator register: row = (r&3) + 8*(r>>2) + 4*h
 __device__ __forceinline__ constexpr int acc_row(int r) { return (r & 3) + 8 * (r >> 2); }
 
+// Channel tile ct of a per-channel vector (bias, beta) in accumulator order.  Registers 4g .. 4g+3 are the rows
+// 8g + 4h .. 8g + 4h + 3: four aligned groups of four consecutive floats, so a tile is four 16-byte loads (from HBM or
+// from LDS) instead of sixteen 4-byte ones.  `vec` is 16-byte aligned and CT*32 floats long: every such vector is an
+// allocation of its own, padded to whole channel tiles (upload_channels, cae_api.hip; LDS copies start 16-byte aligned).
+__device__ __forceinline__ void load_acc_tile(f32x16 &a, const float *vec, int ct, int h) {
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+        const f32x4 v = *(const f32x4 *)(vec + 32 * ct + 8 * g + 4 * h);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) a[4 * g + k] = v[k];
+    }
+}
+
 template <int CT>
 __device__ __forceinline__ void init_acc(f32x16 (&acc)[CT], const float *vec, int h, float fill) {
 #pragma unroll
-    for (int ct = 0; ct < CT; ++ct)
+    for (int ct = 0; ct < CT; ++ct) {
+        if (vec) {  // (uniform)
+            load_acc_tile(acc[ct], vec, ct, h);
+        } else {
 #pragma unroll
-        for (int r = 0; r < 16; ++r) acc[ct][r] = vec ? vec[32 * ct + acc_row(r) + 4 * h] : fill;
+            for (int r = 0; r < 16; ++r) acc[ct][r] = fill;
+        }
+    }
 }
 
 // ---- fused GDN / IGDN on the accumulators ---------------------------------------------------

@@ -470,8 +470,9 @@ __global__ void __launch_bounds__(CONV_F16_NW * 64, 1) conv_s2_f16_kernel(const 
 }
 
 // GDN / IGDN with the whole packed gamma resident in LDS (no staging, no barriers): persistent kernels.
+// beta: CT*32 floats, 16-byte aligned, in LDS -- or in HBM where a kernel has no room for them (deconv_s2_f16).
 template <int CT, bool INVERSE>
-__device__ __forceinline__ void gdn_resident_f16(f32x16 (&y)[CT], const char *gbuf, const float *beta_lds, int lane) {
+__device__ __forceinline__ void gdn_resident_f16(f32x16 (&y)[CT], const char *gbuf, const float *beta, int lane) {
     const int h = lane >> 5;
     f32x16 nrm[CT];
     float mx = 0.0f;
@@ -483,9 +484,11 @@ __device__ __forceinline__ void gdn_resident_f16(f32x16 (&y)[CT], const char *gb
     float isc;
     const float sc = pixel_scale(mx, &isc), sc2 = sc * sc;
 #pragma unroll
-    for (int ct = 0; ct < CT; ++ct)
+    for (int ct = 0; ct < CT; ++ct) {
+        load_acc_tile(nrm[ct], beta, ct, h);
 #pragma unroll
-        for (int r = 0; r < 16; ++r) nrm[ct][r] = beta_lds[32 * ct + acc_row(r) + 4 * h] * sc2;
+        for (int r = 0; r < 16; ++r) nrm[ct][r] *= sc2;
+    }
 #pragma unroll
     for (int jt = 0; jt < CT; ++jt) {
         const char *gb = gbuf + jt * (CT * 4096) + lane * 16;
@@ -671,9 +674,11 @@ __global__ void __launch_bounds__(256, 1) gdn_f16_kernel(const LayerArgs p) {
         for (int half = 0; half < 2; ++half) {
             f32x16 nrm[CH];
 #pragma unroll
-            for (int c = 0; c < CH; ++c)
+            for (int c = 0; c < CH; ++c) {
+                load_acc_tile(nrm[c], beta_lds, half * CH + c, h);
 #pragma unroll
-                for (int r = 0; r < 16; ++r) nrm[c][r] = beta_lds[32 * (half * CH + c) + acc_row(r) + 4 * h] * sc2;
+                for (int r = 0; r < 16; ++r) nrm[c][r] *= sc2;
+            }
 #pragma unroll
             for (int jt = 0; jt < CT; ++jt) {
                 const char *gb = gbuf + jt * (CT * 4096) + lane * 16;
@@ -910,19 +915,20 @@ __host__ __device__ __forceinline__ size_t pmap_record(int n, int OH, int OW, in
 // layout gives every lane four scattered 16-byte pieces of its pixel's record; written like that (16 bytes per lane at a
 // 128-byte stride) the store cost 0.25 ms of deconv3's 3.07 (timed without it).  So the tile is transposed through
 // LDS (XOR-swizzled pieces: conflict-free both ways) and leaves as four instructions of 1 KiB contiguous each.
-template <int CT>
+// pm_lds: the block's LDS copy of the first LDS_JT 4-KiB pieces of p.pm (the others are read from HBM).
+template <int CT, int LDS_JT>
 __device__ __forceinline__ void store_pmap_f16(const f32x16 (&y)[CT], const LayerArgs &p, char *tbuf, int n, int oy, int par,
-                                               int j0, int lane, bool row_valid) {
+                                               int j0, int lane, bool row_valid, const char *pm_lds) {
     const int h = lane >> 5, m = lane & 31;
     f32x16 pm;
 #pragma unroll
     for (int r = 0; r < 16; ++r) pm[r] = 0.0f;
     float mx = 0.0f;
-    const char *ab = (const char *)p.pm + lane * 16;
 #pragma unroll
     for (int jt = 0; jt < CT; ++jt)
 #pragma unroll
         for (int s = 0; s < 2; ++s) {
+            const char *ab = (jt < LDS_JT ? pm_lds : (const char *)p.pm) + lane * 16;
             u32x4v hw, lw;
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
@@ -946,13 +952,16 @@ __device__ __forceinline__ void store_pmap_f16(const f32x16 (&y)[CT], const Laye
         *(f32x4 *)(tbuf + m * 128 + (((2 * g + h) ^ (m & 7)) * 16)) = v;
     }
     __builtin_amdgcn_wave_barrier();
-    const int half_w = p.OW >> 1;
-    float *row = (float *)p.out + ((((size_t)n * p.OH + oy) * 2 + par) * half_w) * 32;
+    // The wave's 32 records are contiguous and n, oy, par, j0 are the same in all its lanes (the block's tile, the wave's
+    // row): one wave-uniform 64-bit base, lane l's piece (px, q) = (l >> 3, l & 7) of each store 16 l bytes into it, the
+    // four stores 1 KiB apart -- no 64-bit address arithmetic per store.
+    const int half_w = p.OW >> 1, j0u = __builtin_amdgcn_readfirstlane(j0);
+    float *rec0 = (float *)p.out + ((((size_t)n * p.OH + oy) * 2 + par) * half_w + j0u) * 32 + 4 * lane;
 #pragma unroll
     for (int it = 0; it < 4; ++it) {
         const int px = (lane >> 3) + 8 * it, q = lane & 7;
         const f32x4 v = *(const f32x4 *)(tbuf + px * 128 + ((q ^ (px & 7)) * 16));
-        if (row_valid && j0 + px < half_w) *(f32x4 *)(row + (size_t)(j0 + px) * 32 + 4 * q) = v;
+        if (row_valid && j0u + px < half_w) *(f32x4 *)(rec0 + it * 256) = v;
     }
     __builtin_amdgcn_wave_barrier();
 }
@@ -1093,14 +1102,30 @@ struct DeconvGeomF16 {
     // the streamed form re-fetched gamma for every (px, row) tile -- 8 passes per block, each of CT stages with a barrier,
     // a vmcnt wait and only 24 MFMAs per wave to hide them behind.
     static constexpr int G_ALL = IGDN ? CT * CT * 4096 : 0;
+    // Bias and beta, [bias CT*32][beta CT*32] floats, staged once per block behind the stage buffers and the resident
+    // gamma: every wave reads the bias twice (once per output-row parity) and beta once per (px, row) tile.  An
+    // instance whose LDS has no room for them reads them from HBM (both ways in 16-byte pieces, load_acc_tile).
+    static constexpr int VEC_BYTES = 2 * CT * 128;
     static constexpr bool RESIDENT = IGDN && 2 * STAGE_BYTES + G_ALL <= 160 * 1024;
+    static constexpr int G_LDS = RESIDENT ? G_ALL : 0;
     static constexpr int PMAP_LDS = NW * 4096;  // OUT_PMAP: one 4-KiB transpose buffer per wave
     // ... which live behind everything else, or -- when that exceeds the LDS -- in the stage buffer the K loop has
     // just finished with (one block barrier before the epilogue)
-    static constexpr bool TBUF_IN_STAGE = RESIDENT && 2 * STAGE_BYTES + G_ALL + PMAP_LDS > 160 * 1024;
+    static constexpr bool TBUF_IN_STAGE = RESIDENT && 2 * STAGE_BYTES + G_LDS + PMAP_LDS > 160 * 1024;
     static_assert(!TBUF_IN_STAGE || STAGE_BYTES >= PMAP_LDS, "transpose buffers must fit a stage buffer");
+    // (the vectors never take the room of transpose buffers that fitted behind everything else without them)
+    static constexpr bool VEC_IN_LDS = 2 * STAGE_BYTES + G_LDS + VEC_BYTES + (TBUF_IN_STAGE ? 0 : PMAP_LDS) <= 160 * 1024;
+    static constexpr int VEC_LDS = VEC_IN_LDS ? VEC_BYTES : 0;
+    static constexpr int TBUF_LDS = TBUF_IN_STAGE ? 0 : PMAP_LDS;
+    // OUT_PMAP: the packed last-layer weights are CT pieces of 4 KiB (one per 32 channels of this layer).  Every wave
+    // reads all of them for each of its 4 (px, row) tiles: from HBM that was 64 KiB per wave and block, a third of the
+    // kernel's vector-memory traffic.  As many pieces as the LDS still has room for (3 of the 4 of the canonical
+    // 128-channel instance) are staged once per block behind everything else; the rest is read from HBM as before.
+    static constexpr int PM_ROOM = (160 * 1024 - (2 * STAGE_BYTES + G_LDS + VEC_LDS + TBUF_LDS)) / 4096;
+    static constexpr int PM_LDS_JT = PM_ROOM < 0 ? 0 : (PM_ROOM < CT ? PM_ROOM : CT);
+    static constexpr int PM_OFF = 2 * STAGE_BYTES + G_LDS + VEC_LDS + TBUF_LDS;
     static constexpr int lds_bytes(bool pmap) {
-        return 2 * STAGE_BYTES + (RESIDENT ? G_ALL : 0) + ((pmap && !TBUF_IN_STAGE) ? PMAP_LDS : 0);
+        return 2 * STAGE_BYTES + G_LDS + VEC_LDS + (pmap ? TBUF_LDS + PM_LDS_JT * 4096 : 0);
     }
     static constexpr int dmin(int py) { return -((py + P) / 2); }
     static constexpr int nky(int py) { return (KS - 1 - py - P) / 2 - dmin(py) + 1; }
@@ -1153,11 +1178,15 @@ __device__ __forceinline__ void deconv_phase_f16(const LayerArgs &p, const char 
     constexpr int STAGE_BYTES = G::STAGE_BYTES;
     const int h = lane >> 5;
     const int NS = p.cci * G::nky(PY);
+    // bias and beta: the block's LDS copy (staged by the kernel before the first phase; no bias = zeros), or HBM
+    const float *vec_lds = (const float *)(smem + 2 * STAGE_BYTES + G::G_LDS);
+    const float *bias = G::VEC_IN_LDS ? vec_lds : p.bias;
+    [[maybe_unused]] const float *beta = G::VEC_IN_LDS ? vec_lds + CT * 32 : p.beta;  // (resident IGDN)
     f32x16 acc[2][PT][CT];  // [px][row tile][ct]
 #pragma unroll
     for (int x = 0; x < 2; ++x)
 #pragma unroll
-        for (int pt = 0; pt < PT; ++pt) init_acc<CT>(acc[x][pt], p.bias, h, 0.0f);
+        for (int pt = 0; pt < PT; ++pt) init_acc<CT>(acc[x][pt], bias, h, 0.0f);
 
     for (int s = 0; s < NS; ++s) {
         wait_vm0();
@@ -1204,7 +1233,7 @@ __device__ __forceinline__ void deconv_phase_f16(const LayerArgs &p, const char 
     }
 
     // transpose buffer of this wave for the product-map store
-    char *tbuf = smem + 2 * STAGE_BYTES + (G::RESIDENT ? G::G_ALL : 0) + wave * 4096;
+    char *tbuf = smem + 2 * STAGE_BYTES + G::G_LDS + G::VEC_LDS + wave * 4096;
     if constexpr (G::TBUF_IN_STAGE) {
         __syncthreads();  // every wave is done with the last stage's buffer (sc was incremented past it)
         tbuf = smem + ((sc + 1) & 1) * STAGE_BYTES + wave * 4096;
@@ -1212,7 +1241,8 @@ __device__ __forceinline__ void deconv_phase_f16(const LayerArgs &p, const char 
     auto store = [&](auto x_tag, auto pt_tag) {
         constexpr int x = decltype(x_tag)::value, pt = decltype(pt_tag)::value;
         if (p.outfmt == OUT_PMAP)
-            store_pmap_f16<CT>(acc[x][pt], p, tbuf, n, 2 * (iy + pt) + PY, x, ix - (lane & 31), lane, (iy + pt) < p.H);
+            store_pmap_f16<CT, G::PM_LDS_JT>(acc[x][pt], p, tbuf, n, 2 * (iy + pt) + PY, x, ix - (lane & 31), lane,
+                                             (iy + pt) < p.H, smem + G::PM_OFF);
         else
             store_tiles_f16<CT, true, !IGDN && CT <= 4>(acc[x][pt], p, n, 2 * (iy + pt) + PY, 2 * ix + x, h, (iy + pt) < p.H && ix < p.W);
     };
@@ -1222,7 +1252,7 @@ __device__ __forceinline__ void deconv_phase_f16(const LayerArgs &p, const char 
         static_for<2 * PT>([&](auto it) {
             constexpr int idx = decltype(it)::value;
             constexpr int x = idx / PT, pt = idx % PT;
-            gdn_resident_f16<CT, true>(acc[x][pt], gbuf, p.beta, lane);
+            gdn_resident_f16<CT, true>(acc[x][pt], gbuf, beta, lane);
             store(std::integral_constant<int, x>{}, std::integral_constant<int, pt>{});
         });
     } else if constexpr (IGDN) {
@@ -1304,7 +1334,19 @@ __global__ void __launch_bounds__(NW * 64, NW * PT <= 4 ? 2 : 1) deconv_s2_f16_k
         for (int j = wave; j < G::G_ALL / 1024; j += NW)
             glds16((const char *)p.gp + (size_t)j * 1024 + lane * 16, smem + 2 * G::STAGE_BYTES + j * 1024);
     }
+    if (G::PM_LDS_JT > 0 && p.outfmt == OUT_PMAP) {  // (the LDS of a launch without the product map ends before them)
+        for (int j = wave; j < G::PM_LDS_JT * 4; j += NW)
+            glds16((const char *)p.pm + (size_t)j * 1024 + lane * 16, smem + G::PM_OFF + j * 1024);
+    }
     deconv_issue_f16<KS, CT, NW, PT, IGDN, 0>(p, in_n, plane_bytes, 0, smem, hrow, hbase, wave, lane);
+    if constexpr (G::VEC_IN_LDS) {  // bias | beta, once per block; the barrier: the first phase reads the bias at once
+        float *vec_lds = (float *)(smem + 2 * G::STAGE_BYTES + G::G_LDS);
+        for (int i = threadIdx.x; i < CT * 32; i += NW * 64) {
+            vec_lds[i] = p.bias ? p.bias[i] : 0.0f;
+            vec_lds[CT * 32 + i] = (IGDN && p.beta) ? p.beta[i] : 1.0f;
+        }
+        __syncthreads();
+    }
     deconv_phase_f16<KS, CT, NW, PT, IGDN, 0>(p, in_n, plane_bytes, smem, sc, hrow, hbase, wave, lane, b_off, stray_mask, n,
                                               iy, ix);
     deconv_phase_f16<KS, CT, NW, PT, IGDN, 1>(p, in_n, plane_bytes, smem, sc, hrow, hbase, wave, lane, b_off, stray_mask, n,
