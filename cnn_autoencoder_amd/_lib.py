@@ -189,6 +189,18 @@ SYMBOLS = {
     'cae_seg_object_distances_workspace': (c_size_t, [c_int, c_int, c_int]),
     'cae_seg_weight_map': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_float, c_float, c_int, c_size_t,
                                    c_void_p, c_void_p, c_void_p]),
+    'cae_mask_gray': (c_int, [c_void_p, c_int, c_size_t, c_void_p, c_void_p, c_void_p]),
+    'cae_mask_hist': (c_int, [c_void_p, c_void_p, c_int, c_size_t, c_void_p, c_void_p, c_size_t, c_void_p]),
+    'cae_mask_hist_workspace': (c_size_t, [c_int, c_size_t]),
+    'cae_mask_hist_fold': (c_size_t, []),
+    'cae_mask_threshold': (c_int, [c_void_p, c_void_p, c_int, c_size_t, c_void_p, c_void_p]),
+    'cae_mask_label': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    'cae_mask_label_workspace': (c_size_t, [c_int, c_int, c_int]),
+    'cae_mask_area_filter': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t,
+                                     c_void_p]),
+    'cae_mask_area_workspace': (c_size_t, [c_int, c_int, c_int]),
+    'cae_mask_within': (c_int, [c_void_p, c_int, c_size_t, c_int, c_void_p, c_void_p]),
+    'cae_mask_downscale': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_size_t, c_size_t, c_int, c_void_p, c_void_p]),
     'cae_seg_set_weights': (c_int, [c_void_p, c_void_p, c_int, c_void_p]),
     'cae_seg_pack_dev': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p]),
     'cae_seg_conv2d_workspace': (c_size_t, [c_int] * 6),

@@ -47,6 +47,15 @@ int launch_seg_record(const unsigned long long *partial, int n, int bx, int c, l
 template <typename W>
 int launch_seg_histsum(const W *partial, int n, int bx, int per_image, int bits, long long *hist, hipStream_t st);
 
+// the labelling of cae_seg_components (cae_seg_objects.hip) for any connectivity (4 or 8) and reading of the plane:
+// foreground is any non-zero value (kAny), neighbours join only with equal values (kByValue), or foreground is where
+// the plane is 0 (kZero).  The caller has checked shapes and pointers; workspace: components_workspace bytes, 8-byte
+// aligned; n_objects may be NULL.  Labels: 0, or 1 + the smallest row-major index of the object
+enum { kAny = 0, kByValue = 1, kZero = 2 };
+size_t components_workspace(int n, int h, int w);
+int launch_components(const uint8_t *target, const int32_t *extent, int n, int h, int w, int mode, int connectivity,
+                      int32_t *labels, long long *n_objects, void *workspace, hipStream_t st);
+
 // ---- device steps ------------------------------------------------------------------------------------------------
 // the counted part of image n: (rows, cols), clamped to the plane
 __device__ __forceinline__ void extent_of(const int32_t *extent, int n, int h, int w, int &rows, int &cols) {

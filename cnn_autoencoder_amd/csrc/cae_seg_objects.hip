@@ -8,6 +8,9 @@
 // (2) unions along the wave seams and with the row above, only where a neighbour in the same run does not make the same
 // union; (3) every pixel walks to its root, which is the smallest index of its component whatever the order of the
 // unions, and writes 1 + root; roots are counted per block; (4) the block counts are summed.  No lane waits for another.
+// The same launches label for the tissue mask (cae_mask.hip, through launch_components): step (2) is one body with the
+// connectivity as a template parameter -- 8 here, 4 (no unions across corners) in mask_merge4_kernel -- and the plane
+// can be read as "zero is foreground", which labels the complement.
 //
 // cae_seg_object_cover: box limits in integer min / max arrays addressed by the root pixel (the root's row is the top
 // row), one +-1 per box corner into a difference plane, row and column prefix sums.  All sums are integer: exact in any
@@ -79,14 +82,15 @@ struct CompArgs {
     int *labels;
     unsigned long long *partial;  // [n][bx] roots per block
     Plane p;
-    int by_value;
+    int by_value;  // kAny, kByValue or kZero
 };
 
-// value of (y, x) of a plane as the labelling sees it: 0 outside plane or extent; 1 for any foreground unless by_value
+// value of (y, x) of a plane as the labelling sees it: 0 outside plane or extent; else 1 for any foreground (kAny), the
+// pixel's value (kByValue), or 1 where the plane is 0 (kZero: the objects of the complement)
 __device__ __forceinline__ int seen(const uint8_t *tg, int w, int rows, int cols, int by_value, int y, int x) {
     if (y < 0 || x < 0 || y >= rows || x >= cols) return 0;
     const int t = tg[(size_t)y * w + x];
-    return by_value ? t : (t != 0);
+    return by_value == kByValue ? t : ((t != 0) != (by_value == kZero));
 }
 
 __global__ __launch_bounds__(kThreads) void obj_init_kernel(CompArgs a) {
@@ -112,7 +116,9 @@ __global__ __launch_bounds__(kThreads) void obj_init_kernel(CompArgs a) {
     a.labels[(size_t)n * hw + (size_t)y * w + x] = entry;
 }
 
-__global__ __launch_bounds__(kThreads) void obj_merge_kernel(CompArgs a) {
+// CONN: 8 joins pixels that touch by an edge or a corner, 4 by an edge only
+template <int CONN>
+__device__ __forceinline__ void merge_step(const CompArgs &a) {
     int n, y, x, rows, cols;
     place(a.p, n, y, x);
     const int h = a.p.h, w = a.p.w;
@@ -132,13 +138,16 @@ __global__ __launch_bounds__(kThreads) void obj_merge_kernel(CompArgs a) {
     if (up) {
         // with left and upper-left in the component, the left pixel joins the two rows
         if (!(left && ul)) unite(L, i, i - w);
-    } else {
+    } else if constexpr (CONN == 8) {
         // the left pixel has the upper-left one straight above it, the right pixel the upper-right one
         if (ul && !left) unite(L, i, i - w - 1);
         const bool ur = seen(tg, w, rows, cols, a.by_value, y - 1, x + 1) == v;
         if (ur && seen(tg, w, rows, cols, a.by_value, y, x + 1) != v) unite(L, i, i - w + 1);
     }
 }
+
+__global__ __launch_bounds__(kThreads) void obj_merge_kernel(CompArgs a) { merge_step<8>(a); }
+__global__ __launch_bounds__(kThreads) void mask_merge4_kernel(CompArgs a) { merge_step<4>(a); }
 
 __global__ __launch_bounds__(kThreads) void obj_flatten_kernel(CompArgs a) {
     int n, y, x;
@@ -398,15 +407,41 @@ int hist_blocks(int n, int h, int w, int bits) {
 }
 
 }  // namespace
-}  // namespace cae
 
-using namespace cae;
-
-extern "C" size_t cae_seg_components_workspace(int n, int h, int w) {
+size_t components_workspace(int n, int h, int w) {
     Plane p;
     if (!plane_ok(n, h, w) || !plane_of(n, h, w, p)) return 0;
     return (size_t)n * p.bx * sizeof(unsigned long long);
 }
+
+int launch_components(const uint8_t *target, const int32_t *extent, int n, int h, int w, int mode, int connectivity,
+                      int32_t *labels, long long *n_objects, void *workspace, hipStream_t st) {
+    CompArgs a;
+    if (!plane_of(n, h, w, a.p)) return fail(CAE_ERR_ARG, "%d planes of %d x %d are too many for one call", n, h, w);
+    a.target = target, a.extent = extent, a.labels = labels, a.by_value = mode;
+    a.partial = static_cast<unsigned long long *>(workspace);
+    const dim3 grid((unsigned)((size_t)n * a.p.bx)), block(kThreads);
+    hipLaunchKernelGGL(obj_init_kernel, grid, block, 0, st, a);
+    HIP_TRY(hipGetLastError());
+    if (connectivity == 8)
+        hipLaunchKernelGGL(obj_merge_kernel, grid, block, 0, st, a);
+    else
+        hipLaunchKernelGGL(mask_merge4_kernel, grid, block, 0, st, a);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(obj_flatten_kernel, grid, block, 0, st, a);
+    HIP_TRY(hipGetLastError());
+    if (n_objects) {
+        hipLaunchKernelGGL(obj_total_kernel, dim3(n), dim3(64), 0, st, a.partial, a.p.bx, n_objects);
+        HIP_TRY(hipGetLastError());
+    }
+    return CAE_OK;
+}
+
+}  // namespace cae
+
+using namespace cae;
+
+extern "C" size_t cae_seg_components_workspace(int n, int h, int w) { return components_workspace(n, h, w); }
 
 extern "C" int cae_seg_components(const uint8_t *target, const int32_t *extent, int n, int h, int w, int by_value,
                                   int32_t *labels, int64_t *n_objects, void *workspace, size_t workspace_bytes,
@@ -418,24 +453,13 @@ extern "C" int cae_seg_components(const uint8_t *target, const int32_t *extent, 
     if (!target || !labels || !n_objects) return fail(CAE_ERR_ARG, "cae_seg_components: NULL target, labels or n_objects");
     if (misaligned(labels, 3) || misaligned(n_objects, 7) || (extent && misaligned(extent, 3)))
         return fail(CAE_ERR_ARG, "cae_seg_components: labels / extent not 4-byte or n_objects not 8-byte aligned");
-    CompArgs a;
-    if (!plane_of(n, h, w, a.p)) return fail(CAE_ERR_ARG, "cae_seg_components: %d planes of %d x %d are too many for one call", n, h, w);
+    Plane p;
+    if (!plane_of(n, h, w, p)) return fail(CAE_ERR_ARG, "cae_seg_components: %d planes of %d x %d are too many for one call", n, h, w);
     const size_t need = cae_seg_components_workspace(n, h, w);
     if (!workspace || workspace_bytes < need || misaligned(workspace, 7))
         return fail(CAE_ERR_ARG, "cae_seg_components: workspace NULL, not 8-byte aligned or too small: %zu bytes needed", need);
-    a.target = target, a.extent = extent, a.labels = labels, a.by_value = by_value != 0;
-    a.partial = static_cast<unsigned long long *>(workspace);
-    hipStream_t st = (hipStream_t)stream;
-    const dim3 grid((unsigned)((size_t)n * a.p.bx)), block(kThreads);
-    hipLaunchKernelGGL(obj_init_kernel, grid, block, 0, st, a);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(obj_merge_kernel, grid, block, 0, st, a);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(obj_flatten_kernel, grid, block, 0, st, a);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(obj_total_kernel, dim3(n), dim3(64), 0, st, a.partial, a.p.bx, reinterpret_cast<long long *>(n_objects));
-    HIP_TRY(hipGetLastError());
-    return CAE_OK;
+    return launch_components(target, extent, n, h, w, by_value ? kByValue : kAny, 8, labels,
+                             reinterpret_cast<long long *>(n_objects), workspace, (hipStream_t)stream);
 }
 
 extern "C" size_t cae_seg_object_cover_workspace(int n, int h, int w) {

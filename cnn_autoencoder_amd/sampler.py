@@ -63,13 +63,24 @@ def philox_normals(seed: int, sample: np.ndarray, pixel: np.ndarray) -> np.ndarr
     return out
 
 
-def _zarr_tiles(stores, group: str):
+def _zarr_tiles(stores, group: str, mask_group: Optional[str] = None):
     """Every chunk of the ``group`` array (Y, X, C uint8; or Y, X) of each store as one tile, padded to the chunk shape:
-    ``(tiles, valid (rows, columns) per tile, [(Y, X) shape and chunks per store])``."""
+    ``(tiles, valid (rows, columns) per tile, [(Y, X) shape and chunks per store])``.  With ``mask_group`` only the
+    chunks that the store's mask touches (``tissue.mask_tiles``; a bool or uint8 (Y', X') array with the attribute
+    ``scale``, as ``tissue.mask_zarr`` writes it); ValueError if that leaves none."""
     from .zarrio import ZarrArray
     tiles, hw, shape, geometry = [], [], None, []
     for store in ([stores] if isinstance(stores, str) else stores):
         arr = ZarrArray.open(store, group)
+        keep = None
+        if mask_group is not None:
+            from .tissue import mask_tiles
+            marr = ZarrArray.open(store, mask_group)
+            if 'scale' not in marr.attrs:
+                raise ValueError(f"{store}: the mask {mask_group} has no 'scale' attribute")
+            if len(marr.shape) != 2 or marr.dtype not in (np.dtype(np.bool_), np.dtype(np.uint8)):
+                raise ValueError(f'{store}: expected a bool or uint8 (Y, X) mask, got {marr.dtype} {marr.shape}')
+            keep = mask_tiles(marr[:], float(marr.attrs['scale']), arr.shape[:2], arr.chunks[:2])
         if len(arr.shape) not in (2, 3) or arr.dtype != np.uint8:
             raise ValueError(f'{store}: expected a uint8 (Y, X, C) or (Y, X) array, got {arr.dtype} {arr.shape}')
         if len(arr.shape) == 3 and arr.chunks[2] != arr.shape[2]:
@@ -80,11 +91,13 @@ def _zarr_tiles(stores, group: str):
             raise ValueError(f'{store}: chunk shape {arr.chunks} differs from {shape}; tiles must be of equal shape')
         geometry.append((tuple(arr.shape[:2]), tuple(arr.chunks[:2])))
         for idx in arr.chunk_indices():
+            if keep is not None and not keep[idx[0], idx[1]]:
+                continue
             data = arr[arr.chunk_slices(idx)]
             hw.append(data.shape[:2])
             tiles.append(arr.pad_chunk(data))
     if not tiles:
-        raise ValueError('no store given')
+        raise ValueError('no store given' if mask_group is None or not geometry else f'the masks {mask_group} leave no tile')
     return tiles, hw, geometry
 
 
@@ -150,11 +163,14 @@ class PatchSampler:
 
     # ---- construction from slides ------------------------------------------------------------------------------------
     @classmethod
-    def from_zarr(cls, stores: Sequence[str], data_group: str = '0/0', patch_size: int = 128, **kwargs) -> 'PatchSampler':
+    def from_zarr(cls, stores: Sequence[str], data_group: str = '0/0', patch_size: int = 128,
+                  mask_group: Optional[str] = None, **kwargs) -> 'PatchSampler':
         """A sampler over every chunk of the ``data_group`` array (Y, X, C uint8; or Y, X) of each store, read through
         ``ZarrArray.__getitem__``.  One tile per chunk: all stores share one chunk shape; the chunks on the lower and
-        right edges of an image are padded to it (``ZarrArray.pad_chunk``) and keep their valid size."""
-        tiles, hw, _ = _zarr_tiles(stores, data_group)
+        right edges of an image are padded to it (``ZarrArray.pad_chunk``) and keep their valid size.  ``mask_group``
+        (the reference's ``--mask-group``, e.g. 'masks/0/0' of ``tissue.mask_zarr``): only the chunks that the store's
+        mask touches enter the pool, in their order; ValueError when none is left."""
+        tiles, hw, _ = _zarr_tiles(stores, data_group, mask_group)
         return cls(np.stack(tiles), patch_size, tile_hw=np.asarray(hw, dtype=np.int32), **kwargs)
 
     # ---- host: the random draws --------------------------------------------------------------------------------------
@@ -605,13 +621,14 @@ class LabeledPatchSampler(PatchSampler):
 
     @classmethod
     def from_zarr(cls, stores: Sequence[str], data_group: str = '0/0', labels_data_group: str = 'labels/0/0',
-                  patch_size: int = 128, **kwargs) -> 'LabeledPatchSampler':
+                  patch_size: int = 128, mask_group: Optional[str] = None, **kwargs) -> 'LabeledPatchSampler':
         """``PatchSampler.from_zarr`` for both arrays of each store: the image (Y, X, C) under ``data_group`` and the
         labels (Y, X, K; or Y, X) under ``labels_data_group``, both read through ``ZarrArray``.  The two arrays of a store
         must agree in Y / X shape and chunking (ValueError otherwise), so a chunk of one is the tile of the other; ragged
-        edge tiles keep their valid size for both."""
-        tiles, hw, geometry = _zarr_tiles(stores, data_group)
-        masks, mask_hw, mask_geometry = _zarr_tiles(stores, labels_data_group)
+        edge tiles keep their valid size for both.  ``mask_group``: one selection of chunks for image and labels, as in
+        ``PatchSampler.from_zarr``."""
+        tiles, hw, geometry = _zarr_tiles(stores, data_group, mask_group)
+        masks, mask_hw, mask_geometry = _zarr_tiles(stores, labels_data_group, mask_group)
         for store, g, mg in zip([stores] if isinstance(stores, str) else stores, geometry, mask_geometry):
             if g != mg:
                 raise ValueError(f'{store}: image {data_group} has (Y, X) shape and chunks {g}, labels {labels_data_group} '

@@ -144,6 +144,20 @@ class ZarrArray:
             raise ValueError('only C order is supported')
         return cls(root, meta, codec=codec)
 
+    # ---- attributes (.zattrs) ----------------------------------------------------------------
+    @property
+    def attrs(self) -> dict:
+        """the array's user attributes: the JSON object of its .zattrs file, {} where there is none"""
+        p = os.path.join(self.root, '.zattrs')
+        if not os.path.exists(p):
+            return {}
+        with open(p) as f:
+            return json.load(f)
+
+    def write_attrs(self, attrs: dict):
+        with open(os.path.join(self.root, '.zattrs'), 'w') as f:
+            json.dump(dict(attrs), f, indent=4, sort_keys=True)
+
     # ---- chunk grid --------------------------------------------------------------------------
     @property
     def grid(self) -> Tuple[int, ...]:

@@ -987,6 +987,66 @@ int cae_seg_weight_map(const float *target_dev, const int32_t *d2_dev, const int
                        const float *class_weights_dev, int n_class_weights, float sigma_2, float w_0, int n, size_t hw,
                        float *out_dev, int *flag_dev, void *stream);
 
+/* ---- Tissue mask of a slide (csrc/cae_mask.hip) ----------------------------------------------------
+ * The reference's scripts/compute_mask.py on the device: gray, Otsu threshold, small objects out, small holes in,
+ * dilation by a disk -- with the labelling of cae_seg_components and the distances of cae_seg_object_distances between
+ * the kernels here.  All results are integers or float64 values rounded operation by operation: functions of the input
+ * alone, bitwise repeatable.  The host makes the threshold from the 256 counts (tissue.otsu_threshold).
+ *
+ * cae_mask_gray: img_dev (n, hw, 3) uint8 -> gray_dev (n, hw) float64 and minmax_dev float64 [n][2] = (min, max) of each
+ * plane.  gray = (0.2125 r + 0.7154 g) + 0.0721 b with r = R / 255.0 (likewise g, b), every operation rounded on its
+ * own.  Gray is never negative, so the range is an integer min / max over the bit patterns.
+ *
+ * cae_mask_hist: gray_dev and edges_dev float64 [n][257] (numpy.linspace(min, max, 257) of each plane, made by the
+ * caller) -> counts_dev int64 [n][256], the counts of numpy.histogram(gray, 256): bin = (int)((x - e[0]) (256 / (e[256]
+ * - e[0]))), 256 becomes 255, then one step down where x < e[bin] and one step up where x >= e[bin + 1] below the last
+ * bin.  The bin is clamped to 0..255 before it is an index.  A block counts in 32-bit LDS bins and folds them into 64-bit
+ * sums every cae_mask_hist_fold() pixels; blocks write partials that a second launch sums.  A plane with min == max
+ * gives no meaningful counts (the caller's threshold is then the value itself).
+ *
+ * cae_mask_threshold: plane_dev (n, hw) uint8 = gray <= thr_dev[n] (float64 [n]), 1 or 0.
+ *
+ * cae_mask_label: plane_dev (n, h, w) uint8 -> labels_dev (n, h, w) int32 as cae_seg_components writes them (0, or 1 +
+ * the smallest row-major index of the object), with connectivity 4 (edges) or 8 (edges and corners).  Foreground is
+ * plane != 0, or with of_zero != 0 plane == 0: the objects of the complement.
+ *
+ * cae_mask_area_filter: labels_dev of cae_mask_label -> every pixel of plane_inout_dev (n, h, w) uint8 whose object has
+ * fewer than min_area pixels becomes set_value (0 or 1).  Areas stand in an int32 array addressed by the root pixel
+ * (workspace: cae_mask_area_workspace bytes, 4-byte aligned): one launch clears the roots' entries, one counts -- the
+ * first lane of every run of equal labels among a wave's 64 consecutive pixels adds the run's length, and a run that
+ * goes on into the wave's next 64 pixels is carried there before it is added -- and one rewrites.
+ * wide_out_dev (n, h, w) int32, or NULL: the resulting plane as 0 / 1, the form cae_seg_object_distances reads.  A
+ * label that does not name a root pixel of its plane is ignored; no label is an index before that is checked.
+ *
+ * cae_mask_within: d2_dev (n, 2, h w) int32 of cae_seg_object_distances -> plane_dev (n, hw) uint8 = 0 <= d2[n][0] <= r2:
+ * the dilation by the disk dx^2 + dy^2 <= r2 (an empty plane, all -1, stays empty).
+ *
+ * cae_mask_downscale: img_dev uint8, n images of h x w pixels of c channels (1..4), rows row_pitch bytes and images
+ * plane_pitch bytes apart -> out_dev (n, ceil(h / f), ceil(w / f), c) uint8, dense: the mean of the f x f block (f in
+ * 1..64; only the real pixels of a block on the lower or right edge), (2 sum + count) / (2 count) in integers.
+ *
+ * Neither outputs nor workspaces need initialising.  Launches are asynchronous on `stream`.  CAE_ERR_ARG before any
+ * launch: n < 0, hw / h / w < 1, hw or h w > 2^31 - 1, planes beyond 3 min(h, w) <= 65535 or h, w <= 32768 (label, area
+ * filter), connectivity not 4 or 8, min_area < 0, set_value not 0 or 1, r2 < 0, c outside 1..4, f outside 1..64, pitches
+ * shorter than a row or an image, and for n >= 1 a NULL or misaligned pointer or a workspace that is too small.  n == 0:
+ * CAE_OK, nothing launched.  The queries return 0 for refused shapes and for n == 0. */
+int cae_mask_gray(const uint8_t *img_dev, int n, size_t hw, double *gray_dev, double *minmax_dev, void *stream);
+int cae_mask_hist(const double *gray_dev, const double *edges_dev, int n, size_t hw, int64_t *counts_dev,
+                  void *workspace_dev, size_t workspace_bytes, void *stream);
+size_t cae_mask_hist_workspace(int n, size_t hw);
+size_t cae_mask_hist_fold(void);
+int cae_mask_threshold(const double *gray_dev, const double *thr_dev, int n, size_t hw, uint8_t *plane_dev, void *stream);
+int cae_mask_label(const uint8_t *plane_dev, int n, int h, int w, int connectivity, int of_zero, int32_t *labels_dev,
+                   void *workspace_dev, size_t workspace_bytes, void *stream);
+size_t cae_mask_label_workspace(int n, int h, int w);
+int cae_mask_area_filter(const int32_t *labels_dev, int n, int h, int w, int min_area, int set_value,
+                         uint8_t *plane_inout_dev, int32_t *wide_out_dev, void *workspace_dev, size_t workspace_bytes,
+                         void *stream);
+size_t cae_mask_area_workspace(int n, int h, int w);
+int cae_mask_within(const int32_t *d2_dev, int n, size_t hw, int r2, uint8_t *plane_dev, void *stream);
+int cae_mask_downscale(const uint8_t *img_dev, int n, int h, int w, int c, size_t row_pitch, size_t plane_pitch, int f,
+                       uint8_t *out_dev, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
