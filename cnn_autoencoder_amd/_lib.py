@@ -201,6 +201,9 @@ SYMBOLS = {
     'cae_mask_area_workspace': (c_size_t, [c_int, c_int, c_int]),
     'cae_mask_within': (c_int, [c_void_p, c_int, c_size_t, c_int, c_void_p, c_void_p]),
     'cae_mask_downscale': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_size_t, c_size_t, c_int, c_void_p, c_void_p]),
+    'cae_tile_byte_hist': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    'cae_tile_byte_hist_workspace': (c_size_t, [c_int, c_int, c_int, c_int]),
+    'cae_tile_byte_hist_blocks': (c_int, [c_int, c_int, c_int, c_int]),
     'cae_seg_set_weights': (c_int, [c_void_p, c_void_p, c_int, c_void_p]),
     'cae_seg_pack_dev': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p]),
     'cae_seg_conv2d_workspace': (c_size_t, [c_int] * 6),

@@ -9,6 +9,9 @@ its datasets then draw patches inside that mask (``--mask-group``).  Here:
     otsu_threshold the threshold from 256 counts and their edges, on the host in float64
     mask_zarr      a store's image -> its mask under masks/0/0, with the attribute 'scale'
     mask_tiles     which chunks of an array a mask touches: what the samplers' ``mask_group`` keeps
+    tile_histograms       exact byte histograms of tiles on the device (cae_tile_byte_hist, csrc/cae_tiles.hip): the look
+                          zarrio.compress_image takes at the chunks a mask does not touch before it skips them
+    fill_from_histogram, fill_sse   the fill value with the least squared error and that error, exact, on the host
 
 The contract is stated in numpy / scipy terms ("Tissue mask"); parity with skimage's own functions is unpinned.
 """
@@ -21,7 +24,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .segmenters import MAX_DISTANCE_EDGE, _check_planes, _workspace, object_distances
+from .segmenters import MAX_DISTANCE_EDGE, _check_planes, _extent_arg, _workspace, object_distances
 
 MAX_FACTOR = 64
 BINS = 256
@@ -202,6 +205,83 @@ def mask_tiles(mask, scale: float, shape, chunks) -> np.ndarray:
             c0, c1 = span(j * cw, min((j + 1) * cw, W), mask.shape[1])
             keep[i, j] = bool(mask[r0:r1, c0:c1].any())
     return keep
+
+
+# ---- the look at background tiles: exact byte histograms, and the fill value and squared error they fix ----------------
+@torch.no_grad()
+def tile_histograms(tiles: torch.Tensor, extents=None) -> torch.Tensor:
+    """uint8 tiles (N,H,W,C) on the device, contiguous, C <= 4, read where they stand (any byte address) -> int64 CUDA
+    tensor (N, 256): how many samples of every tile hold each value (cae_tile_byte_hist, csrc/cae_tiles.hip; asynchronous on
+    the current stream).  ``extents``: (N,2) integers (rows, cols): only the samples y < rows, x < cols of each tile are
+    counted (values are clamped to the tile), so the padding of an edge chunk is in no histogram.  Counts are exact and
+    add over tiles, batches and ranks; every row sums to rows cols C."""
+    if not isinstance(tiles, torch.Tensor):
+        raise ValueError(f'expected a uint8 tensor (N,H,W,C) on the device, got {type(tiles).__name__}')
+    if tiles.dtype != torch.uint8 or tiles.dim() != 4:
+        raise ValueError(f'expected uint8 tiles (N,H,W,C), got {tiles.dtype} {tuple(tiles.shape)}')
+    n, h, w, c = tiles.shape
+    if not 1 <= c <= 4:
+        raise ValueError(f'expected 1 to 4 channels, got {c}')
+    if n and (h < 1 or w < 1):
+        raise ValueError(f'empty tiles: {n} x {h} x {w}')
+    if not tiles.is_cuda:
+        raise ValueError(f'expected tiles on the device, got them on {tiles.device}: there is no CPU path')
+    if not tiles.is_contiguous():
+        raise ValueError('expected contiguous tiles')
+    dev = tiles.device
+    ext = _extent_arg(extents, n, dev)
+    with torch.cuda.device(dev):
+        if n == 0:
+            return torch.zeros((0, BINS), dtype=torch.int64, device=dev)
+        L = _lib.lib()
+        hist = torch.empty((n, BINS), dtype=torch.int64, device=dev)
+        ws = _workspace(L.cae_tile_byte_hist_workspace(n, h, w, c), dev)
+        _lib.check(L.cae_tile_byte_hist(tiles.data_ptr(), None if ext is None else ext.data_ptr(), n, h, w, c,
+                                        hist.data_ptr(), ws.data_ptr(), ws.numel() * 8, _lib.stream_ptr()))
+    return hist
+
+
+def _counts(hist) -> np.ndarray:
+    """integer histograms (..., 256), host or device -> the same as Python integers (an object array): no product or sum
+    of them is rounded or wraps"""
+    if isinstance(hist, torch.Tensor):
+        hist = hist.detach().cpu().numpy()
+    hist = np.asarray(hist)
+    if hist.dtype.kind not in 'iuO' or hist.ndim not in (1, 2) or hist.shape[-1] != BINS:
+        raise ValueError(f'expected integer histograms (256,) or (N, 256), got {hist.dtype} {hist.shape}')
+    out = hist.astype(object)
+    if any(v < 0 for v in out.ravel()):
+        raise ValueError('a histogram holds a negative count')
+    return out
+
+
+def fill_from_histogram(hist):
+    """Histograms (N, 256) of tile_histograms (or one, (256,)) -> (fill, sse): with cnt = their sum over the tiles, the f
+    in 0..255 with the smallest sum_v cnt[v] (v - f)^2, the smallest such f on a tie, and that sum.  Python integers on the
+    host: exact whatever the counts.  All counts zero: (0, 0)."""
+    cnt = _counts(hist)
+    if cnt.ndim == 2:
+        cnt = cnt.sum(axis=0) if cnt.shape[0] else np.zeros(BINS, dtype=object)
+    s0 = sum(int(k) for k in cnt)
+    s1 = sum(int(k) * v for v, k in enumerate(cnt))
+    s2 = sum(int(k) * v * v for v, k in enumerate(cnt))
+    best = min(range(BINS), key=lambda f: (s2 - 2 * f * s1 + f * f * s0, f))
+    return best, s2 - 2 * best * s1 + best * best * s0
+
+
+def fill_sse(hist, fill: int) -> np.ndarray:
+    """Histograms (N, 256) of tile_histograms and a fill value in 0..255 -> int64 (N,): sum_v hist[i][v] (v - fill)^2, the
+    squared error of every tile against the fill value, exact (a sum beyond 2^63 - 1 is an OverflowError)."""
+    if isinstance(fill, bool) or int(fill) != fill or not 0 <= int(fill) <= 255:
+        raise ValueError(f'the fill value is an integer in 0..255, got {fill!r}')
+    cnt = _counts(hist)
+    if cnt.ndim != 2:
+        raise ValueError(f'expected histograms (N, 256), got {cnt.shape}')
+    weight = np.array([(v - int(fill)) ** 2 for v in range(BINS)], dtype=object)
+    sums = [int(sum(row * weight)) for row in cnt]
+    if any(s > np.iinfo(np.int64).max for s in sums):
+        raise OverflowError('a squared error leaves 64 bits')
+    return np.array(sums, dtype=np.int64).reshape(len(sums))
 
 
 MASK_GROUP = 'masks/0/0'

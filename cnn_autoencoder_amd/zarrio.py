@@ -158,6 +158,12 @@ class ZarrArray:
         with open(os.path.join(self.root, '.zattrs'), 'w') as f:
             json.dump(dict(attrs), f, indent=4, sort_keys=True)
 
+    @property
+    def is_sparse(self) -> bool:
+        """written by compress_image with a mask or a fill value (the attribute 'sparse'): chunks without a file are
+        meant, and the slide drivers leave them out; in any other array they take a missing chunk file for damage"""
+        return 'sparse' in self.attrs
+
     # ---- chunk grid --------------------------------------------------------------------------
     @property
     def grid(self) -> Tuple[int, ...]:
@@ -354,13 +360,84 @@ def _batches(items: Sequence, n: int) -> Iterable[Sequence]:
         yield items[i:i + n]
 
 
+def _sparse_plan(image, patch_size, keep, fill_value, max_fill_rmse, batch_tiles, rank, world):
+    """Pass 1 of a sparse compress_image -> (the chunk indices of this rank that get no file, the fill value, the
+    'sparse' attribute of the array).  `keep`: (grid rows, grid columns) bool, the chunks the mask keeps; the others are
+    the candidates.  This rank's candidates go to the device in batches of `batch_tiles` padded chunks, their byte
+    histograms over the real (rows, cols) come back, and fill value, rescues and the exact squared error follow on the
+    host; the sums over the ranks are integer all-reduces.  With a given fill value and no guard nothing is uploaded."""
+    import torch
+    from . import slide, tissue
+    h, w, c = image.shape
+    src = ZarrArray(None, dict(shape=[h, w, c], chunks=[patch_size, patch_size, c], dtype='|u1'), codec=_Raw())
+    tiles = src.chunk_indices()
+    lo, hi = slide.tile_range(rank, world, len(tiles))
+    cand = [idx for idx in tiles[lo:hi] if not keep[idx[0], idx[1]]]
+    account = dict(tiles=len(tiles), kept=int(np.count_nonzero(keep)), rescued=0, skipped=len(tiles) - int(np.count_nonzero(keep)),
+                   skipped_samples=None, skipped_sse=None)
+    if fill_value is not None and max_fill_rmse is None:
+        return set(cand), int(fill_value), dict(account, fill_value=int(fill_value))
+    # two pinned staging buffers: the host fills one while the copy engine empties the other; a chunk's real part is
+    # copied once and what lies beyond it is never counted, so nothing is padded; the histograms come back in one copy
+    stage = [torch.empty((batch_tiles, patch_size, patch_size, c), dtype=torch.uint8).pin_memory() for _ in range(2)] if cand else []
+    sent = [None, None]
+    parts = []
+    for k, group in enumerate(_batches(cand, batch_tiles)):
+        pin = stage[k % 2]
+        if sent[k % 2] is not None:
+            sent[k % 2].synchronize()
+        real = []
+        for t, idx in enumerate(group):
+            part = image[src.chunk_slices(idx)]
+            pin[t, :part.shape[0], :part.shape[1]] = torch.from_numpy(part)
+            real.append(part.shape[:2])
+        batch = pin[:len(group)].to('cuda', non_blocking=True)
+        sent[k % 2] = torch.cuda.Event()
+        sent[k % 2].record()
+        parts.append(tissue.tile_histograms(batch, real))
+    hist = torch.cat(parts).cpu().numpy() if parts else np.zeros((0, 256), dtype=np.int64)
+    if fill_value is None:
+        total = slide.reduce_histogram(torch.from_numpy(hist.sum(axis=0)).cuda())
+        fill_value = tissue.fill_from_histogram(total)[0]
+    fill_value = int(fill_value)
+    sse, samples = tissue.fill_sse(hist, fill_value), hist.sum(axis=1)
+    if max_fill_rmse is None:
+        rescue = np.zeros(len(cand), dtype=bool)
+    else:
+        rescue = sse.astype(np.float64) / np.maximum(samples, 1).astype(np.float64) > float(max_fill_rmse) ** 2
+    mine = [int(np.count_nonzero(rescue)), int(np.count_nonzero(~rescue)), int(samples[~rescue].sum()),
+            int(sse[~rescue].sum())]
+    rescued, n_skipped, skipped_samples, skipped_sse = (int(v) for v in slide.reduce_histogram(
+        torch.tensor(mine, dtype=torch.int64, device='cuda')).cpu())
+    account.update(fill_value=fill_value, rescued=rescued, skipped=n_skipped, skipped_samples=skipped_samples,
+                   skipped_sse=skipped_sse)
+    return {idx for idx, r in zip(cand, rescue) if not r}, fill_value, account
+
+
 def compress_image(codec: str, checkpoint, image: np.ndarray, output_filename: str, patch_size: int = 512,
                    data_group: str = '0/0', save_as_bottleneck: bool = False, gpu: bool = True,
-                   batch_tiles: int = 32, coder: str = 'host') -> ZarrArray:
+                   batch_tiles: int = 32, coder: str = 'host', mask=None, mask_scale: Optional[float] = None,
+                   fill_value: Optional[int] = None, max_fill_rmse: Optional[float] = None) -> ZarrArray:
     """compress.py:29-128 for an in-memory (H, W, C) uint8 image: rechunk to (patch, patch, C) and write a
     zarr array whose chunks are ``codec`` bitstreams.  codec: 'CAE' | 'Zlib' | 'None' (the reference's
     'Blosc' / 'Jpeg*' names are other libraries' codecs and raise ValueError here).  coder: where the range coder of
-    the CAE codecs runs, 'host' or 'device' (same chunk bytes)."""
+    the CAE codecs runs, 'host' or 'device' (same chunk bytes).
+
+    Sparse stores ('CAE' pixel arrays only; without ``mask`` and ``fill_value`` nothing below applies and the store is
+    what it always was).  ``mask`` (Y, X) at ``mask_scale`` mask pixels per image pixel, as tissue.tissue_mask and
+    tissue.mask_zarr make it: the chunks that ``tissue.mask_tiles`` does not keep are candidates for skipping.  A skipped
+    chunk has no file -- a stale one is removed -- and reads as the array's ``fill_value`` (zarr v2), which also pads the
+    edge chunks.
+    Pass 1 looks at this rank's candidates on the device (tissue.tile_histograms over each chunk's real pixels, batches of
+    ``batch_tiles``): ``fill_value`` None takes the value with the least squared error over all candidates of all ranks
+    (tissue.fill_from_histogram of the histograms' sum, slide.reduce_histogram), else an integer in 0..255 is taken as
+    given.  ``max_fill_rmse``: a candidate whose squared error against the fill value per sample is above its square
+    (float64) is rescued, i.e. coded like a kept chunk -- a pen mark, faint tissue the mask missed.  With a given
+    ``fill_value`` and no ``max_fill_rmse`` no candidate is looked at or uploaded.
+    Rank 0 writes ``.zattrs['sparse'] = dict(fill_value, tiles, kept, rescued, skipped, skipped_samples, skipped_sse)``,
+    sums over all ranks: ``kept`` chunks the mask keeps, ``skipped_sse`` the exact integer squared error of the skipped
+    chunks' real samples against the fill value (both ``skipped_*`` None where pass 1 did not run).  The squared error of
+    the whole slide is ``skipped_sse`` plus the coded chunks' (slide.slide_summary's ``sse`` column), over all samples."""
     from . import slide
     from .entropy import check_coder
     check_coder(coder)
@@ -373,6 +450,26 @@ def compress_image(codec: str, checkpoint, image: np.ndarray, output_filename: s
         data_group = '0/0'
     h, w, c = image.shape
     rank, world = _rank_world()
+    sparse = mask is not None or fill_value is not None
+    if mask is None and (mask_scale is not None or max_fill_rmse is not None):
+        raise ValueError('mask_scale and max_fill_rmse need a mask')
+    if sparse:
+        if 'CAE' not in codec or save_as_bottleneck:
+            raise ValueError("a mask or a fill_value needs the 'CAE' pixel codec (no save_as_bottleneck, 'Zlib' or 'None')")
+        if mask is not None and mask_scale is None:
+            raise ValueError('a mask needs its mask_scale (mask pixels per image pixel)')
+        if fill_value is not None and (isinstance(fill_value, (bool, np.bool_)) or not isinstance(
+                fill_value, (int, np.integer)) or not 0 <= int(fill_value) <= 255):
+            raise ValueError(f'fill_value is an integer in 0..255, got {fill_value!r}')
+        if max_fill_rmse is not None and not (isinstance(max_fill_rmse, (int, float, np.integer, np.floating))
+                                              and not isinstance(max_fill_rmse, bool) and max_fill_rmse >= 0):
+            raise ValueError(f'max_fill_rmse is a number >= 0, got {max_fill_rmse!r}')
+        if not 1 <= c <= 4:
+            raise ValueError(f'a sparse store needs 1 to 4 channels, got {c}')
+        keep = np.ones((-(-h // patch_size), -(-w // patch_size)), dtype=bool)
+        if mask is not None:
+            from . import tissue
+            keep = tissue.mask_tiles(mask, mask_scale, image.shape, (patch_size, patch_size))
     if 'CAE' in codec and not save_as_bottleneck and not isinstance(checkpoint, str):
         # the 'cae' codec persists its checkpoint PATH in the .zarray metadata (_autoencoders.py:532): fail before
         # the model is built, not when the metadata is written
@@ -412,20 +509,29 @@ def compress_image(codec: str, checkpoint, image: np.ndarray, output_filename: s
         compressor = None
     else:
         raise ValueError('Codec %s not supported' % codec)
+    skipped, account = set(), None
+    if sparse:
+        skipped, fill_value, account = _sparse_plan(image, patch_size, keep, fill_value, max_fill_rmse, batch_tiles,
+                                                    rank, world)
     z = ZarrArray.create(output_filename, data_group, (h, w, c), (patch_size, patch_size, c), np.uint8,
-                         codec=compressor, write_meta=rank == 0)
+                         codec=compressor, write_meta=rank == 0, **(dict(fill_value=fill_value) if sparse else {}))
     tiles = z.chunk_indices()
     lo, hi = slide.tile_range(rank, world, len(tiles))
     if isinstance(compressor, ConvolutionalAutoencoder):
         # pipelined: the GPU analyses the next batches while a host worker range-encodes and this thread writes files
         import struct
-        groups = list(_batches(tiles[lo:hi], batch_tiles))
+        for idx in tiles[lo:hi]:
+            if idx in skipped and os.path.exists(z.chunk_path(idx)):  # a skipped chunk is a chunk without a file
+                os.remove(z.chunk_path(idx))
+        groups = list(_batches([i for i in tiles[lo:hi] if i not in skipped], batch_tiles))
         sc = slide.SlideCoder(compressor, coder=coder)
         stream = sc.compress_batches(np.stack([z.pad_chunk(image[z.chunk_slices(i)]) for i in g]) for g in groups)
         head = struct.pack('>QQ', patch_size, patch_size)  # chunk = '>QQ'(h, w) + rANS payload (_autoencoders.py:553-555)
         for group, payloads in zip(groups, stream):
             for idx, payload in zip(group, payloads):
                 z.write_chunk_bytes(idx, head + payload)
+        if sparse and rank == 0:
+            z.write_attrs(dict(z.attrs, sparse=account))
         _barrier()
         return z
     for idx in tiles[lo:hi]:
@@ -442,7 +548,9 @@ def decompress_image(input_filename: str, data_group: str = '0/0', checkpoint=No
     roi = (y0, y1, x0, x1), full-resolution pixels: the reference's ROI flow (decompress.py:49-59, parse_roi applied
     before anything is decoded) -- only the chunks under the rectangle are read and decoded.  scale = s: the image at
     1 / 2^s of the resolution (ZarrArray.read_region: rows floor(y0 / 2^s) : ceil(y1 / 2^s) of the mosaic of scale-s
-    tiles); needs a 'cae' array or the 'cae_bn' + checkpoint branch, and a model with colour layers."""
+    tiles); needs a 'cae' array or the 'cae_bn' + checkpoint branch, and a model with colour layers.
+    The chunks a sparse store (``ZarrArray.is_sparse``) has no file for are not decoded: their part of the result is the
+    array's fill_value, at any scale.  A full read of any other 'cae' store raises ValueError at a missing chunk file."""
     from .entropy import check_coder
     check_coder(coder)
     from .codec import ConvolutionalAutoencoder, _module, autoencoder_from_state_dict
@@ -463,7 +571,11 @@ def decompress_image(input_filename: str, data_group: str = '0/0', checkpoint=No
             import struct
             from . import slide
             out = np.empty(z.shape, dtype=z.dtype)
-            groups = list(_batches(z.chunk_indices(), batch_tiles))
+            present = z.chunk_indices()
+            if z.is_sparse:  # the chunks without a file are not decoded: their part of the image is the fill value
+                out[...] = z.fill_value
+                present = [i for i in present if os.path.exists(z.chunk_path(i))]
+            groups = list(_batches(present, batch_tiles))
             ph, pw = z.chunks[0], z.chunks[1]
 
             def payloads(group):
@@ -553,6 +665,13 @@ def segment_image(input_filename: str, seg_model, output_filename: str, data_gro
     'auc', 'auc_slack' and 'roc'; rank 0 then writes object_level/fpr, tpr, thrsh and thrsh_logit as above.  An object cut
     by a tile border counts as two.
 
+    A sparse store (compress_image with a mask; ``ZarrArray.is_sparse``): the chunks without a file are not run and get no
+    class/0/0 or scores/0/0 chunk -- their fill 0 is the background class -- and the result gains 'skipped_tiles' (this
+    rank's).  With a target the record of such a chunk is made on the host from its labels with the prediction "background
+    everywhere": one class, tn = the count of target == 0 and fn = p = the count of target > 0; several classes, tp =
+    tp_top = the count of target == 0, fp = fn = pixels - tp, p = pixels.  ``roc_bits`` and ``object_level`` raise
+    ValueError there: a skipped chunk has no logit.  In any other store a missing chunk file raises ValueError.
+
     -> segmenters.class_metrics of the slide's summed record, plus
     'records': the (tiles, 6) int64 per-tile records of all ranks in tile order (slide.gather_counts), 'tiles' and
     'head_fp32_repeats' (this rank's); without a target only the last two."""
@@ -587,6 +706,9 @@ def segment_image(input_filename: str, seg_model, output_filename: str, data_gro
         if tz is None or C != 1:
             raise ValueError('roc_bits needs a target_group and a one-class head')
         roc_bits = segmenters._check_roc_bits(roc_bits)
+    sparse = z.is_sparse
+    if sparse and (roc_bits is not None or object_level):
+        raise ValueError('roc_bits and object_level are not available on a sparse store: a skipped chunk has no logit')
     sc = slide.SlideCoder(z.codec, coder=coder)
     zc = ZarrArray.create(output_filename, 'class/0/0', (H, W), (ph, pw), np.bool_ if C == 1 else np.uint8,
                           codec=Zlib(9), write_meta=rank == 0)
@@ -594,7 +716,10 @@ def segment_image(input_filename: str, seg_model, output_filename: str, data_gro
                           write_meta=rank == 0) if scores else None
     tiles = z.chunk_indices()
     lo, hi = slide.tile_range(rank, world, len(tiles))
-    groups = list(_batches(tiles[lo:hi], batch_tiles))
+    run = tiles[lo:hi]
+    if sparse:  # the chunks without a file are not run: their class is the fill 0 of class/0/0, the background
+        run = [i for i in run if os.path.exists(z.chunk_path(i))]
+    groups = list(_batches(run, batch_tiles))
     # the real pixels (rows, cols) of every tile: an edge chunk is padded beyond them, and the padding is in no histogram
     sizes = [[(min(ph, H - i * ph), min(pw, W - j * pw)) for i, j, _ in g] for g in groups]
 
@@ -645,6 +770,18 @@ def segment_image(input_filename: str, seg_model, output_filename: str, data_gro
                     rec[t, 2] -= pad_on
             records.append(torch.from_numpy(rec))
     out = dict(tiles=hi - lo, head_fp32_repeats=sc.timers.get('head_fp32_repeats', 0))
+    if sparse:
+        out['skipped_tiles'] = (hi - lo) - len(run)
+    if tz is not None and len(run) < hi - lo:
+        # a skipped chunk's record, made here from its labels: the prediction is background everywhere
+        def background(idx):
+            part = tz[idx[0] * ph:min((idx[0] + 1) * ph, H), idx[1] * pw:min((idx[1] + 1) * pw, W)]
+            px, zero = int(part.size), int(np.count_nonzero(part == 0))
+            return (0, zero, 0, px - zero, px - zero, 0) if C == 1 else (zero, 0, px - zero, px - zero, px, zero)
+
+        done = dict(zip(run, torch.cat(records).numpy())) if records else {}
+        rows = [done[i] if i in done else background(i) for i in tiles[lo:hi]]  # in tile order, as ever
+        records = [torch.from_numpy(np.array(rows, dtype=np.int64).reshape(-1, slide.COUNTS_WIDTH))]
 
     def gathered(parts):  # this rank's (tiles, 6) records -> those of all ranks, in tile order
         local = torch.cat(parts) if parts else torch.zeros((0, slide.COUNTS_WIDTH), dtype=torch.int64)

@@ -1047,6 +1047,30 @@ int cae_mask_within(const int32_t *d2_dev, int n, size_t hw, int r2, uint8_t *pl
 int cae_mask_downscale(const uint8_t *img_dev, int n, int h, int w, int c, size_t row_pitch, size_t plane_pitch, int f,
                        uint8_t *out_dev, void *stream);
 
+/* ---- Byte histograms of tiles (csrc/cae_tiles.hip) -------------------------------------------------
+ * The look a sparse slide takes at the tiles its tissue mask calls background (zarrio.compress_image with a mask): the
+ * squared error of a tile against any fill value is a function of the tile's 256 byte counts.
+ * tiles_dev: n contiguous (h, w, c) uint8 tiles, c in 1..4, read where they stand (any byte address).  extent_dev int32
+ * [n][2] = (rows, cols) on the device or NULL: only samples with y < rows and x < cols are counted, all c channels of
+ * them, values clamped to 0..h / 0..w, NULL = whole tiles (the convention of cae_seg_roc_hist); rows beyond `rows` are
+ * never loaded.
+ *   hist_dev int64 [n][256]: hist[i][v] = the number of counted samples of tile i with value v.  Every entry is written
+ *   on every call, nothing is accumulated into what the buffer held; integers, exact in any order, and
+ *   sum_v hist[i][v] = rows_i cols_i c.
+ * Two launches, asynchronous on `stream`: blocks that count a contiguous span of a tile's bytes in a uint32 [256] LDS
+ * table and store it as one partial per (tile, block) in workspace_dev (cae_tile_byte_hist_workspace bytes, 16-byte
+ * aligned), then the sum of the partials in a fixed order.  No global atomics; neither histogram nor workspace needs
+ * initialising.  The blocks of a launch are capped, so on large batches a block's lanes take many turns.
+ * CAE_ERR_ARG before any launch: n < 0, h or w < 1, c outside 1..4, h w c so large that a block's span would leave 32
+ * bits, and for n >= 1 a NULL tiles or histogram pointer, a misaligned extent (4) or histogram (8), or a workspace that
+ * is NULL, not 16-byte aligned or too small.  n == 0: CAE_OK, nothing launched.  cae_tile_byte_hist_workspace and
+ * cae_tile_byte_hist_blocks (blocks per tile, for the tests) return 0 for shapes cae_tile_byte_hist refuses and for
+ * n == 0. */
+int cae_tile_byte_hist(const uint8_t *tiles_dev, const int32_t *extent_dev, int n, int h, int w, int c, int64_t *hist_dev,
+                       void *workspace_dev, size_t workspace_bytes, void *stream);
+size_t cae_tile_byte_hist_workspace(int n, int h, int w, int c);
+int cae_tile_byte_hist_blocks(int n, int h, int w, int c);
+
 #ifdef __cplusplus
 }
 #endif
