@@ -174,6 +174,9 @@ SYMBOLS = {
                                  c_size_t, c_void_p]),
     'cae_seg_roc_workspace': (c_size_t, [c_int, c_int, c_int, c_int]),
     'cae_seg_roc_blocks': (c_int, [c_int, c_int, c_int, c_int]),
+    'cae_seg_score_hist': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p,
+                                   c_void_p, c_size_t, c_void_p]),
+    'cae_seg_score_workspace': (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
     'cae_seg_components': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t,
                                    c_void_p]),
     'cae_seg_components_workspace': (c_size_t, [c_int, c_int, c_int]),

@@ -27,18 +27,6 @@ struct RocArgs {
     int h, w, bits, bx;
 };
 
-// one pixel per lane into the block's histogram; `word` = positive * B + bin
-__device__ __forceinline__ void roc_add(uint32_t *hist, bool on, uint32_t word) {
-    if (on) {
-        const uint32_t lead = __builtin_amdgcn_readfirstlane(word);
-        const unsigned long long same = __ballot(word == lead);  // the lanes of this branch only; the first is among them
-        if (word != lead)
-            atomicAdd(&hist[word], 1u);
-        else if ((int)(threadIdx.x & 63) == __ffsll((long long)same) - 1)
-            atomicAdd(&hist[lead], (uint32_t)__popcll(same));
-    }
-}
-
 __global__ __launch_bounds__(kThreads) void roc_hist_kernel(RocArgs a) {
     extern __shared__ uint32_t hist[];  // [2][B]
     const int n = blockIdx.x / a.bx, x = blockIdx.x % a.bx, tid = threadIdx.x;
@@ -77,7 +65,7 @@ __global__ __launch_bounds__(kThreads) void roc_hist_kernel(RocArgs a) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const bool on = !ragged || c < (size_t)cols;
-            roc_add(hist, on, (((t4 >> (8 * j)) & 255u) ? B : 0u) + roc_bin(v[j], shift));
+            hist_add(hist, on, (((t4 >> (8 * j)) & 255u) ? B : 0u) + roc_bin(v[j], shift));
             if (++c == w) c = 0;
         }
         col += dcol;
@@ -87,7 +75,7 @@ __global__ __launch_bounds__(kThreads) void roc_hist_kernel(RocArgs a) {
     if (x == 0 && (size_t)tid < singles) {
         const size_t p = (size_t)tid < head ? (size_t)tid : tail + ((size_t)tid - head);  // < lim
         const bool on = !ragged || p % w < (size_t)cols;
-        roc_add(hist, on, (tg[p] ? B : 0u) + roc_bin(lg[p], shift));
+        hist_add(hist, on, (tg[p] ? B : 0u) + roc_bin(lg[p], shift));
     }
     __syncthreads();
 

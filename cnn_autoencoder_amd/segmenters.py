@@ -17,6 +17,8 @@ The head's structure is stated once, in the library (``cae_seg_plan``); ``JNet.s
 metrics; ``cae_seg_predict``, csrc/cae_seg_predict.hip); ``slide.SlideCoder.segment_batches`` and ``zarrio.segment_image``
 run whole slides through codec, head and prediction.  ``roc_histogram`` / ``roc_from_histogram`` give the threshold-free
 results of a one-class head, ROC curve and AUC, from exact logit histograms (``cae_seg_roc_hist``, csrc/cae_seg_roc.hip).
+``score_histogram`` / ``ap_from_histogram`` give the average precision of a head of several classes, with bounds on that of
+the unbinned scores, from exact histograms of the softmax scores (``cae_seg_score_hist``, csrc/cae_seg_ap.hip).
 ``components`` / ``object_cover`` / ``object_counts`` / ``object_roc_histogram`` give the object-level half of the harness:
 connected objects of the target, their boxes, and counts and histogram over the pixels of all boxes (csrc/cae_seg_objects.hip).
 
@@ -618,6 +620,145 @@ def roc_from_histogram(hist) -> Dict:
             ties += pb * nb
         auc, slack = area / (2 * P * N), ties / (2 * P * N)
     return dict(fpr=fpr, tpr=tpr, thresholds=thr, score_thresholds=score_thr, auc=auc, auc_slack=slack, p=P, n=N)
+
+
+# ---- average precision from score histograms (csrc/cae_seg_ap.hip); a one-class head's from its ROC histogram --------
+AP_BITS = 14           # bins of the slide histograms: 2^14 per row, the most cae_seg_score_hist takes
+AP_BITS_RANGE = (8, 14)
+
+
+def _check_ap_bits(bits) -> int:
+    if isinstance(bits, bool) or int(bits) != bits or not AP_BITS_RANGE[0] <= int(bits) <= AP_BITS_RANGE[1]:
+        raise ValueError(f'ap bits must be an integer in {AP_BITS_RANGE[0]}..{AP_BITS_RANGE[1]}, got {bits!r}')
+    return int(bits)
+
+
+def score_bin_edges(bits: int = AP_BITS) -> np.ndarray:
+    """float32 (2^bits,): e_j, the smallest score in [0, 1] of bin j of cae_seg_score_hist (include/cae_hip.h), NaN for
+    the bins that no fp32 score reaches: those between the two halves, and near 1 those whose values of 1 - s are no
+    multiple of 2^-24.  For a score s in [0, 1], ``bin(s) >= j`` exactly when ``s >= e_j``."""
+    bits = _check_ap_bits(bits)
+    B, sh = 1 << bits, 31 - bits
+    half = 0x3F000000 >> sh  # bits_of(0.5f) >> sh: the lower half's bins are 0 .. half - 1
+    edges = np.full(B, np.nan, dtype=np.float32)
+    edges[:half] = (np.arange(half, dtype=np.uint32) << np.uint32(sh)).view(np.float32)
+    # upper half: bin B - 1 - q holds t = 1 - s with bits_of(t) >> sh == q; s is a multiple of 2^-24 there, so t is one
+    # too, and the smallest s belongs to the largest such t.  All of it exact in float64
+    q = np.arange(half + 1, dtype=np.uint32)
+    t_min = (q << np.uint32(sh)).view(np.float32).astype(np.float64)
+    t_max = np.minimum((((q + np.uint32(1)) << np.uint32(sh)) - np.uint32(1)).view(np.float32).astype(np.float64), 0.5)
+    k = np.floor(t_max * 2.0 ** 24)
+    reached = k >= t_min * 2.0 ** 24
+    edges[B - 1 - q[reached]] = (1.0 - k[reached] * 2.0 ** -24).astype(np.float32)
+    return edges
+
+
+def _scores_arg(scores):
+    """fp32 scores (N,C,H,W) of a head of 2..255 classes on the device, non-empty planes -> (contiguous, n, c, h, w)"""
+    if not isinstance(scores, torch.Tensor) or scores.dim() != 4 or scores.dtype != torch.float32:
+        raise ValueError('expected fp32 scores (N,C,H,W) on the device')
+    n, c, h, w = scores.shape
+    if not 2 <= c <= 255:
+        raise ValueError(f'the score histogram is built for heads of 2..255 classes, got {c}: a one-class head has '
+                         f"roc_histogram, and ap_from_histogram(..., key='logit') reads it")
+    if n and (h < 1 or w < 1):
+        raise ValueError(f'empty planes: {tuple(scores.shape)}')
+    if h * w > 2 ** 31 - 1:
+        raise ValueError(f'planes of {h} x {w} pixels are too large: a block counts in 32 bits')
+    _lib.require_gpu()
+    if not scores.is_cuda:
+        raise ValueError('expected fp32 scores (N,C,H,W) on the device')
+    return scores.contiguous(), n, c, h, w  # (a view of a larger buffer at any element offset is read in place)
+
+
+@torch.no_grad()
+def score_histogram(scores: torch.Tensor, target: torch.Tensor, extent=None, bits: int = AP_BITS,
+                    per_image: bool = False, per_class: bool = False) -> torch.Tensor:
+    """fp32 scores (N,C,H,W) of a head of 2..255 classes on the device, read as they stand -- ``predict(scores=True)``
+    writes them, any values in [0, 1] will do -- and a uint8 target (N,H,W) -> int64 CUDA tensor (2, 2^bits): row 1 counts
+    the pairs (pixel, class k) with target == k, row 0 all others, per score bin, summed over batch and classes (the
+    micro histogram of the one-hot target); (C, 2, 2^bits) with ``per_class``, (N, 2, 2^bits) with ``per_image``,
+    (N, C, 2, 2^bits) with both (cae_seg_score_hist; asynchronous on the current stream).  A pixel whose label is >= C
+    is unlabelled and counted nowhere.  ``extent``: (N,2) integers (rows, cols): only the pixels y < rows, x < cols of
+    each image are counted (values are clamped to the plane).  Histograms are exact and add; ``ap_from_histogram`` makes
+    average precision and its curve of them."""
+    bits = _check_ap_bits(bits)
+    scores, n, c, h, w = _scores_arg(scores)
+    dev = scores.device
+    tgt = _target_arg(target, dev, n, h, w)
+    ext = _extent_arg(extent, n, dev)
+    shape = ((n,) if per_image else ()) + ((c,) if per_class else ()) + (2, 1 << bits)
+    with torch.cuda.device(dev):
+        if n == 0:
+            return torch.zeros(shape, dtype=torch.int64, device=dev)
+        L = _lib.lib()
+        hist = torch.empty(shape, dtype=torch.int64, device=dev)
+        ws = _workspace(L.cae_seg_score_workspace(n, c, h, w, bits), dev)
+        _lib.check(L.cae_seg_score_hist(scores.data_ptr(), tgt.data_ptr(), _ptr(ext), n, c, h, w, bits,
+                                        int(bool(per_image)), int(bool(per_class)), hist.data_ptr(), ws.data_ptr(),
+                                        ws.numel() * 8, _lib.stream_ptr()))
+    return hist
+
+
+def ap_from_histogram(hist, key: str = 'score') -> Dict:
+    """One histogram (2, B) of score_histogram -- a tile's, or the sum of many tiles' -- or an (M, 2, B) array of them
+    (per image, per class), which is summed -> dict(precision, recall, thresholds, avg_prec, avg_prec_lo, avg_prec_hi,
+    p, n); pure numpy on the host.  ``key='logit'``: a histogram of roc_histogram instead, with roc_bin_edges -- the
+    sigmoid is monotone, so a one-class head has its average precision from the histogram it already has.
+
+    Walking the non-empty bins from the top down, with TP, FP the totals above bin b, p_b and n_b its positives and
+    negatives and P = sum p_b:  ``avg_prec`` = (1/P) sum_b p_b (TP + p_b) / (TP + FP + p_b + n_b), which is sklearn's
+    ``average_precision_score`` of the scores snapped to their bins (the ties of a bin are one threshold).  The average
+    precision of the unbinned scores lies in [``avg_prec_lo``, ``avg_prec_hi``], whatever the order and ties inside a bin:
+    hi = (1/P) sum_b p_b (TP + p_b) / (TP + FP + p_b) (no negative of the bin above any of its positives, and the
+    precision behind the i-th positive grows with i); lo = (1/P) sum_b [p_b - (FP + n_b) ln((T + p_b) / T)], T = TP + FP
+    + n_b, the term p_b where T = 0 (all negatives of the bin above its positives: sum_i (TP + i) / (T + i) = p_b -
+    (FP + n_b) sum_i 1 / (T + i), and the sum is below the integral of 1/x).  lo = hi = avg_prec where no negative lies
+    in or above a bin with positives.  Terms are divided in Python integers (correctly rounded) and added with
+    math.fsum: avg_prec and hi are within 2^-51 of their exact values, lo within 2^-49.  All NaN without positives.
+
+    ``precision`` / ``recall``: as sklearn's ``precision_recall_curve`` returns them for the snapped scores, one point per
+    non-empty bin in rising order of ``thresholds`` (the bins' lower edges e_j: ``score >= e_j``), then the end point
+    (1, 0)."""
+    import math
+    if key not in ('score', 'logit'):
+        raise ValueError(f"key must be 'score' or 'logit', got {key!r}")
+    if isinstance(hist, torch.Tensor):
+        hist = hist.detach().cpu().numpy()
+    hist = np.asarray(hist)
+    if hist.dtype.kind not in 'iu' or hist.ndim not in (2, 3) or hist.shape[-2] != 2:
+        raise ValueError(f'expected integer histograms (2, B) or (M, 2, B), got {hist.dtype} {hist.shape}')
+    hist = hist.astype(np.int64)
+    if hist.ndim == 3:
+        hist = hist.sum(axis=0)
+    B = hist.shape[1]
+    bits = B.bit_length() - 1
+    lo_bits, hi_bits = AP_BITS_RANGE if key == 'score' else ROC_BITS_RANGE
+    if B != 1 << bits or not lo_bits <= bits <= hi_bits or (hist < 0).any():
+        raise ValueError(f'expected non-negative counts in 2^{lo_bits}..2^{hi_bits} bins, got {B}')
+    neg, pos = hist[0], hist[1]
+    N, P = int(neg.sum()), int(pos.sum())
+    full = np.flatnonzero(neg + pos)  # the non-empty bins, rising
+    edges = (score_bin_edges if key == 'score' else roc_bin_edges)(bits)
+    thr = edges[full].astype(np.float64)
+    if not P:
+        nan = float('nan')
+        return dict(precision=np.full(full.size + 1, nan), recall=np.full(full.size + 1, nan), thresholds=thr,
+                    avg_prec=nan, avg_prec_lo=nan, avg_prec_hi=nan, p=P, n=N)
+    precision, recall = np.ones(full.size + 1), np.zeros(full.size + 1)
+    mid, low, high = [], [], []
+    TP = FP = 0
+    for i in range(full.size - 1, -1, -1):  # Python integers: a slide's p_b (TP + p_b) does not fit 64 bits
+        pb, nb = int(pos[full[i]]), int(neg[full[i]])
+        precision[i], recall[i] = (TP + pb) / (TP + FP + pb + nb), (TP + pb) / P
+        if pb:
+            T = TP + FP + nb
+            mid.append(pb * (TP + pb) / (T + pb))
+            high.append(pb * (TP + pb) / (TP + FP + pb))
+            low.append(pb - (FP + nb) * math.log1p(pb / T) if T else float(pb))
+        TP, FP = TP + pb, FP + nb
+    return dict(precision=precision, recall=recall, thresholds=thr, avg_prec=math.fsum(mid) / P,
+                avg_prec_lo=math.fsum(low) / P, avg_prec_hi=math.fsum(high) / P, p=P, n=N)
 
 
 # ---- object-level results: connected objects of the target, their boxes' cover, weighted counts (csrc/cae_seg_objects.hip)

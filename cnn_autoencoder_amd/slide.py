@@ -575,7 +575,7 @@ class SlideCoder:
     # ---- pipelined segmentation of compressed tiles ---------------------------------------------------------
     def segment_batches(self, payload_batches, h: int, w: int, seg_model, targets=None, threshold: float = 0.5,
                         threshold_on: str = 'scores', top_k: int = 5, scores: bool = False, keep_logits: bool = False,
-                        to_host: bool = False, roc_bits=None, extents=None, object_level: bool = False):
+                        to_host: bool = False, roc_bits=None, extents=None, object_level: bool = False, ap_bits=None):
         """Generator: for every list of chunk byte strings (the 16-byte '>QQ' tile size in front of the rANS payload, as
         ZarrArray.read_chunk_bytes returns and segmenters.segment_compressed takes them; tiles of h x w pixels) the
         prediction of the segmentation head ``seg_model`` (a JNet in eval mode), in order:
@@ -593,6 +593,11 @@ class SlideCoder:
         'object_roc_hist', the histogram over those pixels (segmenters.object_roc_histogram; stays on the device).
         ``extents`` then bound objects and boxes too.  All of it runs behind cae_seg_predict on the main stream, on the
         labels that are on the device already.
+        ``ap_bits`` (8..14; needs ``targets``): each result gains 'ap_hist' (2, 2^ap_bits) int64 for
+        segmenters.ap_from_histogram, counted inside ``extents`` and left on the device as 'roc_hist' is.  Several classes:
+        the micro histogram of the batch's softmax scores (segmenters.score_histogram); the scores are made on the device
+        for it whether or not ``scores`` asks to receive them.  One class: the logit histogram at ap_bits
+        (segmenters.roc_histogram, read with key='logit'), the tensor of 'roc_hist' itself where ap_bits == roc_bits.
 
         The stages of decompress_batches: a worker range-decodes up to `depth` batches ahead (host or device coder), the
         symbols cross on the H2D side stream; then, on the main stream, dequantiser, synthesis track with its bridges
@@ -602,7 +607,8 @@ class SlideCoder:
 
         ValueError before any work: seg_model in training mode, a head built for other latent channels than the
         codec's, a bad threshold / threshold_on / top_k, roc_bits without targets, for a head of several classes or
-        outside 8..14, object_level without targets, extents without roc_bits or object_level; and for every batch,
+        outside 8..14, ap_bits without targets or outside 8..14, object_level without targets, extents without roc_bits,
+        ap_bits or object_level; and for every batch,
         before it is handed to the decoder: a chunk whose header is not (h, w) -- chunks of mixed tile sizes."""
         from .codec import _module
         from . import segmenters
@@ -623,8 +629,16 @@ class SlideCoder:
             if seg._num_classes != 1:
                 raise ValueError(f'roc_bits needs a one-class head, this one has {seg._num_classes} classes')
             roc = segmenters._check_roc_bits(roc_bits)
-        elif extents is not None and not object_level:
-            raise ValueError('extents bound the ROC histograms and the object boxes: they need roc_bits or object_level')
+        ap = None
+        if ap_bits is not None:
+            if targets is None:
+                raise ValueError('ap_bits needs targets: the histograms are those of the labelled pixels')
+            if seg._num_classes > 255:
+                raise ValueError(f'ap_bits takes heads of up to 255 classes, this one has {seg._num_classes}')
+            ap = segmenters._check_ap_bits(ap_bits)
+        if extents is not None and roc is None and ap is None and not object_level:
+            raise ValueError('extents bound the histograms and the object boxes: they need roc_bits, ap_bits or '
+                             'object_level')
         if object_level:
             if targets is None:
                 raise ValueError('object_level needs targets: the objects are those of the label maps')
@@ -632,11 +646,11 @@ class SlideCoder:
         return self._segment_batches(payload_batches, int(h), int(w), seg, targets,
                                      dict(threshold=threshold, threshold_on=threshold_on, top_k=top_k, scores=scores),
                                      keep_logits, to_host, roc, iter(extents) if extents is not None else None,
-                                     bool(object_level))
+                                     bool(object_level), ap)
 
     @torch.no_grad()
     def _segment_batches(self, payload_batches, h, w, seg, targets, how, keep_logits, to_host, roc=None, extents=None,
-                         object_level=False):
+                         object_level=False, ap=None):
         import struct
         from concurrent.futures import ThreadPoolExecutor
         from . import _lib, segmenters
@@ -662,7 +676,7 @@ class SlideCoder:
             out = self._ring('c').take(k, tuple(cls.shape), torch.uint8)
             _lib.check(_lib.lib().cae_copy_to_host(out.data_ptr(), cls.data_ptr(), cls.numel()))
             # there to be summed: left on the device
-            stay = {key: res[key] for key in ('roc_hist', 'object_roc_hist') if key in res}
+            stay = {key: res[key] for key in ('roc_hist', 'object_roc_hist', 'ap_hist') if key in res}
             host = {key: None if v is None else v.cpu().numpy() for key, v in res.items() if key != 'cls' and key not in stay}
             _clock(tm, 'copy', t0)
             return dict(host, cls=out.numpy(), **stay)
@@ -691,12 +705,20 @@ class SlideCoder:
             t0 = time.perf_counter()
             if target is not None and not (isinstance(target, torch.Tensor) and target.is_cuda):
                 target = torch.as_tensor(np.ascontiguousarray(target)).to(main.device)
-            res = segmenters.predict(logits, target, **how)
+            several = ap is not None and seg._num_classes > 1  # the score histogram reads the scores of this call
+            res = segmenters.predict(logits, target, **dict(how, scores=how['scores'] or several))
             res['logits'] = logits if keep_logits else None
             if extent is not None:  # on the device once, for every call below
                 extent = segmenters._extent_arg(extent, n, main.device)
             if roc is not None:
                 res['roc_hist'] = segmenters.roc_histogram(logits, target, extent=extent, bits=roc)
+            if several:
+                res['ap_hist'] = segmenters.score_histogram(res['scores'], target, extent=extent, bits=ap)
+                if not how['scores']:
+                    res['scores'] = None
+            elif ap is not None:
+                res['ap_hist'] = res['roc_hist'] if ap == roc else segmenters.roc_histogram(logits, target, extent=extent,
+                                                                                            bits=ap)
             if object_level:
                 labels, res['n_objects'] = segmenters.components(target.reshape(n, h, w), extent=extent,
                                                                  by_value=seg._num_classes > 1)

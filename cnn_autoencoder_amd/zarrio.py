@@ -631,7 +631,7 @@ def decompress_image(input_filename: str, data_group: str = '0/0', checkpoint=No
 def segment_image(input_filename: str, seg_model, output_filename: str, data_group: str = '0/0', checkpoint=None,
                   target_group: Optional[str] = None, batch_tiles: int = 4, threshold: float = 0.5,
                   threshold_on: str = 'scores', top_k: int = 5, scores: bool = False, coder: str = 'host',
-                  roc_bits: Optional[int] = None, object_level: bool = False) -> Dict:
+                  roc_bits: Optional[int] = None, object_level: bool = False, ap_bits: Optional[int] = None) -> Dict:
     """The reference's segmentation harness on a compressed slide (test_cae_classifier.py:46-55 and its metrics), without
     decoding a pixel to the host: the chunk bytes of the 'cae'-coded array ``data_group`` of ``input_filename`` go through
     SlideCoder.segment_batches (range decoder on ``coder``, synthesis track, the head ``seg_model``, cae_seg_predict)
@@ -664,13 +664,20 @@ def segment_image(input_filename: str, seg_model, output_filename: str, data_gro
     object-level record plus 'n_objects' (the slide's sum), 'records' ((tiles, 6), all ranks) and, with ``roc_bits``,
     'auc', 'auc_slack' and 'roc'; rank 0 then writes object_level/fpr, tpr, thrsh and thrsh_logit as above.  An object cut
     by a tile border counts as two.
+    ``ap_bits`` (8..14, segmenters.AP_BITS = 14; needs a target): the slide's average precision, the reference's avg_prec
+    (utils/_metrics.py:90-92), from histograms of 2^ap_bits bins -- several classes: the micro histogram of the softmax
+    scores (segmenters.score_histogram); one class: the logit histogram -- over each tile's real pixels, summed on the
+    device, then over the ranks (SlideCoder.segment_batches(ap_bits=...), slide.reduce_histogram).  The result gains
+    'avg_prec', 'avg_prec_lo', 'avg_prec_hi' (the average precision of the unbinned scores lies between the last two) and
+    'pr' (segmenters.ap_from_histogram), and rank 0 writes image_level/precision, image_level/recall and
+    image_level/pr_thrsh (one threshold fewer than points; on the scores, or for one class on the logits) as above.
 
     A sparse store (compress_image with a mask; ``ZarrArray.is_sparse``): the chunks without a file are not run and get no
     class/0/0 or scores/0/0 chunk -- their fill 0 is the background class -- and the result gains 'skipped_tiles' (this
     rank's).  With a target the record of such a chunk is made on the host from its labels with the prediction "background
     everywhere": one class, tn = the count of target == 0 and fn = p = the count of target > 0; several classes, tp =
-    tp_top = the count of target == 0, fp = fn = pixels - tp, p = pixels.  ``roc_bits`` and ``object_level`` raise
-    ValueError there: a skipped chunk has no logit.  In any other store a missing chunk file raises ValueError.
+    tp_top = the count of target == 0, fp = fn = pixels - tp, p = pixels.  ``roc_bits``, ``ap_bits`` and ``object_level``
+    raise ValueError there: a skipped chunk has no logit.  In any other store a missing chunk file raises ValueError.
 
     -> segmenters.class_metrics of the slide's summed record, plus
     'records': the (tiles, 6) int64 per-tile records of all ranks in tile order (slide.gather_counts), 'tiles' and
@@ -706,9 +713,16 @@ def segment_image(input_filename: str, seg_model, output_filename: str, data_gro
         if tz is None or C != 1:
             raise ValueError('roc_bits needs a target_group and a one-class head')
         roc_bits = segmenters._check_roc_bits(roc_bits)
+    if ap_bits is not None:
+        if tz is None:
+            raise ValueError('ap_bits needs a target_group')
+        if C > 255:
+            raise ValueError(f'ap_bits takes heads of up to 255 classes, this one has {C}')
+        ap_bits = segmenters._check_ap_bits(ap_bits)
     sparse = z.is_sparse
-    if sparse and (roc_bits is not None or object_level):
-        raise ValueError('roc_bits and object_level are not available on a sparse store: a skipped chunk has no logit')
+    if sparse and (roc_bits is not None or ap_bits is not None or object_level):
+        raise ValueError('roc_bits, ap_bits and object_level are not available on a sparse store: a skipped chunk has '
+                         'no logit')
     sc = slide.SlideCoder(z.codec, coder=coder)
     zc = ZarrArray.create(output_filename, 'class/0/0', (H, W), (ph, pw), np.bool_ if C == 1 else np.uint8,
                           codec=Zlib(9), write_meta=rank == 0)
@@ -741,13 +755,13 @@ def segment_image(input_filename: str, seg_model, output_filename: str, data_gro
                                 targets=None if tz is None else (labels(g) for g in groups), threshold=threshold,
                                 threshold_on=threshold_on, top_k=top_k, scores=scores, to_host=True, roc_bits=roc_bits,
                                 extents=(np.array(s, dtype=np.int32).reshape(-1, 2) for s in sizes)
-                                if roc_bits is not None or object_level else None,
-                                object_level=bool(object_level))
+                                if roc_bits is not None or ap_bits is not None or object_level else None,
+                                object_level=bool(object_level), ap_bits=ap_bits)
     records, obj_records, obj_numbers = [], [], []
-    hists = {}  # 'roc_hist', 'object_roc_hist' -> this rank's sum, on the device
+    hists = {}  # 'roc_hist', 'object_roc_hist', 'ap_hist' -> this rank's sum, on the device
     # res['cls']: pinned ring buffer, written out before the generator advances
     for group, real, res in zip(groups, sizes, stream):
-        for key in ('roc_hist', 'object_roc_hist'):
+        for key in ('roc_hist', 'object_roc_hist', 'ap_hist'):
             if key in res:
                 hists[key] = res[key] + hists.get(key, 0)
         if object_level:
@@ -817,5 +831,15 @@ def segment_image(input_filename: str, seg_model, output_filename: str, data_gro
         out['object_level'] = obj
     if roc_bits is not None:
         curve('image_level', hists.get('roc_hist'), out)
+    if ap_bits is not None:
+        hist = hists.get('ap_hist')
+        if hist is None:  # a rank without tiles
+            hist = torch.zeros((2, 1 << ap_bits), dtype=torch.int64, device='cuda')
+        pr = segmenters.ap_from_histogram(slide.reduce_histogram(hist), key='score' if C > 1 else 'logit')
+        out.update(avg_prec=pr['avg_prec'], avg_prec_lo=pr['avg_prec_lo'], avg_prec_hi=pr['avg_prec_hi'], pr=pr)
+        for name, key in (('precision', 'precision'), ('recall', 'recall'), ('pr_thrsh', 'thresholds')):
+            v = pr[key].astype(np.float32)
+            if rank == 0 and v.size:  # (no labelled pixel at all: no threshold)
+                ZarrArray.create(output_filename, f'image_level/{name}', v.shape, v.shape, np.float32, codec=Zlib(9))[:] = v
     _barrier()
     return out

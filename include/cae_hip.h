@@ -884,6 +884,43 @@ int cae_seg_roc_hist(const float *logits_dev, const uint8_t *target_dev, const i
 size_t cae_seg_roc_workspace(int n, int h, int w, int bits);
 int cae_seg_roc_blocks(int n, int h, int w, int bits);
 
+/* ---- Score histograms of a head of several classes (csrc/cae_seg_ap.hip) --------------------------
+ * What the reference's avg_prec needs -- average_precision_score(one_hot_target, softmax_scores, average='micro')
+ * (utils/_metrics.py:90-92) -- without sorting a score: precision and recall at a threshold are fixed by how many
+ * positive and how many negative (pixel, class) pairs lie at or above it.
+ * scores_dev (n, c, h, w) fp32 contiguous, read as they stand in memory (any 4-byte aligned address): what
+ * cae_seg_predict wrote to scores_dev, or any values in [0, 1].  Nothing is recomputed: the histogram is an exact
+ * function of these bits.  target_dev (n, h, w) uint8 at any address; extent_dev as for cae_seg_roc_hist.
+ *   bin:   B = 2^bits, 8 <= bits <= 14, sh = 31 - bits, u(v) the bits of the float v.
+ *          NaN, -0 and s <= 0: bin 0.  0 < s < 0.5: u(s) >> sh.  0.5 <= s < 1: B - 1 - (u(1.0f - s) >> sh); the
+ *          subtraction is exact in fp32 (Sterbenz), so no rounding or denormal mode has a say.  s >= 1: B - 1.
+ *          u(0.5f) = 0x3F000000 < 2^30: the lower half ends at bin (0x3F000000 >> sh) - 1 and the upper begins at
+ *          B - 1 - (0x3F000000 >> sh); the bins between them stay empty.  Monotone non-decreasing in s, with relative
+ *          resolution near 0 and near 1: bin(s) >= j exactly when s >= e_j, the smallest score of bin j.
+ *   class: for class k the pair (pixel, k) is positive when target == k and negative otherwise.  A pixel whose target
+ *          is >= c is unlabelled: it is in no histogram, of no class.  Pixels outside the extent are in none either.
+ *   hist_dev int64 [n if per_image else 1][c if per_class else 1][2][2^bits], row 0 the negatives and row 1 the
+ *          positives.  The sum over the classes is the micro histogram (positives: the ones of the one-hot target).
+ *          Every entry is written, nothing is accumulated into what the buffer held; integers, exact in any order, and
+ *          they add across tiles, batches and ranks.
+ * From a histogram, walking the non-empty bins from the top down with TP, FP the totals above bin b, p_b and n_b its
+ * counts and P = sum p_b: avg_prec = (1 / P) sum_b p_b (TP + p_b) / (TP + FP + p_b + n_b) is the average precision of
+ * the scores snapped to their bins (the ties of a bin form one threshold), and that of the unbinned scores lies in
+ * [(1 / P) sum_b (p_b - (FP + n_b) ln((T + p_b) / T)), (1 / P) sum_b p_b (TP + p_b) / (TP + FP + p_b)], T = TP + FP + n_b
+ * (the term is p_b where T = 0), whatever the order and the ties inside a bin.
+ *
+ * Two launches, asynchronous on `stream`: blocks that count a contiguous span of one class plane in an LDS table of
+ * 2^(bits+3) bytes and store it as one partial per (plane, block) in workspace_dev (cae_seg_score_workspace bytes,
+ * 16-byte aligned), then the sum of the partials in a fixed order.  Each plane reads its image's target: 4 c + c bytes
+ * per pixel in all.  No global atomics, no floating-point atomics; neither histogram nor workspace needs initialising;
+ * results are bitwise repeatable.  CAE_ERR_ARG before any launch: bits outside 8..14, c outside 2..255, n, h or w < 1,
+ * planes of more than 2^31 - 1 pixels, a NULL or misaligned pointer, a workspace that is too small.
+ * cae_seg_score_workspace returns 0 for shapes cae_seg_score_hist refuses. */
+int cae_seg_score_hist(const float *scores_dev, const uint8_t *target_dev, const int32_t *extent_dev, int n, int c, int h,
+                       int w, int bits, int per_image, int per_class, int64_t *hist_dev, void *workspace_dev,
+                       size_t workspace_bytes, void *stream);
+size_t cae_seg_score_workspace(int n, int c, int h, int w, int bits);
+
 /* ---- Objects of a label plane (csrc/cae_seg_objects.hip) -----------------------------------------
  * The object-level half of the reference's harness (--compute-components-metrics, test_cae_classifier.py:97-157 and
  * 267-370): every connected object of the target gets a bounding box, and counts and ROC curve are taken over the pixels
