@@ -207,6 +207,7 @@ SYMBOLS = {
     'cae_tile_byte_hist': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
     'cae_tile_byte_hist_workspace': (c_size_t, [c_int, c_int, c_int, c_int]),
     'cae_tile_byte_hist_blocks': (c_int, [c_int, c_int, c_int, c_int]),
+    'cae_persistent_launch': (c_int, [c_int] * 5 + [ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(c_int)]),
     'cae_seg_set_weights': (c_int, [c_void_p, c_void_p, c_int, c_void_p]),
     'cae_seg_pack_dev': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p]),
     'cae_seg_conv2d_workspace': (c_size_t, [c_int] * 6),

@@ -7,6 +7,46 @@
 #include "cae_launch.hpp"
 #include "cae_kernels_f16.hpp"
 namespace cae {
+// Launch shape of the three persistent kernels of this file: what the kernel's loop counts (`tiles`), the grid on the
+// current device (`blocks`: one block per CU at the most, a block takes tiles b, b + blocks, ...) and the launch facts
+// of the kernel's tile.  The launchers and cae_persistent_launch (the tests) read it here and nowhere else.
+struct PersistentShape {
+    size_t tiles;
+    unsigned blocks;
+    LayerArgs args;  // the caller's arguments with tiles_x, tiles_y and cci filled in (gdn_f16_kernel: as given)
+};
+
+static int persistent_shape(const LayerArgs &b, size_t tiles, size_t tiles_per_block, PersistentShape &s) {
+    int n_cu = 0;
+    CAE_TRY(device_cus(n_cu));
+    if (tiles > 0x7fffffff) return fail(CAE_ERR_ARG, "batch too large");
+    s.tiles = tiles;
+    s.blocks = (unsigned)std::min<size_t>((tiles + tiles_per_block - 1) / tiles_per_block, (size_t)std::max(n_cu, 1));
+    s.args = b;
+    return CAE_OK;
+}
+
+// conv_first_f16_kernel: tiles of TX x TY output pixels (a.N, a.OH, a.OW), the same for every instantiation
+using FirstTile = FirstGeomF16<3, 1, false>;
+static int first_f16_shape(const LayerArgs &a, int cin, PersistentShape &s) {
+    const LayerArgs b = with_launch_facts(a, a.OW, a.OH, FirstTile::TX, FirstTile::TY, (cin + 7) / 8);
+    return persistent_shape(b, (size_t)b.N * b.tiles_x * b.tiles_y, 1, s);
+}
+
+// gdn_f16_kernel: every wave of a 4-wave block takes 32-pixel groups of the split rows (a.N, a.OH, a.OW)
+template <bool INVERSE>
+static int gdn_f16_shape(const LayerArgs &a, PersistentShape &s) {
+    const size_t groups = c8s_row_bytes<INVERSE>(a.OW) / 1024;
+    return persistent_shape(a, (size_t)a.N * a.OH * groups, 4, s);
+}
+
+// deconv_last_f16_kernel: tiles of TXC x NW input pixels (a.N, a.H, a.W), 32-channel contraction groups
+template <class G>
+static int last_f16_shape(const LayerArgs &a, int cin, PersistentShape &s) {
+    const LayerArgs b = with_launch_facts(a, a.W, a.H, G::TXC, G::NW, (cin + 31) / 32);
+    return persistent_shape(b, (size_t)b.N * b.tiles_x * b.tiles_y, 1, s);
+}
+
 template <int KS, int CT, bool GDN>
 static int launch_first_f16_t(const LayerArgs &a, const FirstArgs &f, hipStream_t st) {
     using G = FirstGeomF16<KS, CT, GDN>;
@@ -16,16 +56,12 @@ static int launch_first_f16_t(const LayerArgs &a, const FirstArgs &f, hipStream_
     } else {
         auto kern_u8 = conv_first_f16_kernel<KS, CT, GDN, true>;
         auto kern_f32 = conv_first_f16_kernel<KS, CT, GDN, false>;
-        int n_cu = 0;
+        static_assert(G::TX == FirstTile::TX && G::TY == FirstTile::TY, "one output tile for every instantiation");
         CAE_TRY(ensure_lds((const void *)kern_u8, LDS));
         CAE_TRY(ensure_lds((const void *)kern_f32, LDS));
-        CAE_TRY(device_cus(n_cu));
-        const LayerArgs b = with_launch_facts(a, a.OW, a.OH, G::TX, G::TY, (f.cin + 7) / 8);
-        const size_t total = (size_t)b.N * b.tiles_x * b.tiles_y;
-        if (total > 0x7fffffff) return fail(CAE_ERR_ARG, "batch too large");
-        // persistent: one block per CU walks over the tiles
-        const unsigned grid = (unsigned)std::min<size_t>(total, (size_t)std::max(n_cu, 1));
-        hipLaunchKernelGGL(f.in_is_u8 ? kern_u8 : kern_f32, dim3(grid), dim3(G::NW * 64), LDS, st, b, f);
+        PersistentShape s;  // persistent: one block per CU walks over the tiles
+        CAE_TRY(first_f16_shape(a, f.cin, s));
+        hipLaunchKernelGGL(f.in_is_u8 ? kern_u8 : kern_f32, dim3(s.blocks), dim3(G::NW * 64), LDS, st, s.args, f);
         HIP_TRY(hipGetLastError());
         return CAE_OK;
     }
@@ -53,14 +89,10 @@ static int launch_gdn_f16_t(const LayerArgs &a, hipStream_t st) {
     constexpr int LDS = CT * CT * 4096 + CT * 32 * 4;
     static_assert(LDS <= 160 * 1024, "packed gamma must fit the LDS");
     auto kern = gdn_f16_kernel<CT, INVERSE, INVERSE>;  // analysis rows are C8S, synthesis rows C8SP
-    int n_cu = 0;
     CAE_TRY(ensure_lds((const void *)kern, LDS));
-    CAE_TRY(device_cus(n_cu));
-    const size_t groups = c8s_row_bytes<INVERSE>(a.OW) / 1024;
-    const size_t total = (size_t)a.N * a.OH * groups;  // wave tiles of 32 pixels
-    if (total > 0x7fffffff) return fail(CAE_ERR_ARG, "batch too large");
-    const unsigned grid = (unsigned)std::min<size_t>((total + 3) / 4, (size_t)std::max(n_cu, 1));  // persistent
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), LDS, st, a);
+    PersistentShape s;  // persistent; wave tiles of 32 pixels
+    CAE_TRY((gdn_f16_shape<INVERSE>(a, s)));
+    hipLaunchKernelGGL(kern, dim3(s.blocks), dim3(256), LDS, st, s.args);
     HIP_TRY(hipGetLastError());
     return CAE_OK;
 }
@@ -85,18 +117,13 @@ bool last_f16_fits(int ks, int cin) {
 template <int KS, class G>
 static int launch_last_f16_t(int cin, const LayerArgs &a, hipStream_t st) {
     constexpr int NW = G::NW, DEPTH = G::DEPTH;
-    // tiles of TXC x NW input pixels, 32-channel contraction groups
-    const LayerArgs b = with_launch_facts(a, a.W, a.H, G::TXC, NW, (cin + 31) / 32);
-    const int lds = G::lds_bytes(b.cci);
+    const int lds = G::lds_bytes((cin + 31) / 32);
     if (lds > 160 * 1024) return fail(CAE_ERR_UNSUPPORTED, "last-layer weights do not fit the LDS");
     auto kern = deconv_last_f16_kernel<KS, NW, DEPTH>;
-    int n_cu = 0;
     CAE_TRY(ensure_lds((const void *)kern, 160 * 1024));
-    CAE_TRY(device_cus(n_cu));
-    const size_t total = (size_t)b.N * b.tiles_x * b.tiles_y;
-    if (total > 0x7fffffff) return fail(CAE_ERR_ARG, "batch too large");
-    const unsigned grid = (unsigned)std::min<size_t>(total, (size_t)std::max(n_cu, 1));  // persistent
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(NW * 64), lds, st, b);
+    PersistentShape s;  // persistent
+    CAE_TRY(last_f16_shape<G>(a, cin, s));
+    hipLaunchKernelGGL(kern, dim3(s.blocks), dim3(NW * 64), lds, st, s.args);
     HIP_TRY(hipGetLastError());
     return CAE_OK;
 }
@@ -108,3 +135,25 @@ int launch_last_f16(int ks, int cin, const LayerArgs &a, hipStream_t st) {
 }
 
 }  // namespace cae
+
+extern "C" int cae_persistent_launch(int kernel, int ks, int n, int h, int w, int64_t *tiles, int *blocks) {
+    using namespace cae;
+    if (kernel < 0 || kernel > 3 || n < 1 || h < 1 || w < 1 || !tiles || !blocks)
+        return fail(CAE_ERR_ARG, "cae_persistent_launch: bad arguments (kernel %d, n %d, h %d, w %d)", kernel, n, h, w);
+    if (kernel <= 1 && ks != 3 && ks != 5)
+        return fail(CAE_ERR_ARG, "cae_persistent_launch: kernel_size %d not supported (3 or 5)", ks);
+    LayerArgs a{};
+    a.N = n;
+    a.H = a.OH = h;
+    a.W = a.OW = w;
+    PersistentShape s;
+    switch (kernel) {
+        case 0: CAE_TRY(first_f16_shape(a, 1, s)); break;
+        case 1: CAE_TRY(ks == 3 ? last_f16_shape<LastF16K3>(a, 32, s) : last_f16_shape<LastF16K5>(a, 32, s)); break;
+        case 2: CAE_TRY(gdn_f16_shape<false>(a, s)); break;
+        default: CAE_TRY(gdn_f16_shape<true>(a, s)); break;
+    }
+    *tiles = (int64_t)s.tiles;
+    *blocks = (int)s.blocks;
+    return CAE_OK;
+}

@@ -277,6 +277,17 @@ int cae_tile_sse(const uint8_t *a_dev, const uint8_t *b_dev, int n, size_t elems
 int cae_model_set_profiling(cae_model_t *m, int enable);
 int cae_model_get_profile(cae_model_t *m, int track, double *ms, int n_slots, int *calls, int reset);
 
+/* Launch shape of the persistent kernels of the f16x3 path on the current device (read-only, for the tests; the
+ * launchers compute their grids with the same functions).  kernel: 0 conv_first_f16_kernel, 1 deconv_last_f16_kernel,
+ * 2 gdn_f16_kernel on analysis rows (GDN), 3 on synthesis rows (IGDN: the row groups pair even and odd pixels of
+ * 64-pixel blocks).  ks: kernel size, 3 or 5, of kernels 0 and 1 (ignored for the others).  n samples of the h x w
+ * extent the launcher tiles: the output of the first layer and of the normalisation, the input of the last layer.
+ * tiles: what the kernel's loop counts -- tiles of the first and the last layer, 32-pixel wave groups of the
+ * normalisation (four per block and turn).  blocks: the grid; block b takes tiles b, b + blocks, ... (the
+ * normalisation: wave v of block b groups 4 b + v, 4 b + v + 4 blocks, ...).  CAE_ERR_ARG: an unknown kernel, another
+ * ks, n, h or w < 1, a NULL pointer, more than 2^31 - 1 tiles. */
+int cae_persistent_launch(int kernel, int ks, int n, int h, int w, int64_t *tiles, int *blocks);
+
 /* ---- training (BASELINE config 5: bf16 convolutions, fp32 GDN) ----------------------------
  * What `loss.backward()` (train_cae_ms.py:214) differentiates on the reference: nn.Conv2d(reflect, stride 2) /
  * nn.ConvTranspose2d(stride 2, output_padding 1) (_autoencoders.py:78-85, :204-211) and compressai GDN / IGDN (:29-30).

@@ -24,10 +24,10 @@ PRECISIONS = ['fp32', 'f16x3']
 
 
 # ----------------------------------------------------------------------------------------------------- judge (CPU)
-def _emulate_f16x3_conv(x, w, b, k, seed, mutate=None):
+def _emulate_f16x3_conv(x, w, b, k, seed, mutate=None, tile=(slice(0, 16), slice(0, 16), slice(0, 32))):
     """one f16x3 strided reflect convolution as the kernel computes it: split operands, three f16 products per term
     (exact in fp32), fp32 accumulation in 16-term steps in a shuffled order, bias in the epilogue; `mutate` plants
-    one defect"""
+    one defect (`tile`: the output rows, columns and channels of 'drop_al_bh_on_one_tile')"""
     P = k // 2
     xh, xl = (t.float().numpy() for t in R.split(x))
     wh, wl = (t.float().numpy() for t in R.split(w))
@@ -51,7 +51,7 @@ def _emulate_f16x3_conv(x, w, b, k, seed, mutate=None):
         terms = np.concatenate([ch[..., None, :] * Wh, ch[..., None, :] * Wl, cl[..., None, :] * Wh], -1)
         if mutate == 'drop_al_bh_on_one_tile':  # the xl * wh products of output tile (32 channels, 16 x 16 pixels)
             kk = Wh.shape[1]
-            terms[:, :16, :16, :32, 2 * kk:] = 0.0
+            terms[:, tile[0], tile[1], tile[2], 2 * kk:] = 0.0
         perm = np.random.default_rng(seed).permutation(terms.shape[-1])
         terms = terms[..., perm]
         acc = np.zeros(terms.shape[:-1], np.float32)
