@@ -20,6 +20,7 @@ constexpr int kBins = 256;                // bins of the histogram; one lane of 
 constexpr uint32_t kFold = 16384;         // pixels a block adds into its 32-bit LDS bins before it folds them away
 constexpr size_t kHistPerBlock = 65536;   // pixels per block of the histogram below the cap: four folds
 constexpr int kHistBlocksTarget = 1024;
+constexpr int kSumBits = 7;               // launch_seg_histsum sums tables of 2 << bits words
 constexpr int kMaxFactor = 64;            // 64 x 64 x 255 stays far below 2^32
 
 __device__ __forceinline__ bool aligned_to(const void *p, unsigned mask) {
@@ -145,13 +146,6 @@ __global__ __launch_bounds__(kThreads) void mask_hist_kernel(const double *gray,
         __syncthreads();
     }
     partial[(size_t)blockIdx.x * kBins + tid] = mine;  // every (plane, block) writes its partial, work or not
-}
-
-__global__ __launch_bounds__(kBins) void mask_hist_sum_kernel(const unsigned long long *partial, int bx, long long *counts) {
-    const int n = blockIdx.x, tid = threadIdx.x;
-    unsigned long long s = 0;
-    for (int b = 0; b < bx; ++b) s += partial[((size_t)n * bx + b) * kBins + tid];
-    counts[(size_t)n * kBins + tid] = (long long)s;
 }
 
 // ---- 16 pixels of a uint8 plane from 16 elements of T ---------------------------------------------------------------
@@ -379,9 +373,8 @@ extern "C" int cae_mask_hist(const double *gray, const double *edges, int n, siz
     const int bx = hist_blocks(n, hw);
     hipLaunchKernelGGL(mask_hist_kernel, dim3((unsigned)((size_t)n * bx)), dim3(kThreads), 0, st, gray, edges, partial, hw, bx);
     HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(mask_hist_sum_kernel, dim3((unsigned)n), dim3(kBins), 0, st, partial, bx, reinterpret_cast<long long *>(counts));
-    HIP_TRY(hipGetLastError());
-    return CAE_OK;
+    // the partials of a plane summed in a fixed order (seg_histsum_kernel, cae_seg_merge.hip: 256 words are the table of "7 bits")
+    return launch_seg_histsum(partial, n, bx, 1, kSumBits, reinterpret_cast<long long *>(counts), st);
 }
 
 extern "C" int cae_mask_threshold(const double *gray, const double *thr, int n, size_t hw, uint8_t *out, void *stream) {

@@ -1,7 +1,8 @@
-// The steps that the slide metrics share (cae_seg_predict.hip, cae_seg_roc.hip, cae_seg_ap.hip, cae_seg_objects.hip): one
-// text each for the per-pixel decisions, the block tally, the histogram add, the counted extent, the aligned head, the grid
-// policy, the shape and bits checks, and the launchers of the two merge kernels (cae_seg_merge.hip).  The key and bin of a
-// logit: cae_seg_roc_key.hpp; the bin of a score: cae_seg_score_bin.hpp.
+// The steps that the slide metrics share (cae_seg_predict.hip, cae_seg_hist.hip, cae_seg_objects.hip, cae_tiles.hip,
+// cae_mask.hip): one text each for the per-pixel decisions, the block tally, the histogram add, the counted extent, the
+// grid policy, the shape and bits checks, and the launchers of the two merge kernels (cae_seg_merge.hip).  The span a
+// block of a plane histogram takes: cae_seg_span.hpp.  The key and bin of a logit: cae_seg_roc_key.hpp; the bin of a
+// score: cae_seg_score_bin.hpp.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -10,6 +11,7 @@
 #include <cstdint>
 
 #include "cae_launch.hpp"
+#include "cae_seg_span.hpp"
 
 namespace cae {
 
@@ -68,22 +70,26 @@ __device__ __forceinline__ void extent_of(const int32_t *extent, int n, int h, i
 }
 
 // floats in front of the first 16-byte aligned address at or behind p (p 4-byte aligned)
-__device__ __forceinline__ size_t aligned_head(const float *p) {
-    return (size_t)((0 - (reinterpret_cast<uintptr_t>(p) >> 2)) & 3);
-}
+__device__ __forceinline__ size_t aligned_head(const float *p) { return span_head<4>(span_offset<4>(p)); }
 
-// one pixel per lane into a block's LDS histogram, `word` its counter.  Lanes of a wave that hit the first active lane's
-// word add once, by their number: a slide's background puts most of a wave on one or two words, and 64 adds to one LDS
-// word take 64 turns
+// `EACH` counts from every lane that is `on` into a block's LDS histogram, `word` the lane's counter.  LEADS times over,
+// the lanes of a wave that hold the word of the first waiting lane add once, by their number, before the rest add on
+// their own: a slide's background puts most of a wave on one or two words, and 64 adds to one LDS word take 64 turns
+template <uint32_t EACH, int LEADS>
 __device__ __forceinline__ void hist_add(uint32_t *hist, bool on, uint32_t word) {
-    if (on) {
-        const uint32_t lead = __builtin_amdgcn_readfirstlane(word);
-        const unsigned long long same = __ballot(word == lead);  // the lanes of this branch only; the first is among them
-        if (word != lead)
-            atomicAdd(&hist[word], 1u);
-        else if ((int)(threadIdx.x & 63) == __ffsll((long long)same) - 1)
-            atomicAdd(&hist[lead], (uint32_t)__popcll(same));
+#pragma unroll
+    for (int r = 0; r < LEADS; ++r) {
+        if (on) {
+            const uint32_t lead = __builtin_amdgcn_readfirstlane(word);
+            const unsigned long long same = __ballot(word == lead);  // the lanes of this branch only; the first is among them
+            if (word == lead) {
+                if ((int)(threadIdx.x & 63) == __ffsll((long long)same) - 1)
+                    atomicAdd(&hist[lead], EACH * (uint32_t)__popcll(same));
+                on = false;
+            }
+        }
     }
+    if (on) atomicAdd(&hist[word], EACH);
 }
 
 // a lane's tallies.  W = unsigned where every pixel adds 1 (a lane sees hw / (256 bx) + 7 pixels and hw floats fit the

@@ -4,12 +4,13 @@
 //
 // First launch: a block takes a contiguous span of one tile's counted bytes, keeps a private uint32 [256] table in LDS,
 // counts with LDS integer adds and stores the table as one partial [tile][block][256] in the workspace, work or not.
-// Loads as roc_hist_kernel: 16-byte loads behind the tile's first aligned address, the (at most 30) bytes in front of it
-// and behind the last whole group one per lane (block 0 of the tile); the next group is in flight while the lane counts
-// the one it holds.  The input this exists for is the worst case of an LDS histogram -- a background tile puts almost
-// every byte on two or three values, and 64 adds to one LDS word take 64 turns -- so lanes combine before they add:
-// a lane whose 16 bytes are one value adds 16 once, and in both kinds of add the lanes of a wave that hold the value of
-// the first waiting lane add once, by their number, kLeads times over before the rest add on their own.  Second
+// The span is that of roc_hist_kernel with 16 elements per group (cae_seg_span.hpp): 16-byte loads behind the tile's
+// first aligned address, the (at most 30) bytes in front of it and behind the last whole group one per lane (block 0 of
+// the tile); the next group is in flight while the lane counts the one it holds.  The input this exists for is the worst
+// case of an LDS histogram -- a background tile puts almost every byte on two or three values, and 64 adds to one LDS
+// word take 64 turns -- so lanes combine before they add: a lane whose 16 bytes are one value adds 16 once, and in both
+// kinds of add the lanes of a wave that hold the value of the first waiting lane add once, by their number, kLeads
+// times over before the rest add on their own (hist_add, cae_seg_metrics.hpp).  Second
 // launch: the partials of a tile summed into int64 in a fixed order (seg_histsum_kernel, cae_seg_merge.hip, as it
 // stands: 256 words are the table of "7 bits").  No global atomics, nothing to initialise.
 #include "cae_seg_metrics.hpp"
@@ -32,26 +33,9 @@ struct TileArgs {
     int h, w, c, bx;
 };
 
-// `each` counts of value v from every lane that is `on`
-template <uint32_t EACH>
-__device__ __forceinline__ void tile_add(uint32_t *hist, bool on, uint32_t v) {
-#pragma unroll
-    for (int r = 0; r < kLeads; ++r) {
-        if (on) {
-            const uint32_t lead = __builtin_amdgcn_readfirstlane(v);
-            const unsigned long long same = __ballot(v == lead);  // the lanes of this branch only; the first is among them
-            if (v == lead) {
-                if ((int)(threadIdx.x & 63) == __ffsll((long long)same) - 1)
-                    atomicAdd(&hist[lead], EACH * (uint32_t)__popcll(same));
-                on = false;
-            }
-        }
-    }
-    if (on) atomicAdd(&hist[v], EACH);
-}
-
 __global__ __launch_bounds__(kThreads) void tile_byte_hist_kernel(TileArgs a) {
     static_assert(kThreads == kBins, "one lane per bin");
+    static_assert(kThreads >= 2 * (16 - 1), "a lane per single");
     __shared__ uint32_t hist[kBins];
     const int n = blockIdx.x / a.bx, x = blockIdx.x % a.bx, tid = threadIdx.x;
     hist[tid] = 0;
@@ -60,48 +44,39 @@ __global__ __launch_bounds__(kThreads) void tile_byte_hist_kernel(TileArgs a) {
     int rows, cols;
     extent_of(a.extent, n, a.h, a.w, rows, cols);
     const size_t rowbytes = a.rowbytes, colbytes = (size_t)cols * a.c;
-    const size_t lim = cols > 0 ? (size_t)rows * rowbytes : 0;  // whole rows beyond `rows` are never loaded
-    const bool ragged = cols < a.w;                             // columns beyond `cols` are loaded and left out
     const uint8_t *tl = a.tiles + (size_t)n * a.hwc;
 
     // bytes [head, tail) in groups of 16 behind 16-byte aligned addresses; the (at most 30) others one per lane
-    const size_t head = std::min(lim, (size_t)((0 - reinterpret_cast<uintptr_t>(tl)) & 15));
-    const size_t groups = (lim - head) / 16;
-    const size_t per_block = (groups + a.bx - 1) / a.bx;
-    const size_t g0 = std::min(groups, (size_t)x * per_block), g1 = std::min(groups, g0 + per_block);
-    constexpr size_t step = 16 * (size_t)kThreads;
-    const size_t dcol = step % rowbytes;
-    size_t g = g0 + tid;
-    size_t col = ragged && g < g1 ? (head + 16 * g) % rowbytes : 0;  // place in its row of the group's first byte
+    const Span<16> s = span_of<16>(span_offset<16>(tl), rowbytes, (size_t)rows, colbytes, (size_t)a.bx, (size_t)x, kThreads);
+    size_t g = s.g0 + tid;
+    size_t col = s.first_col(tid);  // place in its row of the group's first byte
     uint4 q = make_uint4(0, 0, 0, 0);
-    if (g < g1) q = *reinterpret_cast<const uint4 *>(tl + head + 16 * g);  // + 15 < head + 16 groups <= lim <= hwc
-    while (g < g1) {
+    if (g < s.g1) q = *reinterpret_cast<const uint4 *>(tl + s.head + 16 * g);  // + 15 < head + 16 groups <= lim <= hwc
+    while (g < s.g1) {
         const size_t next = g + kThreads;
         uint4 q_next = make_uint4(0, 0, 0, 0);
-        if (next < g1) q_next = *reinterpret_cast<const uint4 *>(tl + head + 16 * next);
+        if (next < s.g1) q_next = *reinterpret_cast<const uint4 *>(tl + s.head + 16 * next);
         const uint32_t word[4] = {q.x, q.y, q.z, q.w};
         const uint32_t v0 = q.x & 255u;
         // all 16 bytes counted and of one value: one add of 16
         const bool flat = q.x == v0 * 0x01010101u && q.y == q.x && q.z == q.x && q.w == q.x &&
-                          (!ragged || col + 16 <= colbytes);
-        tile_add<16>(hist, flat, v0);
+                          (!s.ragged || col + 16 <= colbytes);
+        hist_add<16, kLeads>(hist, flat, v0);
         if (!flat) {
             size_t c = col;
 #pragma unroll
             for (int j = 0; j < 16; ++j) {
-                tile_add<1>(hist, !ragged || c < colbytes, (word[j / 4] >> (8 * (j % 4))) & 255u);
+                hist_add<1, kLeads>(hist, s.on(c), (word[j / 4] >> (8 * (j % 4))) & 255u);
                 if (++c == rowbytes) c = 0;
             }
         }
-        col += dcol;
-        if (col >= rowbytes) col -= rowbytes;
+        s.turn(col);
         q = q_next;
         g = next;
     }
-    const size_t tail = head + 16 * groups, singles = head + (lim - tail);
-    if (x == 0 && (size_t)tid < singles) {
-        const size_t p = (size_t)tid < head ? (size_t)tid : tail + ((size_t)tid - head);  // < lim
-        tile_add<1>(hist, !ragged || p % rowbytes < colbytes, tl[p]);
+    if ((size_t)tid < s.singles) {
+        const size_t p = s.single(tid);  // < lim
+        hist_add<1, kLeads>(hist, s.on(p % rowbytes), tl[p]);
     }
     __syncthreads();
     a.partial[(size_t)blockIdx.x * kBins + tid] = hist[tid];  // every (tile, block) stores its whole table

@@ -16,9 +16,9 @@ The head's structure is stated once, in the library (``cae_seg_plan``); ``JNet.s
 ``predict`` / ``class_metrics`` turn logits into what the reference's harness hands out (class map, scores, counts and
 metrics; ``cae_seg_predict``, csrc/cae_seg_predict.hip); ``slide.SlideCoder.segment_batches`` and ``zarrio.segment_image``
 run whole slides through codec, head and prediction.  ``roc_histogram`` / ``roc_from_histogram`` give the threshold-free
-results of a one-class head, ROC curve and AUC, from exact logit histograms (``cae_seg_roc_hist``, csrc/cae_seg_roc.hip).
+results of a one-class head, ROC curve and AUC, from exact logit histograms (``cae_seg_roc_hist``, csrc/cae_seg_hist.hip).
 ``score_histogram`` / ``ap_from_histogram`` give the average precision of a head of several classes, with bounds on that of
-the unbinned scores, from exact histograms of the softmax scores (``cae_seg_score_hist``, csrc/cae_seg_ap.hip).
+the unbinned scores, from exact histograms of the softmax scores (``cae_seg_score_hist``, csrc/cae_seg_hist.hip).
 ``components`` / ``object_cover`` / ``object_counts`` / ``object_roc_histogram`` give the object-level half of the harness:
 connected objects of the target, their boxes, and counts and histogram over the pixels of all boxes (csrc/cae_seg_objects.hip).
 
@@ -515,15 +515,38 @@ def class_metrics(counts, multiclass: bool = False) -> Dict:
                 prec=ratio(tp, tp + fp), rec=ratio(tp, tp + fn), f1=ratio(2 * tp, 2 * tp + fp + fn))
 
 
-# ---- threshold-free results of a one-class head: ROC curve and AUC from logit histograms (csrc/cae_seg_roc.hip) -------
+# ---- threshold-free results of a one-class head: ROC curve and AUC from logit histograms (csrc/cae_seg_hist.hip) ------
 ROC_BITS = 14          # bins of the slide histograms: 2^14 per class, the most cae_seg_roc_hist takes
 ROC_BITS_RANGE = (8, 14)
 
 
-def _check_roc_bits(bits) -> int:
-    if isinstance(bits, bool) or int(bits) != bits or not ROC_BITS_RANGE[0] <= int(bits) <= ROC_BITS_RANGE[1]:
-        raise ValueError(f'roc bits must be an integer in {ROC_BITS_RANGE[0]}..{ROC_BITS_RANGE[1]}, got {bits!r}')
+def _check_bits(bits, what: str, bits_range) -> int:
+    if isinstance(bits, bool) or int(bits) != bits or not bits_range[0] <= int(bits) <= bits_range[1]:
+        raise ValueError(f'{what} bits must be an integer in {bits_range[0]}..{bits_range[1]}, got {bits!r}')
     return int(bits)
+
+
+def _check_roc_bits(bits) -> int:
+    return _check_bits(bits, 'roc', ROC_BITS_RANGE)
+
+
+def _histogram_arg(hist, bits_range):
+    """One integer histogram (2, B), or an (M, 2, B) array of them, which is summed; B a power of two in range, no
+    negative count -> (neg, pos, N, P, bits)"""
+    if isinstance(hist, torch.Tensor):
+        hist = hist.detach().cpu().numpy()
+    hist = np.asarray(hist)
+    if hist.dtype.kind not in 'iu' or hist.ndim not in (2, 3) or hist.shape[-2] != 2:
+        raise ValueError(f'expected integer histograms (2, B) or (M, 2, B), got {hist.dtype} {hist.shape}')
+    hist = hist.astype(np.int64)
+    if hist.ndim == 3:
+        hist = hist.sum(axis=0)
+    B = hist.shape[1]
+    bits = B.bit_length() - 1
+    if B != 1 << bits or not bits_range[0] <= bits <= bits_range[1] or (hist < 0).any():
+        raise ValueError(f'expected non-negative counts in 2^{bits_range[0]}..2^{bits_range[1]} bins, got {B}')
+    neg, pos = hist[0], hist[1]
+    return neg, pos, int(neg.sum()), int(pos.sum()), bits
 
 
 def roc_bin_edges(bits: int = ROC_BITS) -> np.ndarray:
@@ -590,20 +613,7 @@ def roc_from_histogram(hist) -> Dict:
     ``auc``: the trapezoid area under that curve, sum_b pos_b (2 neg_below_b + neg_b) / (2 P N) in Python integers with one
     division; the AUC of the unbinned logits lies inside auc +- ``auc_slack`` = sum_b pos_b neg_b / (2 P N).  Both are NaN
     without positives (the reference's rule, _metrics.py:128-131) or without negatives; fpr / tpr are then NaN too."""
-    if isinstance(hist, torch.Tensor):
-        hist = hist.detach().cpu().numpy()
-    hist = np.asarray(hist)
-    if hist.dtype.kind not in 'iu' or hist.ndim not in (2, 3) or hist.shape[-2] != 2:
-        raise ValueError(f'expected integer histograms (2, B) or (M, 2, B), got {hist.dtype} {hist.shape}')
-    hist = hist.astype(np.int64)
-    if hist.ndim == 3:
-        hist = hist.sum(axis=0)
-    B = hist.shape[1]
-    bits = B.bit_length() - 1
-    if B != 1 << bits or not ROC_BITS_RANGE[0] <= bits <= ROC_BITS_RANGE[1] or (hist < 0).any():
-        raise ValueError(f'expected non-negative counts in 2^{ROC_BITS_RANGE[0]}..2^{ROC_BITS_RANGE[1]} bins, got {B}')
-    neg, pos = hist[0], hist[1]
-    N, P = int(neg.sum()), int(pos.sum())
+    neg, pos, N, P, bits = _histogram_arg(hist, ROC_BITS_RANGE)
     full = np.flatnonzero(neg + pos)[::-1]  # the non-empty bins from the top down
     with np.errstate(invalid='ignore', divide='ignore', over='ignore'):
         fpr = np.concatenate(([0.0], np.cumsum(neg[full]) / np.float64(N))) if N else np.full(full.size + 1, np.nan)
@@ -622,15 +632,13 @@ def roc_from_histogram(hist) -> Dict:
     return dict(fpr=fpr, tpr=tpr, thresholds=thr, score_thresholds=score_thr, auc=auc, auc_slack=slack, p=P, n=N)
 
 
-# ---- average precision from score histograms (csrc/cae_seg_ap.hip); a one-class head's from its ROC histogram --------
+# ---- average precision from score histograms (csrc/cae_seg_hist.hip); a one-class head's from its ROC histogram ------
 AP_BITS = 14           # bins of the slide histograms: 2^14 per row, the most cae_seg_score_hist takes
 AP_BITS_RANGE = (8, 14)
 
 
 def _check_ap_bits(bits) -> int:
-    if isinstance(bits, bool) or int(bits) != bits or not AP_BITS_RANGE[0] <= int(bits) <= AP_BITS_RANGE[1]:
-        raise ValueError(f'ap bits must be an integer in {AP_BITS_RANGE[0]}..{AP_BITS_RANGE[1]}, got {bits!r}')
-    return int(bits)
+    return _check_bits(bits, 'ap', AP_BITS_RANGE)
 
 
 def score_bin_edges(bits: int = AP_BITS) -> np.ndarray:
@@ -723,21 +731,7 @@ def ap_from_histogram(hist, key: str = 'score') -> Dict:
     import math
     if key not in ('score', 'logit'):
         raise ValueError(f"key must be 'score' or 'logit', got {key!r}")
-    if isinstance(hist, torch.Tensor):
-        hist = hist.detach().cpu().numpy()
-    hist = np.asarray(hist)
-    if hist.dtype.kind not in 'iu' or hist.ndim not in (2, 3) or hist.shape[-2] != 2:
-        raise ValueError(f'expected integer histograms (2, B) or (M, 2, B), got {hist.dtype} {hist.shape}')
-    hist = hist.astype(np.int64)
-    if hist.ndim == 3:
-        hist = hist.sum(axis=0)
-    B = hist.shape[1]
-    bits = B.bit_length() - 1
-    lo_bits, hi_bits = AP_BITS_RANGE if key == 'score' else ROC_BITS_RANGE
-    if B != 1 << bits or not lo_bits <= bits <= hi_bits or (hist < 0).any():
-        raise ValueError(f'expected non-negative counts in 2^{lo_bits}..2^{hi_bits} bins, got {B}')
-    neg, pos = hist[0], hist[1]
-    N, P = int(neg.sum()), int(pos.sum())
+    neg, pos, N, P, bits = _histogram_arg(hist, AP_BITS_RANGE if key == 'score' else ROC_BITS_RANGE)
     full = np.flatnonzero(neg + pos)  # the non-empty bins, rising
     edges = (score_bin_edges if key == 'score' else roc_bin_edges)(bits)
     thr = edges[full].astype(np.float64)
@@ -770,6 +764,19 @@ def _check_planes(n: int, h: int, w: int):
                          f'(3 min(H, W) <= 65535) and a label in 32')
 
 
+def _planes_arg(planes, dtype, what: str, check=_check_planes):
+    """a tensor of this dtype, (N,H,W), on the device; its shape is judged (``check``) before a device is asked for
+    -> (n, h, w)"""
+    if not isinstance(planes, torch.Tensor) or planes.dim() != 3 or planes.dtype != dtype:
+        raise ValueError(f'expected {what} (N,H,W) on the device')
+    n, h, w = planes.shape
+    check(n, h, w)
+    _lib.require_gpu()
+    if not planes.is_cuda:
+        raise ValueError(f'expected {what} (N,H,W) on the device')
+    return n, h, w
+
+
 def _extent_arg(extent, n: int, dev):
     """(N,2) integers (rows, cols), on the device as the int32 the library reads (clamped there to the plane), or None"""
     if extent is None:
@@ -789,13 +796,7 @@ def components(target: torch.Tensor, extent=None, by_value: bool = False):
     ``by_value`` neighbours join only when their values are equal (skimage.measure.label of an integer image), otherwise
     all foreground counts as one value (the reference's one-class case).  A label is 0 on background, else 1 + the
     smallest row-major index of its object; objects never reach across planes."""
-    if not isinstance(target, torch.Tensor) or target.dim() != 3 or target.dtype != torch.uint8:
-        raise ValueError('expected uint8 label planes (N,H,W) on the device')
-    n, h, w = target.shape
-    _check_planes(n, h, w)
-    _lib.require_gpu()
-    if not target.is_cuda:
-        raise ValueError('expected uint8 label planes (N,H,W) on the device')
+    n, h, w = _planes_arg(target, torch.uint8, 'uint8 label planes')
     dev = target.device
     ext = _extent_arg(extent, n, dev)
     tgt = target.contiguous()  # (a view of a larger buffer at any byte offset is read in place)
@@ -817,13 +818,7 @@ def object_cover(labels: torch.Tensor, extent=None) -> torch.Tensor:
     is its rows and columns widened by one pixel on every side, clipped to the extent (test_cae_classifier.py:101-109).
     The reference concatenates the pixels of all boxes, so its object-level sums are the image-level sums weighted by
     this cover."""
-    if not isinstance(labels, torch.Tensor) or labels.dim() != 3 or labels.dtype != torch.int32:
-        raise ValueError('expected int32 labels (N,H,W) on the device')
-    n, h, w = labels.shape
-    _check_planes(n, h, w)
-    _lib.require_gpu()
-    if not labels.is_cuda:
-        raise ValueError('expected int32 labels (N,H,W) on the device')
+    n, h, w = _planes_arg(labels, torch.int32, 'int32 labels')
     dev = labels.device
     ext = _extent_arg(extent, n, dev)
     lab = labels.contiguous()
@@ -840,6 +835,14 @@ def object_cover(labels: torch.Tensor, extent=None) -> torch.Tensor:
 MAX_DISTANCE_EDGE = 32768  # cae_seg_object_distances: 2 (edge - 1)^2 stays below 2^31 - 1
 
 
+def _check_distance_planes(n: int, h: int, w: int):
+    if n and (h < 1 or w < 1):
+        raise ValueError(f'empty planes: {n} x {h} x {w}')
+    if max(h, w) > MAX_DISTANCE_EDGE or h * w > 2 ** 31 - 1:
+        raise ValueError(f'planes of {h} x {w} pixels are too large: a squared distance is held in 32 bits '
+                         f'(H, W <= {MAX_DISTANCE_EDGE}, H W <= 2^31 - 1)')
+
+
 @torch.no_grad()
 def object_distances(labels: torch.Tensor) -> torch.Tensor:
     """labels (N,H,W) int32 of ``components`` (0 is background; only that the labels of two objects differ matters) ->
@@ -847,17 +850,7 @@ def object_distances(labels: torch.Tensor) -> torch.Tensor:
     Euclidean distance to the nearest foreground pixel (0 on foreground), plane 1 the smallest squared distance to a
     pixel of another object than the one that gives plane 0; -1 where there is no such object.  Exact integers, the
     distances of the reference's ``WeightsDistances`` (one distance transform per object there, two passes here)."""
-    if not isinstance(labels, torch.Tensor) or labels.dim() != 3 or labels.dtype != torch.int32:
-        raise ValueError('expected int32 labels (N,H,W) on the device')
-    n, h, w = labels.shape
-    if n and (h < 1 or w < 1):
-        raise ValueError(f'empty planes: {n} x {h} x {w}')
-    if max(h, w) > MAX_DISTANCE_EDGE or h * w > 2 ** 31 - 1:
-        raise ValueError(f'planes of {h} x {w} pixels are too large: a squared distance is held in 32 bits '
-                         f'(H, W <= {MAX_DISTANCE_EDGE}, H W <= 2^31 - 1)')
-    _lib.require_gpu()
-    if not labels.is_cuda:
-        raise ValueError('expected int32 labels (N,H,W) on the device')
+    n, h, w = _planes_arg(labels, torch.int32, 'int32 labels', _check_distance_planes)
     dev = labels.device
     lab = labels.contiguous()
     with torch.cuda.device(dev):

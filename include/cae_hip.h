@@ -861,7 +861,7 @@ int cae_seg_predict(const float *logits_dev, const uint8_t *target_dev, int n, i
                     size_t workspace_bytes, void *stream);
 size_t cae_seg_predict_workspace(int n, int c, size_t hw);
 
-/* ---- ROC histograms of a one-class head (csrc/cae_seg_roc.hip) -----------------------------------
+/* ---- ROC histograms of a one-class head (csrc/cae_seg_hist.hip) ----------------------------------
  * The threshold-free results of the reference's harness -- the per-image auc (utils/_metrics.py:128-131), the
  * slide-level ROC curve and its AUC (test_cae_classifier.py:233-264, 356-364) -- without sorting a score: the
  * prediction is logit > t, so the curve is fixed by how many positive and how many negative pixels lie at or above each
@@ -895,7 +895,7 @@ int cae_seg_roc_hist(const float *logits_dev, const uint8_t *target_dev, const i
 size_t cae_seg_roc_workspace(int n, int h, int w, int bits);
 int cae_seg_roc_blocks(int n, int h, int w, int bits);
 
-/* ---- Score histograms of a head of several classes (csrc/cae_seg_ap.hip) --------------------------
+/* ---- Score histograms of a head of several classes (csrc/cae_seg_hist.hip) ------------------------
  * What the reference's avg_prec needs -- average_precision_score(one_hot_target, softmax_scores, average='micro')
  * (utils/_metrics.py:90-92) -- without sorting a score: precision and recall at a threshold are fixed by how many
  * positive and how many negative (pixel, class) pairs lie at or above it.

@@ -1,4 +1,4 @@
-"""cae_seg_score_hist on the GPU (csrc/cae_seg_ap.hip) and what is built on it: segmenters.score_histogram,
+"""cae_seg_score_hist on the GPU (csrc/cae_seg_hist.hip) and what is built on it: segmenters.score_histogram,
 SlideCoder.segment_batches(ap_bits=...), zarrio.segment_image(ap_bits=...).
 
 The oracle is the numpy restatement of the contract (tests/seg_ap_oracle.py) on the SAME scores, bit for bit: those that

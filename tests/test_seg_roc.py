@@ -1,4 +1,4 @@
-"""cae_seg_roc_hist on the GPU (csrc/cae_seg_roc.hip) and what is built on it: segmenters.roc_histogram,
+"""cae_seg_roc_hist on the GPU (csrc/cae_seg_hist.hip) and what is built on it: segmenters.roc_histogram,
 SlideCoder.segment_batches(roc_bits=...), zarrio.segment_image(roc_bits=...).
 
 The oracle is the numpy restatement of the contract (tests/seg_roc_oracle.py) on the SAME logits.  Histograms are

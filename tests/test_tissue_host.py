@@ -274,7 +274,8 @@ def test_the_new_kernels_use_no_scratch(built_lib):
     import scratch_check
     mine = re.compile(r'cae12_GLOBAL__N_1\d+mask_[a-z0-9_]+_kernel')  # (namespace cae: not the sampler's mask_rows_kernel)
     table = {k: v for k, v in scratch_check.kernel_table(built_lib).items() if mine.search(k)}
-    assert len(table) == 9 + 4 + 1, sorted(table)  # the downscale for 1..4 channels; the merge step for 4 neighbours
+    assert len(table) == 8 + 4 + 1, sorted(table)  # the downscale for 1..4 channels; the merge step for 4 neighbours
+    assert not any('mask_hist_sum_kernel' in k for k in table)  # (the histogram's partials: seg_histsum_kernel, tests/test_seg_roc_host.py)
     assert all(v == (0, 0) for v in table.values()), table
 
 

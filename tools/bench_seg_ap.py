@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Measure the score histogram kernels (cae_seg_score_hist, csrc/cae_seg_ap.hip) on one device.  A record, no verdict.
+"""Measure the score histogram kernels (cae_seg_score_hist, csrc/cae_seg_hist.hip) on one device.  A record, no verdict.
 
     python tools/bench_seg_ap.py [--out profiles/seg_ap/kernel_times_mi355x.json] [--batch 4x1024] [--classes 2,5,16]
                                  [--bits 11,14]
